@@ -20,12 +20,19 @@ processes itself (``spawn_ranks``: N child processes with the launcher's environ
 never an exec), relays rank 0's JSON line and exits non-zero if any rank fails.  ``--ruiz`` benchmarks BASELINE configs[4]: the sharded
 Ruiz sweeps first (no rank holds the whole LP), then the same timed region on the scaled problem.
 
-Also reports, in the same JSON line:
+A plain run does only what the headline needs: set-up, warm-up, the timed steps (+ the cost of one check, see above), the
+outputs if --dump-outputs is given, the JSON line.  With --full it also reports, in the same JSON line:
   roofline     algorithmic HBM bytes of the dominant kernel per launch / its mean duration (HIP events); `traffic` (PMC bytes per
                launch) and `measured_read_ceiling` (a streaming-read probe of this GPU) are recorded runs from profiles/
+  phases       N > 1: the parts of an iteration (products, all-gathers, all-reduce), each timed alone
   cpu_baseline the CPU oracle (C port, OpenMP) on a bounded sample of the same workload, rank 0, N=1 only
   time_to_tol  the second half of the metric: after the timed region the same LP is solved from zero to --solve-tol (default
                1e-4, the reference's default; every N); "recorded" carries the separately measured 1e-8 runs of profiles/
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, as a caller of the driver would read it: the
+current iterate (x.npy, y.npy; a fixed seeded sample of at most DUMP_MAX_ENTRIES entries each for longer vectors, the sampled
+indices in x_index.npy / y_index.npy) and the step scalars (step.npy: eta, omega), in the vectors' precision.  The inputs
+depend on the arguments alone (generator seed 0, power-iteration seed 0), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -40,6 +47,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
 INFINITY_CACHE_BYTES = 256 << 20   # MI355X_MICROARCH.md: 256 MB of memory-side cache in front of HBM
+DUMP_MAX_ENTRIES = 1 << 20         # --dump-outputs: entries kept per vector (at most 4 x 8.4 MB in all: x, y and their indices)
 
 
 def spawn_ranks(gpus: int, argv, script: str = None, env: dict = None, launch_timeout: float = None, grace: float = None) -> int:
@@ -180,7 +188,52 @@ def parse(argv=None):
                    help="most rows (= columns) of the CPU baseline's sample; the host's free memory may lower it")
     p.add_argument("--kernel-reps", type=int, default=20)
     p.add_argument("--check-periods", type=int, default=5, help="restart periods the cost of one check is averaged over (after the timed region)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: roofline and device probes, per-phase exchange timing (N > 1), "
+                        "time to tolerance, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's iterate (sampled) and step scalars to DIR/<name>.npy")
     return p.parse_args(argv)
+
+
+def sample_index(length: int):
+    """the entries of a vector that --dump-outputs keeps: all of a short one, else a fixed seeded sample (sorted)"""
+    if length <= DUMP_MAX_ENTRIES:
+        return torch.arange(length)
+    g = torch.Generator().manual_seed(0)
+    return torch.randperm(length, generator=g)[:DUMP_MAX_ENTRIES].sort().values
+
+
+def capture_outputs(eng, n: int, m: int) -> dict:
+    """what a caller of the driver reads after the last timed step: the current iterate (the whole vectors of the original LP, every
+    rank's block gathered, then sampled) and the step scalars; numpy arrays in the vectors' precision"""
+    import numpy as np
+    x, y = eng.get_iterate(N.CUR)
+    if eng.comm is not None:
+        fx = torch.zeros(eng.n, dtype=x.dtype, device=x.device)
+        fy = torch.zeros(eng.m, dtype=y.dtype, device=y.device)
+        fx[eng.cols[0]:eng.cols[1]] = x
+        fy[eng.rows[0]:eng.rows[1]] = y
+        eng.comm.all_gather(fx)
+        eng.comm.all_gather(fy)
+        part = getattr(eng, "part", None)
+        x, y = (fx[:n], fy[:m]) if part is None else (part.unpad_cols(fx), part.unpad_rows(fy))
+    out = {}
+    for name, v in (("x", x), ("y", y)):
+        idx = sample_index(v.numel())
+        out[name] = v[idx.to(v.device)].cpu().numpy()
+        if v.numel() > DUMP_MAX_ENTRIES:
+            out[name + "_index"] = idx.numpy().astype(np.float64)
+    s = eng.scalars()
+    out["step"] = np.array([s["eta"], s["omega"]], dtype=np.float64)
+    return out
+
+
+def write_outputs(outputs: dict, directory: str):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def algorithmic_bytes(n, m, nnz, sv, si, adaptive, sm=None):
@@ -705,6 +758,8 @@ def main(argv=None):
         comm.all_reduce_max(tt)
         return float(tt)
 
+    captured = []                                  # --dump-outputs: (elapsed_s, outputs) of every timed region run
+
     def timed_region():
         """warm-up, EXACTLY --steps timed iterations, then the cost of a restart check: one measurement of the headline number on
         whatever drives the exchange right now (a fresh driver from x = y = 0 every time)"""
@@ -728,6 +783,8 @@ def main(argv=None):
         fence()
         elapsed = max_over_ranks(time.time() - t0)
         checks_in, restarts_in = drv.checks - checks0, drv.n - restarts0
+        if args.dump_outputs:                      # (untimed) the state the last timed step left, before the check periods below
+            captured.append((round(elapsed, 6), capture_outputs(eng, args.n, m)))
         # the cost of one restart check INCLUDING the restart work at the rate restarts fire (wall clock, synchronised), measured
         # over the next whole periods: a check that evaluates the previous iterate too costs 2 products more than one that does
         # not, and a restart adds its vector passes -- several periods average that out
@@ -750,10 +807,12 @@ def main(argv=None):
     period, extra, elapsed, norm_elapsed = reg["period"], reg["extra"], reg["elapsed"], reg["norm_elapsed"]
     checks_in, restarts_in, checks_m, restarts_m, check_s = reg["checks_in"], reg["restarts_in"], reg["checks_m"], reg["restarts_m"], reg["check_s"]
 
-    try:
-        roofline = measure_roofline(args, eng, dt, adaptive, world)
-    except Exception as e:          # the headline number must still be reported
-        roofline = {"bound": "hbm", "error": f"{type(e).__name__}: {e}"[:200]}
+    roofline = None
+    if args.full:
+        try:
+            roofline = measure_roofline(args, eng, dt, adaptive, world)
+        except Exception as e:          # the headline number must still be reported
+            roofline = {"bound": "hbm", "error": f"{type(e).__name__}: {e}"[:200]}
 
     out = {
         "metric": "PDHG iterations/sec", "value": round(args.steps / norm_elapsed, 3), "unit": "iterations/s",
@@ -773,9 +832,10 @@ def main(argv=None):
                    "restarts_in_timed_region": restarts_in, "check_ms": round(check_s * 1e3, 3),
                    "check_ms_measured_over": {"checks": checks_m, "restarts": restarts_m},
                    "warmup_done": args.warmup + extra, "normalised_elapsed_s": round(norm_elapsed, 6)},
-        "roofline": roofline,
         "setup_s": round(setup_s, 1),
     }
+    if roofline is not None:
+        out["roofline"] = roofline
     out["config"].update(notes)
     deadman = Deadman(rank)
     if exchange is not None:
@@ -783,13 +843,14 @@ def main(argv=None):
         out["config"]["exchange"] = exchange
         # the headline is measured: from here on every collective runs under a watchdog that prints it (a rank that raises before a
         # collective leaves its peers blocked inside it, and the try/except below would swallow the only trace)
-        snap0 = json.dumps(out)
-        deadman.arm(300.0 + 3.0 * first_region_s, lambda: snap0, "the per-phase timing of the exchange hung")
-        try:
-            out["timing"]["phases"] = exchange_phases(eng, comm, roofline, norm_elapsed / args.steps * 1e3)
-        except Exception as e:
-            out["timing"]["phases"] = {"error": f"{type(e).__name__}: {e}"[:200]}
-        deadman.disarm()
+        if args.full:
+            snap0 = json.dumps(out)
+            deadman.arm(300.0 + 3.0 * first_region_s, lambda: snap0, "the per-phase timing of the exchange hung")
+            try:
+                out["timing"]["phases"] = exchange_phases(eng, comm, roofline, norm_elapsed / args.steps * 1e3)
+            except Exception as e:
+                out["timing"]["phases"] = {"error": f"{type(e).__name__}: {e}"[:200]}
+            deadman.disarm()
         direct = False
         # (also in the one-GPU rehearsal -- PDLP_BENCH_SHARE_GPU=1, gloo through the host: HIP IPC between processes on one card is
         # the same code path)
@@ -804,10 +865,10 @@ def main(argv=None):
             library_phase(out, exchange, eng, args.steps, timed_region, norm_elapsed, rank,
                           limit=float(os.environ.get("PDLP_COMM_TIMEOUT", "90")), first_region_s=first_region_s)
     # from here on (time to tolerance, teardown of the communicators) a hang must not cost the line either
-    if comm is not None:
+    if comm is not None and args.full:
         deadman.arm(args.solve_limit + 600.0, lambda: json.dumps(dict(out, time_to_tol={"error": "abandoned by the watchdog"})),
                     "the phases after the timed region hung")
-    if args.solve_tol > 0:
+    if args.full and args.solve_tol > 0:
         # time to tolerance (untimed part of the run, the engine of the timed region re-started from zero): the reference's default
         # tolerance fits a bench run; tighter ones are separate runs (tools/time_to_tol.py), recorded in profiles/time_to_tol.json
         # (a solve of several minutes says nothing by itself: a line on stderr every minute shows a supervisor that it is alive)
@@ -837,7 +898,7 @@ def main(argv=None):
         except Exception as e:
             out["time_to_tol"] = {"error": f"{type(e).__name__}: {e}"[:200]}
         beat_stop.set()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         del eng
         torch.cuda.empty_cache()
         try:
@@ -845,6 +906,10 @@ def main(argv=None):
         except Exception as e:
             out["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"[:200]}
     deadman.disarm()
+    if rank == 0 and captured:
+        # the timed region the headline was taken on (N > 1: a later phase may have adopted its own region)
+        headline = out["timing"]["elapsed_s"]
+        write_outputs(next((o for e, o in captured if e == headline), captured[0][1]), args.dump_outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if comm is not None:

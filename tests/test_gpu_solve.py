@@ -361,15 +361,15 @@ def test_mixed_precision_with_ruiz_on_a_plus_minus_one_matrix():
 def test_bench_line_contract_on_a_small_workload():
     """bench.py's one JSON line (the driver's contract): metric / value / unit / n_gpus / steps / warmup / ms_per_step / scaling / dtype /
     data / config.workload, the roofline object measured live (bound, achieved, peak, frac, traffic key, the kernel's launch time), the
-    cpu_baseline object (value, cores, kind, sample) and the time-to-tolerance record -- on a 300k x 300k LP so that it takes seconds.
-    The line is the LAST line of stdout and the only one that parses as JSON."""
+    cpu_baseline object (value, cores, kind, sample) and the time-to-tolerance record of a --full run -- on a 300k x 300k LP so that it
+    takes seconds.  The line is the LAST line of stdout and the only one that parses as JSON."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PDLP_BENCH_N="300000", PDLP_BENCH_NNZ="20")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "40", "--warmup", "5", "--cpu-sample-rows", "100000",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "40", "--warmup", "5", "--cpu-sample-rows", "100000",
                         "--solve-limit", "30"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -386,3 +386,37 @@ def test_bench_line_contract_on_a_small_workload():
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "oracle" in cb["sample"] and cb["machine_cores"] >= cb["cores"]
     assert d["time_to_tol"]["tol"] == 1e-4 and d["time_to_tol"]["status"] in ("Solved", "Unsolved (time limit exceeded)")
     assert d["timing"]["checks_in_timed_region"] == 1
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """a plain run (no --full) measures the headline alone -- the same line, without roofline, cpu_baseline or time_to_tol -- and
+    --dump-outputs writes the last timed step's iterate and step scalars; two runs with the same arguments write the same arrays, and
+    --steps sets the timed steps (43: the check that falls due inside them is counted, the missing 0.075 of one is added)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PDLP_BENCH_N="300000", PDLP_BENCH_NNZ="20")
+    env.pop("WORLD_SIZE", None)
+    got = []
+    for rep in range(2):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "43", "--warmup", "5",
+                            "--dump-outputs", str(tmp_path / f"run{rep}")], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert sum(1 for ln in lines if ln.lstrip().startswith("{")) == 1
+        d = json.loads(lines[-1])
+        assert d["metric"] == "PDHG iterations/sec" and d["unit"] == "iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert (d["n_gpus"], d["steps"], d["warmup"]) == (1, 43, 5) and d["timing"]["checks_in_timed_region"] == 1
+        assert d["value"] > 0 and abs(d["ms_per_step"] * d["value"] - 1000.0) < 1.0
+        assert not {"roofline", "cpu_baseline", "time_to_tol"} & set(d)
+        out = tmp_path / f"run{rep}"
+        assert sorted(p.name for p in out.iterdir()) == ["step.npy", "x.npy", "y.npy"]
+        arrays = {k: np.load(out / f"{k}.npy") for k in ("x", "y", "step")}
+        assert arrays["x"].shape == (300000,) and arrays["y"].shape == (300000,) and arrays["step"].shape == (2,)
+        assert arrays["x"].dtype == arrays["y"].dtype == np.float32 and arrays["step"].dtype == np.float64
+        assert all(np.isfinite(a).all() for a in arrays.values()) and np.abs(arrays["x"]).max() > 0 and arrays["step"].min() > 0
+        got.append(arrays)
+    for k in got[0]:
+        np.testing.assert_array_equal(got[0][k], got[1][k], err_msg=k)

@@ -223,8 +223,9 @@ def test_infeasibility_detection_respects_the_pass_cap(golden):
 
 
 def test_bench_command_line_contract(monkeypatch):
-    """the driver's invocations parse (`--gpus N --steps K --warmup W`), the defaults are the metric's configuration, and the
-    second half of the metric (time to tolerance) is part of a default run; the recorded tight-tolerance runs are readable"""
+    """the driver's invocations parse (`--gpus N --steps K --warmup W`), the defaults are the metric's configuration, a plain run
+    measures the headline alone (the second half of the metric, time to tolerance, is part of a --full run), and the recorded
+    tight-tolerance runs are readable"""
     import importlib, json, os, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     monkeypatch.syspath_prepend(root)
@@ -236,13 +237,38 @@ def test_bench_command_line_contract(monkeypatch):
     assert (a.gpus, a.n, a.nnz_per_row, a.mode, a.dtype) == (None, 10_000_000, 100, "adaptive", "f32")   # (None: the launcher's WORLD_SIZE, else 1)
     assert not a.ruiz and a.lib_comm == "auto"
     assert a.solve_tol == 1e-4 and a.solve_limit > 0
+    assert not a.full and a.dump_outputs is None
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "5"])
     a = bench.parse()
     assert (a.gpus, a.steps, a.warmup) == (8, 20, 5)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
     rec = json.load(open(os.path.join(root, "profiles", "time_to_tol.json")))
     assert rec["n10000000_k100"]["1e-8"]["seconds"] < 1200            # inside one GPU call of this pool
     tr = json.load(open(os.path.join(root, "profiles", "traffic.json")))
     assert set(tr["n10000000_k100_f32_adaptive_g1_tiled"]) >= {"primal", "dual"}
+
+
+def test_bench_output_sample_and_files(monkeypatch, tmp_path):
+    """--dump-outputs: a vector up to DUMP_MAX_ENTRIES long is written whole, a longer one as the same seeded sample in every run
+    (sorted, distinct, in range, at most 64 MB in all even in float64), each array as DIR/<name>.npy"""
+    import importlib, os
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    monkeypatch.syspath_prepend(root)
+    bench = importlib.import_module("bench")
+    bench._imports()
+    cap = bench.DUMP_MAX_ENTRIES
+    assert bench.sample_index(1000).tolist() == list(range(1000)) and bench.sample_index(cap).numel() == cap
+    a, b = bench.sample_index(10 * cap + 7), bench.sample_index(10 * cap + 7)
+    assert torch.equal(a, b) and a.numel() == cap and int(a.max()) < 10 * cap + 7
+    assert bool((a[1:] > a[:-1]).all())
+    assert 4 * cap * 8 + 16 <= 64 << 20                  # x, y and their indices in float64, plus the step scalars
+    arrays = {"x": np.arange(5, dtype=np.float32), "step": np.array([0.5, 2.0])}
+    bench.write_outputs(arrays, str(tmp_path / "d"))
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "d" / f"{k}.npy")
+        assert got.dtype == v.dtype and np.array_equal(got, v)
 
 
 def test_offsets_are_64_bit_end_to_end():

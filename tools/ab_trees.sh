@@ -16,7 +16,7 @@ fi
 shift || true
 for rep in 1 2; do
   for tree in . tools/_bin/_reftree; do
-    (cd $tree && python3 bench.py --steps 200 --warmup 40 --no-cpu-baseline --solve-tol 0 "$@" 2>/dev/null | python3 -c "
+    (cd $tree && python3 bench.py --full --steps 200 --warmup 40 --no-cpu-baseline --solve-tol 0 "$@" 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$tree', d['value'], 'it/s; kernels', d['roofline'].get('launch_ms'), d['roofline'].get('other_kernel_ms'), 'ms; check', d['timing']['check_ms'], 'ms')")

@@ -12,7 +12,7 @@ out=gpurun_out/pmc_$tag
 rm -rf "$out" && mkdir -p "$out"
 i=0
 for s in "${sets[@]}"; do
-  rocprofv3 --kernel-trace --pmc $s --output-format csv -d "$out/p$i" -o p -- python3 bench.py --no-cpu-baseline --steps 40 --warmup 3 "$@" > "$out/p$i.log" 2>&1 || { echo "pass $i failed"; tail -5 "$out/p$i.log"; }
+  rocprofv3 --kernel-trace --pmc $s --output-format csv -d "$out/p$i" -o p -- python3 bench.py --full --no-cpu-baseline --steps 40 --warmup 3 "$@" > "$out/p$i.log" 2>&1 || { echo "pass $i failed"; tail -5 "$out/p$i.log"; }
   echo "pass $i done: $s"
   i=$((i+1))
 done

@@ -5,20 +5,21 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 what="${*:-10m 1m neos3 shard phases}"
 log=gpurun_out/r05_measure.log
+res="${log%/*}"          # the folder the batch writes into
 say() { echo "[$(date +%T)] $*" | tee -a "$log"; }
 mkdir -p gpurun_out
 if [[ "$what" == *10m* ]]; then
   say "bench 10M default"
-  timeout -k 10 400 python3 bench.py > gpurun_out/r05_bench_10Mx10M.json 2> gpurun_out/r05_bench_10Mx10M.err || say "bench 10M failed"
+  timeout -k 10 400 python3 bench.py --full > $res/r05_bench_10Mx10M.json 2> $res/r05_bench_10Mx10M.err || say "bench 10M failed"
   say "bench 10M, the driver's flags (--steps 20 --warmup 5)"
-  timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > gpurun_out/r05_bench_10Mx10M_steps20.json 2> gpurun_out/r05_bench_10Mx10M_steps20.err || say "bench 10M steps20 failed"
+  timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $res/r05_bench_10Mx10M_steps20.json 2> $res/r05_bench_10Mx10M_steps20.err || say "bench 10M steps20 failed"
   say "profile 10M (stats + FETCH + WRITE)"
   timeout -k 10 700 bash tools/profile_bench.sh r05_10Mx10M_tiled >> "$log" 2>&1 || say "profile 10M failed"
 fi
 if [[ "$what" == *1m* ]]; then
   export PDLP_BENCH_N=1000000 PDLP_BENCH_NNZ=5
   say "bench 1M x 1M, 5 per row"
-  timeout -k 10 200 python3 bench.py --steps 2000 --warmup 200 > gpurun_out/r05_bench_1Mx1M.json 2> gpurun_out/r05_bench_1Mx1M.err || say "bench 1M failed"
+  timeout -k 10 200 python3 bench.py --full --steps 2000 --warmup 200 > $res/r05_bench_1Mx1M.json 2> $res/r05_bench_1Mx1M.err || say "bench 1M failed"
   say "profile 1M (stats + FETCH + WRITE)"
   timeout -k 10 300 bash tools/profile_bench.sh r05_1Mx1M --solve-tol 0 >> "$log" 2>&1 || say "profile 1M failed"
   say "L2 counters 1M"
