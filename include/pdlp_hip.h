@@ -398,6 +398,48 @@ int pdlp_mv_gap(pdlp_handle h, int nvp, const void* X, const void* Y, void* work
 int pdlp_mv_product(pdlp_handle h, int nvp, const void* X, void* Y);
 int pdlp_mv_combine(int dtype, int64_t rows, int j, const void* V, const void* W, int nw, void* OUT, void* stream);
 
+/* ---- batched solves: B LPs over ONE constraint matrix (pdlp_algorithm_batch, torchpdlp_amd/batch.py) -------------------- */
+/* The LPs share K (the handle's CSR arrays, single GPU, PDLP_F32 or PDLP_F64) and differ in c, q, l, u.  Every population is a
+ * row-major device array [rows][Bp] in the working precision: column b is LP b; Bp = B rounded up to a multiple of the group
+ * width W (8, 16 or 32); a launch covers all Bp / W groups.  c, q, l, u are each one shared vector ([len], *_per_lp = 0) or one
+ * column per LP ([len][Bp], *_per_lp = 1).  The per-LP scalars are [Bp] arrays in the working precision: eta (the step of the
+ * next iteration: eta-hat of the last), omega, eta_sum (weights of the running average), wpend (adaptive: weight of the current
+ * iterate not yet in the sums); live[Bp] (int32): a column with live == 0 is frozen, no call stores into it.  part holds
+ * PDLP_BATCH_PART_PER_COL * Bp doubles of partial sums; out [3][Bp][6] doubles receives the per-LP sums of pdlp_batch_kkt and
+ * pdlp_batch_restart.  No atomics: an LP's results do not depend on B, on its column or on the other LPs (at the same W).
+ * The library allocates nothing: every buffer is the caller's. */
+#define PDLP_BATCH_PART_PER_COL (2 * 4 * 8192)
+typedef struct pdlp_batch {
+    int32_t B, Bp, W;           /* LPs, padded columns (multiple of W), group width 8 | 16 | 32                          */
+    int32_t c_per_lp, q_per_lp, l_per_lp, u_per_lp;   /* 0: shared [len] vector, 1: [len][Bp]                        */
+    const void* c;              /* [n] or [n][Bp]                                                                    */
+    const void* q;              /* [m] or [m][Bp]                                                                    */
+    const void* l;              /* [n] or [n][Bp]  -inf allowed                                                      */
+    const void* u;              /* [n] or [n][Bp]  +inf allowed                                                      */
+    void* x; void* x_prev; void* xbar; void* x_sum; void* x_avg; void* x_last;   /* [n][Bp]                          */
+    void* y; void* y_prev; void* y_sum; void* y_avg; void* y_last; void* dy;     /* [m][Bp]                          */
+    void* eta; void* omega; void* eta_sum; void* wpend;                          /* [Bp]                             */
+    const int32_t* live;        /* [Bp] 1 = running                                                                  */
+    const int32_t* action;      /* [Bp] pdlp_batch_restart: 0 keep, 1 restart at the current, 2 at the averaged iterate */
+    double* part;               /* [PDLP_BATCH_PART_PER_COL * Bp]                                                    */
+    double* out;                /* [3][Bp][6]                                                                        */
+} pdlp_batch;
+/* `iters` PDHG iterations of every live LP, no host synchronisation -- the inner loop pdhg.py:76-112 with
+ * fixed_one_step_pdhg (step.py:3-40) or adaptive_one_step_pdhg (step.py:43-115, one trial: quirk Q1) per column, the weighted
+ * sums x_sum += eta x, y_sum += eta y and eta_sum (pdhg.py:107-109), the previous iterate kept (pdhg.py:77-78).  k0 = the
+ * global iteration count k before the call (the adaptive rule's (k+1)^-0.3, (k+1)^-0.6). */
+int pdlp_batch_iterate(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0);
+/* x_avg = x_sum / eta_sum, y_avg likewise, per live LP (pdhg.py:118-119; adaptive: the current iterate's term is added first) */
+int pdlp_batch_average(pdlp_handle h, const pdlp_batch* b, int adaptive);
+/* compute_residuals_and_duality_gap (helpers.py:53-95) per live LP at PDLP_CUR / PDLP_AVG / PDLP_PREV: out[slot][b][0..5] =
+ * { ||dual residual||^2, l_dual'max(lam,0), u_dual'min(lam,0), c'x, ||primal residual||^2, q'y } (the order of PDLP_BUF_RED);
+ * unscaled != 0: of the un-preconditioned LP from the scaled products and d_col / d_row (pdhg.py:157-163) */
+int pdlp_batch_kkt(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot);
+/* the restarts of action[] (pdhg.py:131-146): the chosen iterate becomes current, sums and eta_sum are zeroed; then
+ * out[slot][b][0..1] = ||x - x_last||^2, ||y - y_last||^2 (primal_weight_update enhancements.py:74-75) and x_last = x,
+ * y_last = y (pdhg.py:63-64) for every LP with action != 0 */
+int pdlp_batch_restart(pdlp_handle h, const pdlp_batch* b, int slot);
+
 /* ---- plain products (power iteration helpers.py:41-51, tests) ------------------------------- */
 /* out_local = K in_full (transpose=0, out has row1-row0 values) or K' in_full (transpose=1) */
 int pdlp_spmv(pdlp_handle h, int transpose, const void* in_full, void* out_local);

@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""Batched solves against the single-LP engine, in one process on one MI355X (torchpdlp_amd/batch.py, pdlp_batch_*).
+
+Rates: LP-iterations per second of ``pdlp_batch_iterate`` for B in --batches, against ``PdlpEngine.iterate`` on the same LP in the
+same run, fixed and adaptive step, on a launch-bound 50k x 50k LP and on BASELINE configs[1] (1M x 1M), both 5 non-zeros per row
+(``gen_lp(..., recipe="box")``, the batch varies q per LP).  Every timed region is warmed up first and ends in a device
+synchronise; the best of --reps repetitions is reported.  End to end: the wall time of ``solve_lp_batch`` on a 32-LP
+``gen_lp_family`` to 1e-4 against 32 sequential ``solve_lp`` calls (50k shape).  Prints one JSON document.
+
+    python tools/bench_batch.py                         # everything
+    python tools/bench_batch.py --shapes 1m --batches 8 --skip-e2e --reps 1   # the rocprofv3 --kernel-trace --stats run
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import torchpdlp_amd as tp
+from torchpdlp_amd.batch import BatchEngine
+
+SHAPES = {"50k": 50_000, "1m": 1_000_000}
+MAX_B = {"50k": 128, "1m": 32}
+
+
+def timed(fn, reps):
+    best = float("inf")
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        best = min(best, time.perf_counter() - t0)
+    return best
+
+
+def bytes_per_lp_iteration(n, m, nnz, B, W, es=4):
+    """the cost model of one fixed-step iteration per LP ("Batched solves"): the two matrices are streamed once per
+    group of W columns and shared by its LPs (8 bytes per item + 8 per row pointer); every item gathers es bytes per LP (in
+    segments of W values); the epilogues stream the LP's columns (primal: read x, x_sum, write x, x_prev, xbar, x_sum; dual: read
+    y, y_sum, q, write y, y_prev, y_sum)"""
+    groups = -(-B // W)
+    matrix = groups * 2 * (nnz * 8 + (n + m) * 8) / B
+    gathers = 2 * nnz * es
+    stream = n * 6 * es + m * 7 * es
+    return dict(matrix=matrix, gathers=gathers, stream=stream, total=matrix + gathers + stream)
+
+
+def rates(shape, batches, steps, reps, warm):
+    rows = SHAPES[shape]
+    dev = torch.device("cuda", 0)
+    lp = tp.gen_lp(rows, rows, 5, seed=0, device=dev)
+    K = tp.CsrPair(lp.m, lp.n, lp.rowptr, lp.colidx, lp.val)
+    out = dict(shape=f"{rows}x{rows}", nnz=int(K.nnz), steps=steps, reps=reps)
+    eng = tp.PdlpEngine.from_full(K, lp.c, lp.q, lp.l, lp.u, lp.m_ineq)
+    sigma = tp.solver.estimate_sigma(eng, power_iters=20, seed=0)
+    eta = 0.9 / sigma
+    single = {}
+    for adaptive in (False, True):
+        eng.set_iterate(torch.zeros(lp.n, device=dev), torch.zeros(lp.m, device=dev))
+        eng.set_step(eta, 1.0, 1.0, 0)
+        eng.iterate(warm, adaptive)
+        single["adaptive" if adaptive else "fixed"] = steps / timed(lambda: eng.iterate(steps, adaptive), reps)
+    out["single_it_per_s"] = single
+    del eng
+    out["batch"] = []
+    g = torch.Generator(device=dev).manual_seed(1)
+    for B in batches:
+        if B > MAX_B[shape]:
+            continue
+        Q = lp.q.view(-1, 1) * (1 + 0.01 * torch.randn(lp.m, B, generator=g, device=dev))
+        be = BatchEngine(K, lp.m_ineq, lp.c, Q, lp.l, lp.u, B)
+        row = dict(B=B, W=be.W, Bp=be.Bp)
+        for adaptive in (False, True):
+            be.start(np.full(B, eta, np.float32), np.ones(B, np.float32))
+            be.iterate(warm, adaptive, 0)
+            k0 = [warm]
+
+            def go():
+                be.iterate(steps, adaptive, k0[0])
+                k0[0] += steps
+            dt = timed(go, reps)
+            key = "adaptive" if adaptive else "fixed"
+            row[f"{key}_lp_it_per_s"] = B * steps / dt
+            row[f"{key}_speedup"] = B * steps / dt / single[key]
+            row[f"{key}_us_per_iteration"] = dt / steps * 1e6
+        model = bytes_per_lp_iteration(lp.n, lp.m, int(K.nnz), B, be.W)
+        row["model_bytes_per_lp_iteration"] = model
+        row["fixed_model_GB_per_s"] = model["total"] * row["fixed_lp_it_per_s"] / 1e9
+        out["batch"].append(row)
+        print(json.dumps(dict(shape=shape, **row)), file=sys.stderr, flush=True)
+        del be
+    return out
+
+
+def end_to_end(B=32, rows=50_000):
+    dev = torch.device("cuda", 0)
+    f = tp.gen_lp_family(rows, rows, 5, B, seed=0)
+    K = tp.CsrPair(f.m, f.n, f.rowptr, f.colidx, f.val).to(dev)
+    C, Q, L, U = (v.to(dev) for v in (f.C, f.Q, f.L, f.U))
+    prob = (C[:, 0], K, Q[:, 0], f.m_ineq, L[:, 0], U[:, 0])
+    tp.solve_lp_batch(prob, C[:, :2], Q[:, :2], L[:, :2], U[:, :2], device=dev, seed=0, max_kkt=200)        # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = tp.solve_lp_batch(prob, C, Q, L, U, device=dev, seed=0, time_limit=600)
+    torch.cuda.synchronize()
+    t_batch = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    seq = [tp.solve_lp((C[:, b], K, Q[:, b], f.m_ineq, L[:, b], U[:, b]), device=dev, seed=0, time_limit=600) for b in range(B)]
+    torch.cuda.synchronize()
+    t_seq = time.perf_counter() - t0
+    rel = lambda a, b: abs(a - b) / (1 + abs(b))
+    return dict(B=B, shape=f"{rows}x{rows}", batch_seconds=t_batch, sequential_seconds=t_seq, speedup=t_seq / t_batch,
+                batch_solved=sum(s == "Solved" for s in res.status), sequential_solved=sum(r.status == "Solved" for r in seq),
+                batch_iterations_max=int(res.iterations.max()), sequential_iterations_sum=int(sum(r.iterations for r in seq)),
+                max_rel_obj_diff_vs_sequential=max(rel(res.objective[b], seq[b].objective) for b in range(B)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="50k,1m")
+    ap.add_argument("--batches", default="1,8,32,128")
+    ap.add_argument("--steps", type=int, default=400)
+    ap.add_argument("--warm", type=int, default=40)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--skip-e2e", action="store_true")
+    a = ap.parse_args()
+    batches = [int(b) for b in a.batches.split(",")]
+    doc = dict(device=torch.cuda.get_device_name(0), dtype="float32", rates={})
+    for s in a.shapes.split(","):
+        doc["rates"][s] = rates(s, batches, a.steps, a.reps, a.warm)
+    if not a.skip_e2e:
+        doc["end_to_end"] = end_to_end()
+    print(json.dumps(doc, indent=1))
+
+
+if __name__ == "__main__":
+    main()

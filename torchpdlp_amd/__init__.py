@@ -14,9 +14,10 @@ from .ops import (KKT_error, adaptive_one_step_pdhg, compute_residuals_and_duali
                   detect_infeasibility, fixed_one_step_pdhg, primal_weight_update, project_lambda_box,
                   spectral_norm_estimate_torch)
 from .precondition import ruiz_precondition                              # noqa: F401
-from .synthetic import SyntheticLP, gen_lp                               # noqa: F401
+from .synthetic import LPFamily, SyntheticLP, gen_lp, gen_lp_family       # noqa: F401
 from .mps import mps_to_standard_form, parse_mps                         # noqa: F401
-from .api import LPResult, solve_lp                                      # noqa: F401
+from .api import BatchResult, LPResult, solve_lp, solve_lp_batch          # noqa: F401
+from .batch import BatchDriver, BatchEngine, batch_decisions, pdlp_algorithm_batch   # noqa: F401
 from .spectral_casting import fishnet, sample_points, spectral_cast      # noqa: F401
 
 __version__ = "0.1.0"

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PDLP_LIB") or os.path.join(_HERE, "libpdlp_hip.so")   # PDLP_LIB: profiling/ablation builds (empty = unset)
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 PDLP_F32, PDLP_F64, PDLP_MIXED = 0, 1, 2
 CUR, AVG, PREV = 0, 1, 2
 (BUF_X_CUR, BUF_X_PREV, BUF_XBAR, BUF_X_AVG, BUF_Y_CUR, BUF_Y_PREV, BUF_Y_AVG, BUF_RED, BUF_X_SUM, BUF_Y_SUM,
@@ -40,6 +40,22 @@ class PdlpTiles(C.Structure):
                 ("rem_rows_n", C.c_int32), ("rem_segs_n", C.c_int32), ("rem_rows", C.c_void_p), ("rem_rptr", C.c_void_p),
                 ("rem_sptr", C.c_void_p), ("rem_col", C.c_void_p), ("rem_val", C.c_void_p), ("rem_work", C.c_void_p),
                 ("rem_extra", C.c_void_p), ("rem_extra_f32", C.c_void_p)]
+
+
+class PdlpBatch(C.Structure):
+    """mirror of ``struct pdlp_batch`` (batched solves over one matrix)"""
+    _fields_ = [("B", C.c_int32), ("Bp", C.c_int32), ("W", C.c_int32),
+                ("c_per_lp", C.c_int32), ("q_per_lp", C.c_int32), ("l_per_lp", C.c_int32), ("u_per_lp", C.c_int32),
+                ("c", C.c_void_p), ("q", C.c_void_p), ("l", C.c_void_p), ("u", C.c_void_p),
+                ("x", C.c_void_p), ("x_prev", C.c_void_p), ("xbar", C.c_void_p), ("x_sum", C.c_void_p), ("x_avg", C.c_void_p),
+                ("x_last", C.c_void_p),
+                ("y", C.c_void_p), ("y_prev", C.c_void_p), ("y_sum", C.c_void_p), ("y_avg", C.c_void_p), ("y_last", C.c_void_p),
+                ("dy", C.c_void_p),
+                ("eta", C.c_void_p), ("omega", C.c_void_p), ("eta_sum", C.c_void_p), ("wpend", C.c_void_p),
+                ("live", C.c_void_p), ("action", C.c_void_p), ("part", C.c_void_p), ("out", C.c_void_p)]
+
+
+BATCH_PART_PER_COL = 2 * 4 * 8192          # PDLP_BATCH_PART_PER_COL
 
 
 # every symbol include/pdlp_hip.h declares: name -> (restype, argtypes)
@@ -106,6 +122,10 @@ SIGNATURES = {
     "pdlp_mv_gap": (_I, [_H, _I, _P, _P, _P, C.POINTER(_D)]),
     "pdlp_mv_product": (_I, [_H, _I, _P, _P]),
     "pdlp_mv_combine": (_I, [_I, _I64, _I, _P, _P, _I, _P, _P]),
+    "pdlp_batch_iterate": (_I, [_H, C.POINTER(PdlpBatch), _I, _I, _I64]),
+    "pdlp_batch_average": (_I, [_H, C.POINTER(PdlpBatch), _I]),
+    "pdlp_batch_kkt": (_I, [_H, C.POINTER(PdlpBatch), _I, _I, _I]),
+    "pdlp_batch_restart": (_I, [_H, C.POINTER(PdlpBatch), _I]),
     "pdlp_spmv": (_I, [_H, _I, _P, _P]),
     "pdlp_power_iteration": (_I, [_H, _P, _I, _P, _P, C.POINTER(_D)]),
     "pdlp_probe_stream_read": (_I, [_P, _I64, _I, _P, C.POINTER(_D)]),

@@ -129,3 +129,117 @@ def _solve_lp_sharded(problem, comm, device, tol, precondition, primal_weight_up
     if precondition:
         x = x * eng.d_col
     return LPResult(gather_solution(eng, x, n).view(-1, 1), obj, k, nr, j, status, total)
+
+
+@dataclass
+class BatchResult:
+    x: torch.Tensor            # (n, B) primal solutions of the ORIGINAL problems (un-scaled when preconditioned)
+    y: torch.Tensor            # (m, B) dual solutions (un-scaled)
+    objective: "np.ndarray"    # (B,) c'x per LP
+    iterations: "np.ndarray"   # (B,) k
+    restarts: "np.ndarray"     # (B,) n
+    kkt_passes: "np.ndarray"   # (B,) j
+    status: list               # B status strings of the reference
+    time: float                # seconds for the whole batch
+
+    def __len__(self):
+        return len(self.status)
+
+    def __getitem__(self, i) -> LPResult:
+        return LPResult(self.x[:, i:i + 1], float(self.objective[i]), int(self.iterations[i]), int(self.restarts[i]),
+                        int(self.kkt_passes[i]), self.status[i], self.time)
+
+
+_BATCH_UNSUPPORTED = ("comm", "fishnet", "infeasibility_detect", "adaptive_retry", "direct_exchange")
+
+
+def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=None, u=None, *, device=None, tol: float = 1e-4,
+                   precondition: bool = False, primal_weight_update: bool = False, adaptive_stepsize: bool = False,
+                   max_kkt: int = 100_000, time_limit: float = 3600, restart_period: int = 40, dtype=torch.float32,
+                   seed: Optional[int] = None, compat: bool = True, x_init=None, y_init=None, trace=None, verbose: bool = False,
+                   group_width: Optional[int] = None, b0=None, **unsupported) -> BatchResult:
+    """Solve B LPs that share ``K`` (and ``m_ineq``) of ``problem`` and differ in ``c``, ``q``, ``l``, ``u`` in one batch.
+
+    ``problem`` (an MPS path or ``(c, K, q, m_ineq, l, u)``) supplies K and the default vectors; each of ``c, q, l, u`` may be
+    omitted, 1-D (shared) or 2-D ``(len, B)`` (one column per LP; the 2-D arguments must agree on B).  Every LP runs through the
+    reference's ``pdlp_algorithm`` with the same flags, its own step sizes, primal weight, restarts and KKT-pass count; ``max_kkt``
+    applies per LP, ``time_limit`` to the whole batch.  With ``precondition`` one Ruiz equilibration of K serves every LP and each
+    column of c, q, l, u is scaled.  ``trace``: a list that receives B dicts (``kkt``, ``omega``, ``restarts``).  Flags of
+    ``solve_lp`` that have no batched form (sharding, fishnet, infeasibility detection, ``adaptive_retry``, the direct exchange,
+    ``precision="mixed"``) raise ``ValueError``."""
+    import numpy as np
+    from .batch import batch_size, pdlp_algorithm_batch
+    for name, v in unsupported.items():
+        if name == "precision":
+            if v is not None:
+                raise ValueError(f"precision={v!r} has no batched form (float32 or float64 through dtype)")
+        elif name in _BATCH_UNSUPPORTED:
+            if v:
+                raise ValueError(f"{name} has no batched form")
+        else:
+            raise TypeError(f"solve_lp_batch() got an unexpected keyword argument {name!r}")
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"unsupported dtype {dtype}")
+    if group_width is not None and group_width not in (8, 16, 32):
+        raise ValueError("group_width must be 8, 16 or 32")
+
+    def shape_of(v):
+        return None if v is None else tuple(v.shape)
+
+    if not isinstance(problem, (str, os.PathLike)):
+        c0, K0, q0, m_ineq0, l0, u0 = problem
+        n0, m0 = len(c0), len(q0)
+        for name, v, ln in (("c", c, n0), ("q", q, m0), ("l", l, n0), ("u", u, n0), ("x_init", x_init, n0), ("y_init", y_init, m0)):
+            _check_batch_arg(name, v, ln)
+    _check_start_width(batch_size(*(torch.as_tensor(v) for v in (c, q, l, u) if v is not None)), x_init, y_init)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if isinstance(problem, (str, os.PathLike)):
+        c0, K, q0, m_ineq, l0, u0 = mps_to_standard_form(os.fspath(problem), device=device, verbose=verbose, compat=compat, dtype=dtype)
+        for name, v, ln in (("c", c, K.n), ("q", q, K.m), ("l", l, K.n), ("u", u, K.n), ("x_init", x_init, K.n), ("y_init", y_init, K.m)):
+            _check_batch_arg(name, v, ln)
+    else:
+        c0, K, q0, m_ineq, l0, u0 = problem
+        K = CsrPair.from_any(K, device=device, dtype=dtype)
+    vec = lambda v, d: (torch.as_tensor(d).reshape(-1) if v is None else torch.as_tensor(v)).to(device=device, dtype=dtype)
+    C_, Q, L, U = vec(c, c0), vec(q, q0), vec(l, l0), vec(u, u0)
+    B = batch_size(C_, Q, L, U)
+    time_used, data_precond, Ks = 0.0, None, K
+    if precondition:                         # main.py:106-110: one equilibration of K, every column of c, q, l, u scaled
+        import time as _time
+        ones_n, ones_m = torch.ones(K.n, dtype=dtype, device=device), torch.ones(K.m, dtype=dtype, device=device)
+        Ks, _, _, _, _, data_precond, time_used = ruiz_precondition(ones_n, K, ones_m, ones_n, ones_n, device=device)
+        t0 = _time.time()
+        D_col, D_row = data_precond[0].to(dtype).view(-1, 1), data_precond[1].to(dtype).view(-1, 1)
+        sc = lambda v, D, op: (op(v.view(-1, 1), D).view(-1) if v.dim() == 1 else op(v, D))
+        C_, Q = sc(C_, D_col, torch.mul), sc(Q, D_row, torch.mul)
+        L, U = sc(L, D_col, torch.div), sc(U, D_col, torch.div)
+        time_used += _time.time() - t0
+    traces = None
+    if trace is not None:
+        traces = [dict(kkt=[], omega=[], restarts=[]) for _ in range(B)]
+    X, Y, obj, k, n, j, status, total = pdlp_algorithm_batch(
+        Ks, m_ineq, C_, Q, L, U, device, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period,
+        precondition=precondition, primal_update=primal_weight_update, adaptive=adaptive_stepsize, data_precond=data_precond,
+        time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init, seed=seed, traces=traces, group_width=group_width,
+        b0=b0)
+    if trace is not None:
+        trace.extend(traces)
+    if precondition:                         # x = D_col x_s, y = D_row y_s (pdhg.py:161-162)
+        X = data_precond[0].view(-1, 1).to(X.dtype) * X
+        Y = data_precond[1].view(-1, 1).to(Y.dtype) * Y
+    return BatchResult(X, Y, np.asarray(obj), np.asarray(k), np.asarray(n), np.asarray(j), status, total)
+
+
+def _check_start_width(B, x_init, y_init):
+    """a 2-D start must have one column per LP (B comes from c, q, l, u)"""
+    for name, v in (("x_init", x_init), ("y_init", y_init)):
+        if v is not None and len(v.shape) == 2 and v.shape[1] != B:
+            raise ValueError(f"{name} has {v.shape[1]} columns for a batch of {B} LPs")
+
+
+def _check_batch_arg(name, v, ln):
+    if v is None:
+        return
+    shape = tuple(v.shape)
+    if len(shape) not in (1, 2) or shape[0] != ln or (len(shape) == 2 and shape[1] < 1):
+        raise ValueError(f"{name} must have shape ({ln},) or ({ln}, B), got {shape}")

@@ -1,0 +1,188 @@
+// pdlp_batch_host.inc -- host side of the batched solves (pdlp_batch_*, include/pdlp_hip.h): launch shapes and the C entry points.
+// Part of pdlp_hip.hip (included at file scope after the other entry points; not a translation unit of its own).
+// Kernels: pdlp_kernel_batch.inc.  Instantiated per (dtype, W, epilogue); every flag (shared or per-LP vectors, the iteration
+// count) is a launch argument.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+int batch_check(pdlp_handle h, const pdlp_batch* b)
+{
+    if (!h || !b) return PDLP_ERR_INVALID;
+    if (b->W != 8 && b->W != 16 && b->W != 32) return PDLP_ERR_INVALID;
+    if (b->B < 1 || b->Bp < b->B || b->Bp % b->W != 0) return PDLP_ERR_INVALID;
+    if (!b->c || !b->q || !b->l || !b->u || !b->x || !b->x_prev || !b->xbar || !b->x_sum || !b->x_avg || !b->x_last || !b->y ||
+        !b->y_prev || !b->y_sum || !b->y_avg || !b->y_last || !b->dy || !b->eta || !b->omega || !b->eta_sum || !b->wpend ||
+        !b->live || !b->action || !b->part || !b->out)
+        return PDLP_ERR_INVALID;
+    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->delta) return PDLP_ERR_STATE;     // single GPU, one precision
+    if (h->p.n < 1 || h->p.m < 1) return PDLP_ERR_INVALID;
+    return PDLP_OK;
+}
+
+// the second set of partials (the adaptive rule needs two at once)
+inline double* batch_part2(const pdlp_batch* b) { return b->part + (size_t)4 * BATCH_MAXG * b->Bp; }
+
+template <typename T, int W, class Epi>
+int batch_mv(pdlp_handle h, const pdlp_batch* b, bool transpose, const T* Vin, const Epi& epi, double* partials)
+{
+    const int rows = (int)(transpose ? h->p.n : h->p.m);
+    const pdlp_problem& p = h->p;
+    const int64_t* rp = transpose ? p.KT_rowptr : p.K_rowptr;
+    const int32_t* ci = transpose ? p.KT_colidx : p.K_colidx;
+    const T* va = (const T*)(transpose ? p.KT_val : p.K_val);
+    const dim3 grid(batch_grid(rows, W), b->Bp / W);
+    hipLaunchKernelGGL((k_batch_mv<T, W, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, b->live, epi, partials);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+int batch_finalize(pdlp_handle h, const pdlp_batch* b, const double* partials, int64_t rows, int na, int slot, int off)
+{
+    hipLaunchKernelGGL(k_batch_finalize, dim3(b->Bp * na), dim3(BLOCK), 0, h->stream, partials,
+                       batch_grid(rows, b->W), b->Bp, na, b->out + (size_t)slot * b->Bp * 6, 6, off);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+#define BATCH_TRY(expr)                          \
+    do {                                         \
+        const int rc_ = (expr);                  \
+        if (rc_ != PDLP_OK) return rc_;          \
+    } while (0)
+
+template <typename T, int W> int batch_iterate_w(pdlp_handle h, const pdlp_batch* b, int iters, bool adaptive, int64_t k0)
+{
+    const int ineq_end = (int)h->p.m_ineq;
+    T *eta = (T*)b->eta, *omega = (T*)b->omega, *eta_sum = (T*)b->eta_sum, *wpend = (T*)b->wpend;
+    for (int it = 0; it < iters; ++it) {
+        if (adaptive) {
+            BPrimal<T, true> ep{(T*)b->x, (T*)b->x_prev, (T*)b->xbar, (T*)b->x_sum, (const T*)b->c, (const T*)b->l, (const T*)b->u,
+                                b->c_per_lp, b->l_per_lp, b->u_per_lp, eta, omega, wpend};
+            BATCH_TRY((batch_mv<T, W>(h, b, true, (const T*)b->y, ep, nullptr)));
+            BDual<T, true> ed{(T*)b->y, (T*)b->y_prev, (T*)b->y_sum, (T*)b->dy, (const T*)b->q, b->q_per_lp, eta, omega, wpend, ineq_end};
+            BATCH_TRY((batch_mv<T, W>(h, b, false, (const T*)b->xbar, ed, b->part)));
+            BDen<T> en{(const T*)b->x, (const T*)b->x_prev};
+            BATCH_TRY((batch_mv<T, W>(h, b, true, (const T*)b->dy, en, batch_part2(b))));
+            hipLaunchKernelGGL(k_batch_adapt<T>, dim3(b->Bp), dim3(BLOCK), 0, h->stream, b->Bp, b->live, b->part,
+                               batch_grid(h->p.m, W), batch_part2(b), batch_grid(h->p.n, W), eta, omega, eta_sum, wpend, k0 + it + 1);
+            HIP_TRY(hipGetLastError());
+        } else {
+            BPrimal<T, false> ep{(T*)b->x, (T*)b->x_prev, (T*)b->xbar, (T*)b->x_sum, (const T*)b->c, (const T*)b->l, (const T*)b->u,
+                                 b->c_per_lp, b->l_per_lp, b->u_per_lp, eta, omega, wpend};
+            BATCH_TRY((batch_mv<T, W>(h, b, true, (const T*)b->y, ep, nullptr)));
+            BDual<T, false> ed{(T*)b->y, (T*)b->y_prev, (T*)b->y_sum, (T*)b->dy, (const T*)b->q, b->q_per_lp, eta, omega, wpend, ineq_end};
+            BATCH_TRY((batch_mv<T, W>(h, b, false, (const T*)b->xbar, ed, nullptr)));
+        }
+    }
+    if (!adaptive && iters > 0) {
+        hipLaunchKernelGGL(k_batch_etasum<T>, dim3(grid_for(b->Bp)), dim3(BLOCK), 0, h->stream, b->Bp, b->live, (const T*)eta, eta_sum, iters);
+        HIP_TRY(hipGetLastError());
+    }
+    return PDLP_OK;
+}
+
+template <typename T> int batch_iterate_t(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0)
+{
+    if (b->W == 8) return batch_iterate_w<T, 8>(h, b, iters, adaptive != 0, k0);
+    if (b->W == 16) return batch_iterate_w<T, 16>(h, b, iters, adaptive != 0, k0);
+    return batch_iterate_w<T, 32>(h, b, iters, adaptive != 0, k0);
+}
+
+template <typename T> int batch_average_t(pdlp_handle h, const pdlp_batch* b, int adaptive)
+{
+    const int64_t tn = h->p.n * (int64_t)b->Bp, tm = h->p.m * (int64_t)b->Bp;
+    auto kern = adaptive ? k_batch_average<T, true> : k_batch_average<T, false>;
+    hipLaunchKernelGGL(kern, dim3(grid_for(tn)), dim3(BLOCK), 0, h->stream, tn, b->Bp, b->live, (T*)b->x_sum, (const T*)b->x,
+                       (T*)b->x_avg, (const T*)b->wpend, (const T*)b->eta_sum);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(kern, dim3(grid_for(tm)), dim3(BLOCK), 0, h->stream, tm, b->Bp, b->live, (T*)b->y_sum, (const T*)b->y,
+                       (T*)b->y_avg, (const T*)b->wpend, (const T*)b->eta_sum);
+    HIP_TRY(hipGetLastError());
+    if (adaptive) {            // the pending terms are in the sums now
+        hipLaunchKernelGGL(k_batch_zero_pending, dim3(grid_for(b->Bp)), dim3(BLOCK), 0, h->stream, b->Bp, b->live, b->wpend, (int)sizeof(T));
+        HIP_TRY(hipGetLastError());
+    }
+    return PDLP_OK;
+}
+
+template <typename T, int W, bool U> int batch_kkt_w(pdlp_handle h, const pdlp_batch* b, int which, int slot)
+{
+    const T* X = (const T*)(which == PDLP_CUR ? b->x : which == PDLP_AVG ? b->x_avg : b->x_prev);
+    const T* Y = (const T*)(which == PDLP_CUR ? b->y : which == PDLP_AVG ? b->y_avg : b->y_prev);
+    BKktDual<T, U> ed{X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp, (const T*)h->p.d_col};
+    BATCH_TRY((batch_mv<T, W>(h, b, true, Y, ed, b->part)));
+    BATCH_TRY(batch_finalize(h, b, b->part, h->p.n, 4, slot, 0));
+    BKktPrimal<T, U> ep{Y, (const T*)b->q, b->q_per_lp, (const T*)h->p.d_row, (int)h->p.m_ineq};
+    BATCH_TRY((batch_mv<T, W>(h, b, false, X, ep, batch_part2(b))));
+    return batch_finalize(h, b, batch_part2(b), h->p.m, 2, slot, 4);
+}
+
+template <typename T> int batch_kkt_t(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot)
+{
+    if (unscaled) {
+        if (b->W == 8) return batch_kkt_w<T, 8, true>(h, b, which, slot);
+        if (b->W == 16) return batch_kkt_w<T, 16, true>(h, b, which, slot);
+        return batch_kkt_w<T, 32, true>(h, b, which, slot);
+    }
+    if (b->W == 8) return batch_kkt_w<T, 8, false>(h, b, which, slot);
+    if (b->W == 16) return batch_kkt_w<T, 16, false>(h, b, which, slot);
+    return batch_kkt_w<T, 32, false>(h, b, which, slot);
+}
+
+template <typename T, int W> int batch_restart_w(pdlp_handle h, const pdlp_batch* b, int slot)
+{
+    const dim3 gn(batch_grid(h->p.n, W), b->Bp / W), gm(batch_grid(h->p.m, W), b->Bp / W);
+    hipLaunchKernelGGL((k_batch_restart<T, W>), gn, dim3(BLOCK), 0, h->stream, (int)h->p.n, b->Bp, b->action, (T*)b->x,
+                       (const T*)b->x_avg, (T*)b->x_sum, (T*)b->x_last, (T*)b->eta_sum, (T*)b->wpend, b->part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((k_batch_restart<T, W>), gm, dim3(BLOCK), 0, h->stream, (int)h->p.m, b->Bp, b->action, (T*)b->y,
+                       (const T*)b->y_avg, (T*)b->y_sum, (T*)b->y_last, (T*)nullptr, (T*)nullptr, batch_part2(b));
+    HIP_TRY(hipGetLastError());
+    BATCH_TRY(batch_finalize(h, b, b->part, h->p.n, 1, slot, 0));
+    return batch_finalize(h, b, batch_part2(b), h->p.m, 1, slot, 1);
+}
+
+template <typename T> int batch_restart_t(pdlp_handle h, const pdlp_batch* b, int slot)
+{
+    if (b->W == 8) return batch_restart_w<T, 8>(h, b, slot);
+    if (b->W == 16) return batch_restart_w<T, 16>(h, b, slot);
+    return batch_restart_w<T, 32>(h, b, slot);
+}
+
+#undef BATCH_TRY
+
+}  // namespace
+
+int pdlp_batch_iterate(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0)
+{
+    if (iters < 0 || k0 < 0) return PDLP_ERR_INVALID;
+    const int rc = batch_check(h, b);
+    if (rc != PDLP_OK) return rc;
+    Range range("pdlp: batch iterations", h->stream);
+    return DISPATCH(h, batch_iterate_t, h, b, iters, adaptive, k0);
+}
+
+int pdlp_batch_average(pdlp_handle h, const pdlp_batch* b, int adaptive)
+{
+    const int rc = batch_check(h, b);
+    if (rc != PDLP_OK) return rc;
+    return DISPATCH(h, batch_average_t, h, b, adaptive);
+}
+
+int pdlp_batch_kkt(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot)
+{
+    if ((which != PDLP_CUR && which != PDLP_AVG && which != PDLP_PREV) || slot < 0 || slot > 2) return PDLP_ERR_INVALID;
+    const int rc = batch_check(h, b);
+    if (rc != PDLP_OK) return rc;
+    if (unscaled && (!h->p.d_col || !h->p.d_row)) return PDLP_ERR_STATE;
+    Range range("pdlp: batch KKT pass", h->stream);
+    return DISPATCH(h, batch_kkt_t, h, b, which, unscaled, slot);
+}
+
+int pdlp_batch_restart(pdlp_handle h, const pdlp_batch* b, int slot)
+{
+    if (slot < 0 || slot > 2) return PDLP_ERR_INVALID;
+    const int rc = batch_check(h, b);
+    if (rc != PDLP_OK) return rc;
+    return DISPATCH(h, batch_restart_t, h, b, slot);
+}

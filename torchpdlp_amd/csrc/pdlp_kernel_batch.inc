@@ -1,0 +1,313 @@
+// pdlp_kernel_batch.inc -- batched solves: B LPs over ONE constraint matrix advanced together (pdlp_batch_*).
+// Part of pdlp_hip.hip (included inside its anonymous namespace; not a translation unit of its own).
+//
+// Populations are row-major V[row][Bp]: column b is LP b, Bp is B rounded up to a multiple of the group width W (8, 16, 32).
+// A launch has gridDim.y = Bp / W; group g serves columns [g W, (g + 1) W).  Inside a wave, W lanes work on a row
+// (lane % W = the LP of the group), 64 / W rows at a time, each lane walking the row's items in CSR order -- the row walk of
+// k_csr_mv: an item reads one coalesced segment of W values of the gathered population.
+//
+// Determinism: no atomics.  Per-LP sums go through fixed-order partials: lanes of equal LP over a wave (xor tree), then the
+// four waves, then the blocks in a fixed tree (batch_block_sum: one workgroup per sum).  gridDim.x is a function of the row
+// count and W only, so an LP's
+// arithmetic does not depend on B, on its position in the batch or on the other LPs.
+//
+// Per-LP device scalars (working precision, [Bp]): eta (the step of the next iteration), omega, eta_sum (of the running
+// average), wpend (adaptive: the weight of the current iterate, added to the sums by the next iteration); live[Bp] (int32):
+// a column with live == 0 is frozen -- no kernel stores into it.
+// ------------------------------------------------------------------------------------------------
+constexpr int BATCH_MAXG = 8192;      // workgroups per group of columns at most (partials: BATCH_MAXG x Bp x 4 doubles per set)
+
+inline int batch_grid(int64_t rows, int W)
+{
+    const int64_t rpb = (int64_t)(BLOCK / 64) * (64 / W);
+    const int64_t g = (rows + rpb - 1) / rpb;
+    return (int)(g < 1 ? 1 : (g > BATCH_MAXG ? BATCH_MAXG : g));
+}
+
+// column `b` of a vector that is either shared ([len], per = 0) or one column per LP ([len][Bp], per = 1)
+#define BCOL(ptr, per, r, at) ((ptr)[(per) ? (at) : (size_t)(r)])
+
+// partials[block][column][NA], column = blockIdx.y * W + lane
+template <int W, int NA> __device__ __forceinline__ void batch_store_partials(const double* acc, double* partials, int Bp)
+{
+    __shared__ double red[BLOCK / 64][W][NA > 0 ? NA : 1];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NA; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int off = 32; off >= W; off >>= 1) v += shfl_xor_t(v, off);
+        if (lane < W) red[wv][lane][k] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < W) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            double t = 0.0;
+            for (int w = 0; w < BLOCK / 64; ++w) t += red[w][threadIdx.x][k];
+            partials[((size_t)blockIdx.x * Bp + blockIdx.y * W + threadIdx.x) * NA + k] = t;
+        }
+    }
+}
+
+// Primal half (step.py:25-30 / :78-82): x+ = clamp(x - tau (c - K'y), l, u), xbar = x+ + (x+ - x), x_prev = x;
+// fixed step: x_sum += eta x+ (pdhg.py:107); adaptive: x_sum += wpend x (the previous iteration's term, its weight is known now)
+template <typename T, bool ADAPT> struct BPrimal {
+    static constexpr int NA = 0;
+    T* X; T* Xprev; T* Xbar; T* Xsum; const T* c; const T* l; const T* u; int cs, ls, us;
+    const T* eta; const T* omega; const T* wpend;
+    __device__ void operator()(int j, size_t at, int b, T kty, double*) const
+    {
+        const T xo = X[at];
+        if (ADAPT) Xsum[at] = Xsum[at] + wpend[b] * xo;
+        const T tau = eta[b] / omega[b];
+        T v = xo - tau * (BCOL(c, cs, j, at) - kty);
+        const T lo = BCOL(l, ls, j, at), hi = BCOL(u, us, j, at);
+        v = v < lo ? lo : v;
+        v = v > hi ? hi : v;
+        X[at] = v;
+        Xprev[at] = xo;
+        Xbar[at] = v + (v - xo);                       // theta = 1 (pdhg.py:27)
+        if (!ADAPT) Xsum[at] = Xsum[at] + eta[b] * v;
+    }
+};
+
+// Dual half (step.py:33-38 / :85-90): y+ = y + sigma (q - K xbar), first m_ineq rows >= 0, y_prev = y; adaptive: dy = y+ - y
+// kept for K'dy and ||dy||^2 partials (step.py:92-100)
+template <typename T, bool ADAPT> struct BDual {
+    static constexpr int NA = ADAPT ? 1 : 0;
+    T* Y; T* Yprev; T* Ysum; T* DY; const T* q; int qs; const T* eta; const T* omega; const T* wpend; int ineq_end;
+    __device__ void operator()(int i, size_t at, int b, T kx, double* acc) const
+    {
+        const T yo = Y[at];
+        if (ADAPT) Ysum[at] = Ysum[at] + wpend[b] * yo;
+        const T sigma = eta[b] * omega[b];
+        T v = yo + sigma * (BCOL(q, qs, i, at) - kx);
+        if (i < ineq_end && v < (T)0) v = (T)0;
+        Y[at] = v;
+        Yprev[at] = yo;
+        if (!ADAPT) {
+            Ysum[at] = Ysum[at] + eta[b] * v;
+        } else {
+            const T d = v - yo;
+            DY[at] = d;
+            acc[0] += (double)d * (double)d;
+        }
+    }
+};
+
+// the adaptive rule's other two sums (step.py:96-100): (K'dy).dx and ||dx||^2; rows of K', gathers dy
+template <typename T> struct BDen {
+    static constexpr int NA = 2;
+    const T* X; const T* Xprev;
+    __device__ void operator()(int j, size_t at, int, T kdy, double* acc) const
+    {
+        const T dx = X[at] - Xprev[at];
+        acc[0] += (double)kdy * (double)dx;
+        acc[1] += (double)dx * (double)dx;
+    }
+};
+
+// KKT, variable side (helpers.py:21-37,75-82,93-95): ||c - K'y - lam||^2, l_dual'max(lam,0), u_dual'min(lam,0), c'x -- the
+// arithmetic of KktDualEpi per column
+template <typename T, bool UNSCALE> struct BKktDual {
+    static constexpr int NA = 4;
+    const T* X; const T* c; const T* l; const T* u; int cs, ls, us; const T* dcol;
+    __device__ void operator()(int j, size_t at, int, T kty, double* acc) const
+    {
+        T cj = BCOL(c, cs, j, at), lo = BCOL(l, ls, j, at), hi = BCOL(u, us, j, at), xj = X[at];
+        T g = cj - kty;
+        if (UNSCALE) {            // K_u'(D_row y) = (K_s'y)/D_col, c_u = c_s/D_col, l_u = l_s D_col, x_u = D_col x
+            const T d = dcol[j];
+            g = g / d; cj = cj / d; lo = lo * d; hi = hi * d; xj = xj * d;
+        }
+        const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
+        T lam;
+        if (ninf && pinf) lam = (T)0;
+        else if (ninf) lam = g < (T)0 ? g : (T)0;
+        else if (pinf) lam = g > (T)0 ? g : (T)0;
+        else lam = g;
+        const T ld = ninf ? (T)0 : lo, ud = pinf ? (T)0 : hi;
+        const T r = g - lam;
+        acc[0] += (double)r * (double)r;
+        acc[1] += (double)ld * (double)(lam > (T)0 ? lam : (T)0);
+        acc[2] += (double)ud * (double)(lam < (T)0 ? lam : (T)0);
+        acc[3] += (double)cj * (double)xj;
+    }
+};
+
+// KKT, constraint side (helpers.py:77,87-91): ||(K x - q) with inequality rows clipped at 0||^2, q'y
+template <typename T, bool UNSCALE> struct BKktPrimal {
+    static constexpr int NA = 2;
+    const T* Y; const T* q; int qs; const T* drow; int ineq_end;
+    __device__ void operator()(int i, size_t at, int, T kx, double* acc) const
+    {
+        T qi = BCOL(q, qs, i, at), yi = Y[at];
+        T r = kx - qi;
+        if (UNSCALE) {            // K_u (D_col x) = (K_s x)/D_row, q_u = q_s/D_row, y_u = D_row y
+            const T d = drow[i];
+            r = r / d; qi = qi / d; yi = yi * d;
+        }
+        if (i < ineq_end && r > (T)0) r = (T)0;
+        acc[0] += (double)r * (double)r;
+        acc[1] += (double)qi * (double)yi;
+    }
+};
+
+// one product of the matrix (rows x cols, CSR) with a population Vin[cols][Bp], the epilogue per (row, live column)
+template <typename T, int W, class Epi>
+__global__ __launch_bounds__(BLOCK) void k_batch_mv(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                    const T* __restrict__ va, const T* __restrict__ Vin, int Bp,
+                                                    const int32_t* __restrict__ live, Epi epi, double* __restrict__ partials)
+{
+    constexpr int RPW = 64 / W;
+    const int lane = threadIdx.x & 63, sub = lane / W;
+    const int b = blockIdx.y * W + lane % W;
+    const int wave = (blockIdx.x * BLOCK + threadIdx.x) >> 6, nwaves = gridDim.x * (BLOCK / 64);
+    double acc[Epi::NA > 0 ? Epi::NA : 1] = {0.0};
+    if (live[b]) {
+        for (int r0 = wave * RPW; r0 < rows; r0 += nwaves * RPW) {
+            const int r = r0 + sub;
+            if (r < rows) {
+                T s = (T)0;
+                const int64_t e = rp[r + 1];
+                for (int64_t p = rp[r]; p < e; ++p) s += va[p] * Vin[(size_t)ci[p] * Bp + b];
+                epi(r, (size_t)r * Bp + b, b, s, acc);
+            }
+        }
+    }
+    if (Epi::NA > 0) batch_store_partials<W, Epi::NA>(acc, partials, Bp);
+}
+
+// sum over g < nblocks of partials[(g * Bp + b) * na + a] by one workgroup, in a fixed order: thread t adds g = t, t + 256, ...
+// in turn, then the lanes of a wave (xor tree) and the four waves in order.  Valid in thread 0.
+__device__ __forceinline__ double batch_block_sum(const double* __restrict__ partials, int nblocks, int Bp, int na, int b, int a)
+{
+    __shared__ double wsum[BLOCK / 64];
+    double s = 0.0;
+    for (int g = threadIdx.x; g < nblocks; g += BLOCK) s += partials[((size_t)g * Bp + b) * na + a];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += shfl_xor_t(s, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    double t = 0.0;
+    for (int w = 0; w < BLOCK / 64; ++w) t += wsum[w];
+    return t;
+}
+
+// out[b * stride + off + a] = sum over blocks of partials[block][b][a], a < na: one workgroup per (b, a)
+__global__ __launch_bounds__(BLOCK) void k_batch_finalize(const double* __restrict__ partials, int nblocks, int Bp, int na,
+                                                          double* __restrict__ out, int stride, int off)
+{
+    const int b = blockIdx.x / na, a = blockIdx.x - b * na;
+    const double s = batch_block_sum(partials, nblocks, Bp, na, b, a);
+    if (threadIdx.x == 0) out[(size_t)b * stride + off + a] = s;
+}
+
+// adaptive_one_step_pdhg's step-size rule per LP (step.py:92-115, one trial: quirk Q1), then the bookkeeping of pdhg.py:107-112:
+// the step just taken gets weight eta_w (added to the sums by the next iteration, wpend), eta_sum += eta_w, eta = eta'.
+// One workgroup per LP: it reduces the LP's three partial sums, thread 0 applies the rule.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_batch_adapt(int Bp, const int32_t* __restrict__ live, const double* __restrict__ part_dy,
+                                                       int gm, const double* __restrict__ part_den, int gn, T* eta,
+                                                       const T* __restrict__ omega, T* eta_sum, T* wpend, int64_t k)
+{
+    const int b = blockIdx.x;
+    if (!live[b]) return;                       // (uniform over the workgroup)
+    const double dyy = batch_block_sum(part_dy, gm, Bp, 1, b, 0);
+    const double dkd = batch_block_sum(part_den, gn, Bp, 2, b, 0);
+    const double dxx = batch_block_sum(part_den, gn, Bp, 2, b, 1);
+    if (threadIdx.x != 0) return;
+    const T e = eta[b], om = omega[b];
+    const T den = (T)2 * (T)dkd;                                          // step.py:96
+    T eta_bar, t1;
+    if (den != (T)0) {                                                    // step.py:99-102
+        const T nx = (T)sqrt(dxx), ny = (T)sqrt(dyy);
+        const T num = om * (nx * nx) + (ny * ny) / om;
+        eta_bar = num / (T)fabs((double)den);
+        t1 = (T)(1.0 - pow((double)(k + 1), -0.3)) * eta_bar;
+    } else {                                                              // step.py:104-105
+        eta_bar = (T)INFINITY;
+        t1 = (T)INFINITY;
+    }
+    const T t2 = (T)(1.0 + pow((double)(k + 1), -0.6)) * e;              // step.py:107
+    const T ep = t1 < t2 ? t1 : t2;                                       // step.py:108
+    const T ew = e <= eta_bar ? e : ep;                                   // step.py:110-115
+    eta_sum[b] = eta_sum[b] + ew;
+    wpend[b] = ew;
+    eta[b] = ep;
+}
+
+// fixed step: eta_sum += eta, `iters` times (pdhg.py:109; eta does not change)
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_batch_etasum(int Bp, const int32_t* __restrict__ live, const T* __restrict__ eta, T* eta_sum, int iters)
+{
+    for (int b = blockIdx.x * BLOCK + threadIdx.x; b < Bp; b += gridDim.x * BLOCK) {
+        if (!live[b]) continue;
+        T s = eta_sum[b];
+        const T e = eta[b];
+        for (int i = 0; i < iters; ++i) s = s + e;
+        eta_sum[b] = s;
+    }
+}
+
+// averaged iterate (pdhg.py:118-119): [adaptive: the current iterate's pending term first] V_avg = V_sum / eta_sum
+template <typename T, bool ADAPT>
+__global__ __launch_bounds__(BLOCK) void k_batch_average(int64_t total, int Bp, const int32_t* __restrict__ live, T* Vsum,
+                                                         const T* __restrict__ V, T* __restrict__ Vavg, const T* __restrict__ wpend,
+                                                         const T* __restrict__ eta_sum)
+{
+    for (int64_t at = (int64_t)blockIdx.x * BLOCK + threadIdx.x; at < total; at += (int64_t)gridDim.x * BLOCK) {
+        const int b = (int)(at % Bp);
+        if (!live[b]) continue;
+        T s = Vsum[at];
+        if (ADAPT) {
+            s = s + wpend[b] * V[at];
+            Vsum[at] = s;
+        }
+        Vavg[at] = s / eta_sum[b];
+    }
+}
+
+__global__ void k_batch_zero_pending(int Bp, const int32_t* __restrict__ live, void* wpend, int es)
+{
+    for (int b = blockIdx.x * BLOCK + threadIdx.x; b < Bp; b += gridDim.x * BLOCK)
+        if (live[b]) {
+            if (es == 4) ((float*)wpend)[b] = 0.0f;
+            else ((double*)wpend)[b] = 0.0;
+        }
+}
+
+// restarts per LP (pdhg.py:131-146,150-151,58-64): act 0 keep, 1 restart at the current iterate, 2 at the average (which becomes
+// current).  A restarted column: sums zeroed, partial of ||v - v_last||^2 (enhancements.py:74-75), v_last = v (mark).  With
+// eta_sum / wpend given (the x launch), the LP's eta_sum and pending weight are zeroed as well.
+template <typename T, int W>
+__global__ __launch_bounds__(BLOCK) void k_batch_restart(int rows, int Bp, const int32_t* __restrict__ act, T* V,
+                                                         const T* __restrict__ Vavg, T* Vsum, T* Vlast, T* eta_sum, T* wpend,
+                                                         double* __restrict__ partials)
+{
+    constexpr int RPW = 64 / W;
+    const int lane = threadIdx.x & 63, sub = lane / W;
+    const int b = blockIdx.y * W + lane % W;
+    const int wave = (blockIdx.x * BLOCK + threadIdx.x) >> 6, nwaves = gridDim.x * (BLOCK / 64);
+    const int a = act[b];
+    double acc[1] = {0.0};
+    if (a != 0) {
+        for (int r = wave * RPW + sub; r < rows; r += nwaves * RPW) {
+            const size_t at = (size_t)r * Bp + b;
+            const T v = a == 2 ? Vavg[at] : V[at];
+            if (a == 2) V[at] = v;
+            Vsum[at] = (T)0;
+            const T d = v - Vlast[at];
+            acc[0] += (double)d * (double)d;
+            Vlast[at] = v;
+        }
+        if (eta_sum && wave == 0 && sub == 0) {
+            eta_sum[b] = (T)0;
+            wpend[b] = (T)0;
+        }
+    }
+    batch_store_partials<W, 1>(acc, partials, Bp);
+}
+#undef BCOL

@@ -212,3 +212,73 @@ def csr_to_dense(lp: SyntheticLP) -> torch.Tensor:
     K = torch.zeros(lp.m, lp.n, dtype=lp.val.dtype, device=lp.val.device)
     K.index_put_((rows, lp.colidx.long()), lp.val, accumulate=True)
     return K
+
+
+@dataclass
+class LPFamily:
+    """B LPs over one matrix: ``min C[:, b]'x, K[:m_ineq]x >= Q[:m_ineq, b], K[m_ineq:]x = Q[m_ineq:, b], L[:, b] <= x <= U[:, b]``,
+    each with a known primal-dual optimal pair (``X_opt[:, b]``, ``Y_opt[:, b]``) and optimal objective ``opt_obj[b]``."""
+    m: int
+    n: int
+    m_ineq: int
+    rowptr: torch.Tensor   # int64 [m+1]
+    colidx: torch.Tensor   # int32 [nnz]
+    val: torch.Tensor      # dtype [nnz]
+    C: torch.Tensor        # [n, B]
+    Q: torch.Tensor        # [m, B]
+    L: torch.Tensor        # [n, B]  -inf allowed
+    U: torch.Tensor        # [n, B]  +inf allowed
+    X_opt: torch.Tensor    # [n, B]
+    Y_opt: torch.Tensor    # [m, B]
+    opt_obj: list          # B floats
+
+    @property
+    def B(self) -> int:
+        return int(self.C.shape[1])
+
+
+def gen_lp_family(n: int, m: int, nnz_per_row: int, B: int, seed: int = 0, dtype=torch.float32, device="cpu",
+                  ineq_frac: float = 0.8) -> LPFamily:
+    """One K of the "mixed" recipe and B columns (c, q, l, u), each drawn with that recipe's complementary-slackness construction
+    from a generator of its own (seed, column): all four bound classes of project_lambda_box, an optimal pair built in."""
+    device = torch.device(device)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    k = int(nnz_per_row)
+    m_ineq = int(round(ineq_frac * m))
+    col = _regular_pattern(m, n, k, gen, device, 1 << 20)
+    rowptr = torch.arange(0, (m + 1) * k, k, dtype=torch.int64, device=device)
+    val = torch.randn(m * k, generator=gen, device=device, dtype=torch.float64).to(dtype)
+    cols = {key: [] for key in ("c", "q", "l", "u", "x", "y")}
+    objs = []
+    for b in range(int(B)):
+        g = torch.Generator(device=device)
+        g.manual_seed(int(seed) * 1_000_003 + 7919 * (b + 1))
+        U_ = lambda cnt, lo, hi: torch.rand(cnt, generator=g, device=device, dtype=torch.float64) * (hi - lo) + lo
+        cls = torch.multinomial(torch.tensor([0.4, 0.3, 0.15, 0.15], device=device), n, replacement=True, generator=g)
+        x = U_(n, -2.0, 2.0)
+        at_bound = torch.rand(n, generator=g, device=device) < 0.5
+        gap_lo = torch.where(at_bound, torch.zeros(n, dtype=torch.float64, device=device), U_(n, 0.1, 2.0))
+        gap_hi = U_(n, 0.1, 2.0)
+        inf = torch.full((n,), float("inf"), dtype=torch.float64, device=device)
+        lo, hi = x - gap_lo, x + gap_hi
+        hi = torch.where(cls == 2, x + gap_lo, hi)
+        lo = torch.where((cls == 2) | (cls == 3), -inf, lo)
+        hi = torch.where((cls == 1) | (cls == 3), inf, hi)
+        lam_mag = U_(n, 0.1, 1.0)
+        lam = torch.zeros(n, dtype=torch.float64, device=device)
+        lam = torch.where(at_bound & ((cls == 0) | (cls == 1)), lam_mag, lam)
+        lam = torch.where(at_bound & (cls == 2), -lam_mag, lam)
+        kx = _regular_matvec(col, val, x, m, k, 1 << 20)
+        active = torch.rand(m, generator=g, device=device) < 0.5
+        slack = torch.where(active, torch.zeros(m, dtype=torch.float64, device=device), U_(m, 0.1, 2.0))
+        q = kx.clone()
+        q[:m_ineq] -= slack[:m_ineq]
+        y = torch.randn(m, generator=g, device=device, dtype=torch.float64)
+        y[:m_ineq] = torch.where(active[:m_ineq], y[:m_ineq].abs(), torch.zeros_like(y[:m_ineq]))
+        c = _regular_rmatvec(col, val, y, m, n, k, 1 << 20) + lam
+        objs.append(float((c * x).sum()))
+        for key, v in (("c", c), ("q", q), ("l", lo), ("u", hi), ("x", x), ("y", y)):
+            cols[key].append(v)
+    st = lambda key: torch.stack(cols[key], dim=1).to(dtype)
+    return LPFamily(m, n, m_ineq, rowptr, col, val, st("c"), st("q"), st("l"), st("u"), st("x"), st("y"), objs)
