@@ -11,7 +11,7 @@ import torch
 
 from .mps import mps_to_standard_form
 from .precondition import ruiz_precondition
-from .solver import pdlp_algorithm
+from .solver import is_mixed, pdlp_algorithm, resolve_device
 from .sparse import CsrPair
 
 
@@ -51,23 +51,20 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     stores its block straight into the other ranks' memory over HIP IPC / xGMI (``PdlpEngine.enable_peer_exchange``, DESIGN.md
     section 5); connected and cross-checked against the collective-driven loop first, which stays in charge if anything differs.
     """
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if precision is not None:
-        if precision != "mixed":
-            raise ValueError(f"unknown precision {precision!r}")
+    device = resolve_device(device)
+    if is_mixed(precision):
         dtype = torch.float64
+    # what pdlp_algorithm and run_pdlp are both told, under their names for it
+    run = dict(max_kkt=max_kkt, tol=tol, restart_period=restart_period, precondition=precondition, primal_update=primal_weight_update,
+               adaptive=adaptive_stepsize, time_limit=time_limit, trace=trace, infeasibility_detect=infeasibility_detect,
+               infeas_tol=infeas_tol, adaptive_retry=adaptive_retry)
     if comm is not None and not fishnet:
         from .engine import Comm
         cm = Comm() if comm is True else comm
         if cm.world > 1:
-            return _solve_lp_sharded(problem, cm, device, tol, precondition, primal_weight_update, adaptive_stepsize, max_kkt, time_limit,
-                                     verbose, restart_period, dtype, seed, compat, x_init, y_init, trace, infeasibility_detect,
-                                     infeas_tol, precision, adaptive_retry, direct_exchange)
-    if isinstance(problem, (str, os.PathLike)):
-        c, K, q, m_ineq, l, u = mps_to_standard_form(os.fspath(problem), device=device, verbose=verbose, compat=compat, dtype=dtype)
-    else:
-        c, K, q, m_ineq, l, u = problem
-        K = CsrPair.from_any(K, device=device, dtype=dtype)
+            return _solve_lp_sharded(problem, cm, device, run, dtype=dtype, verbose=verbose, seed=seed, compat=compat, x_init=x_init,
+                                     y_init=y_init, precision=precision, direct_exchange=direct_exchange)
+    c, K, q, m_ineq, l, u = load_problem(problem, device, dtype, verbose, compat)
     time_used, data_precond = 0.0, None
     Ks, cs, qs, ls, us = K, c, q, l, u
     if precondition:                                                    # main.py:106-110
@@ -80,31 +77,32 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
         x_init, y_init = spectral_cast(Ks, cs, qs, ls, us, m_ineq, k=32, device=device, generator=gen)
         time_used += _time.time() - t0
     x, obj, k, n, j, status, total = pdlp_algorithm(
-        Ks, m_ineq, cs, qs, ls, us, device, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period,
-        precondition=precondition, primal_update=primal_weight_update, adaptive=adaptive_stepsize,
-        data_precond=data_precond, time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init, seed=seed,
-        trace=trace, comm=comm, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol, precision=precision,
-        adaptive_retry=adaptive_retry)
+        Ks, m_ineq, cs, qs, ls, us, device, verbose=verbose, data_precond=data_precond, time_used=time_used, x_init=x_init,
+        y_init=y_init, seed=seed, comm=comm, precision=precision, **run)
     if precondition:        # the reference returns the scaled iterate (quirk Q4); solve_lp un-scales: x = D_col x_s (pdhg.py:161)
         x = data_precond[0].view(-1, 1).to(x.dtype) * x
     return LPResult(x, obj, k, n, j, status, total)
 
 
-def _solve_lp_sharded(problem, comm, device, tol, precondition, primal_weight_update, adaptive_stepsize, max_kkt, time_limit, verbose,
-                      restart_period, dtype, seed, compat, x_init, y_init, trace, infeasibility_detect, infeas_tol, precision,
-                      adaptive_retry=False, direct_exchange=False) -> LPResult:
+def load_problem(problem, device, dtype, verbose=False, compat=True):
+    """``(c, K, q, m_ineq, l, u)`` with ``K`` a ``CsrPair`` from an MPS path or from such a tuple with ``K`` dense / COO /
+    scipy-sparse / ``CsrPair``.  ``device=None``: a file is read to the host, given arrays stay where the caller has them."""
+    if isinstance(problem, (str, os.PathLike)):
+        return mps_to_standard_form(os.fspath(problem), device="cpu" if device is None else device, verbose=verbose, compat=compat,
+                                    dtype=dtype)
+    c, K, q, m_ineq, l, u = problem
+    return c, CsrPair.from_any(K, device=device, dtype=dtype), q, m_ineq, l, u
+
+
+def _solve_lp_sharded(problem, comm, device, run, *, dtype, verbose, seed, compat, x_init, y_init, precision, direct_exchange) -> LPResult:
     """``solve_lp`` over the ranks of ``comm``: the problem is read (or taken) on the host by every rank, cut into blocks balanced
     by non-zeros, and only this rank's blocks go to its GPU; Ruiz (enhancements.py:4-71) runs on the shards, the solve is
-    ``run_pdlp`` on the sharded engine (pdhg.py:7-181), and every rank returns the full un-scaled solution."""
+    ``run_pdlp`` (with the options ``run``) on the sharded engine (pdhg.py:7-181), and every rank returns the full un-scaled solution."""
     from .distributed import engine_from_shard, gather_solution, shard_arrays
     from .solver import run_pdlp
     from .sparse import as_vec
-    if isinstance(problem, (str, os.PathLike)):
-        c, K, q, m_ineq, l, u = mps_to_standard_form(os.fspath(problem), device="cpu", verbose=verbose and comm.rank == 0, compat=compat,
-                                                     dtype=dtype)
-    else:
-        c, K, q, m_ineq, l, u = problem
-        K = CsrPair.from_any(K, dtype=dtype)             # (where the caller has it: host or device)
+    verbose = verbose and comm.rank == 0
+    c, K, q, m_ineq, l, u = load_problem(problem, None, dtype, verbose, compat)
     n, m = K.n, K.m
     sh = shard_arrays(K, c, q, l, u, m_ineq, comm.rank, comm.world, vec_dtype=dtype, balance="nnz")
     part = sh["part"]
@@ -112,21 +110,19 @@ def _solve_lp_sharded(problem, comm, device, tol, precondition, primal_weight_up
     mv = lambda v: tuple(one(t) for t in v) if isinstance(v, tuple) else one(v)
     sh = {k: (v if k == "part" else mv(v)) for k, v in sh.items() if v is not None}
     del K
-    eng = engine_from_shard(sh, comm, precision=precision, precondition=precondition)
+    eng = engine_from_shard(sh, comm, precision=precision, precondition=run["precondition"])
     time_used = float(getattr(eng, "ruiz_seconds", 0.0))
     if direct_exchange:            # (every rank asks; the ranks agree on every step, and on any failure all stay on the loop)
         on = eng.enable_peer_exchange()
-        if verbose and comm.rank == 0:
+        if verbose:
             print("direct exchange:", "on" if on else "declined", "--", "; ".join(eng.peer_log))
     vdt = eng.dtype
     if x_init is not None and y_init is not None:          # full vectors in (of the scaled problem when preconditioned, like the
         x_init = part.pad_cols(as_vec(x_init, n, device, vdt))[eng.cols[0]:eng.cols[1]]    # one-GPU path and main.py:114-130);
         y_init = part.pad_rows(as_vec(y_init, m, device, vdt))[eng.rows[0]:eng.rows[1]]    # this rank's blocks of the padded layout on
-    x, obj, k, nr, j, status, total = run_pdlp(eng, max_kkt, tol, verbose and comm.rank == 0, restart_period, precondition,
-                                               primal_weight_update, adaptive_stepsize, time_limit, time_used, x_init, y_init,
-                                               seed=0 if seed is None else seed, trace=trace,
-                                               infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol, adaptive_retry=adaptive_retry)
-    if precondition:
+    x, obj, k, nr, j, status, total = run_pdlp(eng, verbose=verbose, time_used=time_used, x_init=x_init, y_init=y_init,
+                                               seed=0 if seed is None else seed, **run)
+    if run["precondition"]:
         x = x * eng.d_col
     return LPResult(gather_solution(eng, x, n).view(-1, 1), obj, k, nr, j, status, total)
 
@@ -183,23 +179,18 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     if group_width is not None and group_width not in (8, 16, 32):
         raise ValueError("group_width must be 8, 16 or 32")
 
-    def shape_of(v):
-        return None if v is None else tuple(v.shape)
-
-    if not isinstance(problem, (str, os.PathLike)):
-        c0, K0, q0, m_ineq0, l0, u0 = problem
-        n0, m0 = len(c0), len(q0)
+    def check_lengths(n0, m0):
         for name, v, ln in (("c", c, n0), ("q", q, m0), ("l", l, n0), ("u", u, n0), ("x_init", x_init, n0), ("y_init", y_init, m0)):
             _check_batch_arg(name, v, ln)
+
+    from_file = isinstance(problem, (str, os.PathLike))
+    if not from_file:                        # given arrays say their lengths before any device work, a file once it is read
+        check_lengths(len(problem[0]), len(problem[2]))
     _check_start_width(batch_size(*(torch.as_tensor(v) for v in (c, q, l, u) if v is not None)), x_init, y_init)
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if isinstance(problem, (str, os.PathLike)):
-        c0, K, q0, m_ineq, l0, u0 = mps_to_standard_form(os.fspath(problem), device=device, verbose=verbose, compat=compat, dtype=dtype)
-        for name, v, ln in (("c", c, K.n), ("q", q, K.m), ("l", l, K.n), ("u", u, K.n), ("x_init", x_init, K.n), ("y_init", y_init, K.m)):
-            _check_batch_arg(name, v, ln)
-    else:
-        c0, K, q0, m_ineq, l0, u0 = problem
-        K = CsrPair.from_any(K, device=device, dtype=dtype)
+    device = resolve_device(device)
+    c0, K, q0, m_ineq, l0, u0 = load_problem(problem, device, dtype, verbose, compat)
+    if from_file:
+        check_lengths(K.n, K.m)
     vec = lambda v, d: (torch.as_tensor(d).reshape(-1) if v is None else torch.as_tensor(v)).to(device=device, dtype=dtype)
     C_, Q, L, U = vec(c, c0), vec(q, q0), vec(l, l0), vec(u, u0)
     B = batch_size(C_, Q, L, U)

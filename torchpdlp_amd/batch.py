@@ -18,10 +18,12 @@ import torch
 
 from . import _native as N
 from .engine import PdlpEngine
-from .solver import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, _np_t, estimate_sigma, primal_weight_from_distances)
+from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, kkt_error, kkt_from_sums, np_type, primal_weight,
+                    restart_decision, start_eta, start_omega, terminated)
+from .solver import estimate_sigma, precond_factors, resolve_device
 from .sparse import CsrPair
 
-BETA = (0.2, 0.8, 0.36)                      # pdhg.py:28
+batch_decisions, kkt_finish, termination = restart_decision, kkt_from_sums, terminated      # (their earlier names)
 _DT = {torch.float32: N.PDLP_F32, torch.float64: N.PDLP_F64}
 
 
@@ -32,59 +34,6 @@ def group_width(B: int, dtype) -> int:
         if B <= w or w == cap:
             return w
     return cap
-
-
-def kkt_finish(red: np.ndarray, omega: np.ndarray, t=np.float32) -> dict:
-    """helpers.py:84-106 per LP from the six sums of a KKT pass (``red`` [B, 6] in the order of PDLP_BUF_RED), in the working
-    precision -- the vectorised form of the library's kkt_finish"""
-    p, d, lp, un = (red[:, i].astype(t) for i in (3, 5, 1, 2))
-    adj = (d + lp + un).astype(t)
-    gap = (adj - p).astype(t)
-    pr, dr = np.sqrt(red[:, 4]).astype(t), np.sqrt(red[:, 0]).astype(t)
-    res = dict(pr=pr, dr=dr, gap=gap, p=p, d_adj=adj)
-    res["kkt"] = kkt_reweight(res, omega, t)
-    return res
-
-
-def kkt_reweight(res: dict, omega: np.ndarray, t=np.float32) -> np.ndarray:
-    """``kkt_from_residuals`` per LP: the KKT error of known residuals under omega (helpers.py:98-108, pdhg.py:153)"""
-    w = np.asarray(omega).astype(t)
-    w2 = (w * w).astype(t)
-    pr, dr, gap = res["pr"], res["dr"], res["gap"]
-    return np.sqrt((w2 * (pr * pr) + (dr * dr) / w2 + gap * gap).astype(t)).astype(t)
-
-
-def termination(res: dict, q_norm, c_norm, tol, t=np.float32) -> np.ndarray:
-    """``check_termination`` (helpers.py:110-128) per LP; the gap is signed (quirk Q2)"""
-    tol, one = t(tol), t(1)
-    c1 = res["pr"] <= tol * (one + q_norm)
-    c2 = res["dr"] <= tol * (one + c_norm)
-    c3 = res["gap"] <= tol * (one + np.abs(res["p"]) + np.abs(res["d_adj"]))
-    return c1 & c2 & c3
-
-
-def batch_decisions(kkt_cur, kkt_avg, kkt_prev, kkt_first, tt, k, j, live, max_kkt, t=np.float32) -> dict:
-    """The restart decisions of one check (pdhg.py:115-146) and the KKT-pass cap (pdhg.py:54,67) per LP, over arrays.
-
-    ``kkt_*`` are the KKT errors at the current, averaged and previous iterates, ``kkt_first`` the one of the last restart point
-    (0 before the first restart: the first check can only restart artificially), ``tt`` the iterations since the last restart,
-    ``k`` the iteration count, ``j`` the KKT-pass count AFTER the check's three passes.  Returns ``crit`` (-1 none, 0 sufficient,
-    1 necessary, 2 artificial), ``use_avg``, ``capped`` (no restart, and ``j`` has reached ``max_kkt``: the reference leaves the
-    inner loop and continues at pdhg.py:148 from the current iterate) and ``action`` (0 keep, 1 restart at the current iterate,
-    2 at the average).  Dead LPs get -1 / False / 0."""
-    kc, ka, kp, kf = (np.asarray(a, dtype=t) for a in (kkt_cur, kkt_avg, kkt_prev, kkt_first))
-    live = np.asarray(live, dtype=bool)
-    k_min = np.minimum(kc, ka)
-    use_avg = (kc >= ka) & live
-    suff = k_min <= t(BETA[0]) * kf
-    nec = (k_min <= t(BETA[1]) * kf) & (k_min > kp)
-    art = np.asarray(tt, dtype=np.float64) >= BETA[2] * np.asarray(k, dtype=np.float64)
-    crit = np.where(suff, 0, np.where(nec, 1, np.where(art, 2, -1)))
-    crit = np.where(live, crit, -1)
-    restart = crit >= 0
-    capped = live & ~restart & (np.asarray(j) >= max_kkt)
-    action = np.where(restart, np.where(use_avg, 2, 1), np.where(capped, 1, 0))
-    return dict(crit=crit, use_avg=use_avg, capped=capped, action=action.astype(np.int32))
 
 
 class BatchEngine:
@@ -190,7 +139,7 @@ class BatchDriver:
         self.be, self.period = be, int(restart_period)
         self.primal_update, self.adaptive, self.precondition = bool(primal_update), bool(adaptive), bool(precondition)
         self.tol, self.max_kkt, self.traces = tol, int(max_kkt), traces
-        self.t = t = _np_t(be.dtype)
+        self.t = t = np_type(be.dtype)
         B = be.B
         self.q_norm, self.c_norm = np.asarray(q_norm, t), np.asarray(c_norm, t)
         self.k, self.n, self.j, self.tt = (np.zeros(B, np.int64) for _ in range(4))
@@ -203,11 +152,8 @@ class BatchDriver:
 
     def start(self, sigma, x_init=None, y_init=None):
         t = self.t
-        eta = t(0.9) / t(sigma)                                              # pdhg.py:22
-        ok = (self.q_norm > 1e-6) & (self.c_norm > 1e-6)                     # pdhg.py:23
-        with np.errstate(divide="ignore", invalid="ignore"):
-            self.omega = np.where(ok, self.c_norm / self.q_norm, t(1.0)).astype(t)
-        self.be.start(np.full(self.be.B, eta, t), self.omega, x_init, y_init)
+        self.omega = start_omega(self.q_norm, self.c_norm, t)                # pdhg.py:23
+        self.be.start(np.full(self.be.B, start_eta(sigma, t), t), self.omega, x_init, y_init)     # pdhg.py:22
 
     def _finish(self, idx, status):
         for i in idx:
@@ -216,45 +162,57 @@ class BatchDriver:
 
     def step(self, time_left: bool = True):
         """one segment: iterations up to the next check (or the first LP's KKT-pass cap), then the check and the restarts"""
-        be, t, B = self.be, self.t, self.be.B
         live = self.live.copy()
+        if not self._segment(live, time_left):
+            return
+        if self.k_global % self.period == 0:                                 # pdhg.py:115 (tt = k mod period for every live LP)
+            action, capped, chosen = self._restart_check(live)
+        else:                                                                # only the cap ends an inner loop between checks
+            capped = live & (self.j >= self.max_kkt)
+            action, chosen = np.where(capped, 1, 0).astype(np.int32), None
+        if action.any():
+            self._after_restart(action, capped, chosen)
+
+    def _segment(self, live, time_left: bool) -> bool:
+        """PDHG iterations of every live LP up to the next check or the first KKT-pass cap (pdhg.py:76-112); False when the clock
+        or the cap ends the batch instead"""
         if not time_left:                                                    # pdhg.py:68-74, the global clock
             self._finish(np.flatnonzero(live), STATUS_TIME_LIMIT)
-            return
+            return False
         iters = min(self.period - self.k_global % self.period, int((self.max_kkt - self.j[live]).min()))
         if iters <= 0:                                                       # max_kkt <= 0: the reference's loop never runs
             self._finish(np.flatnonzero(live), STATUS_KKT_LIMIT)
-            return
-        be.iterate(iters, self.adaptive, self.k_global)                       # pdhg.py:76-112
+            return False
+        self.be.iterate(iters, self.adaptive, self.k_global)
         self.k_global += iters
         self.k[live] += iters
         self.j[live] += iters
         self.tt[live] += iters
-        chosen = None
-        if self.k_global % self.period == 0:                                 # pdhg.py:115 (tt = k mod period for every live LP)
-            be.average(self.adaptive)                                        # pdhg.py:118-119
-            for slot, which in enumerate((N.CUR, N.AVG, N.PREV)):           # pdhg.py:122-125
-                be.kkt(which, slot)
-            out = be.read_out()
-            r = [kkt_finish(out[s], self.omega, t) for s in range(3)]
-            self.j[live] += 3                                                 # pdhg.py:128
-            dec = batch_decisions(r[0]["kkt"], r[1]["kkt"], r[2]["kkt"], self.kkt_first, self.tt, self.k, self.j, live,
-                                  self.max_kkt, t)
-            if self.traces is not None:
-                for i in np.flatnonzero(live):
-                    tr = self.traces[i]
-                    tr["kkt"] += [float(r[0]["kkt"][i]), float(r[1]["kkt"][i]), float(r[2]["kkt"][i])]
-                    if dec["crit"][i] >= 0:
-                        tr["restarts"].append((int(dec["crit"][i]), int(self.tt[i]), int(dec["use_avg"][i])))
-            chosen = {key: np.where(dec["use_avg"], r[1][key], r[0][key]) for key in r[0]}
-            action, capped = dec["action"], dec["capped"]
-        else:                                                                # only the cap ends an inner loop between checks
-            capped = live & (self.j >= self.max_kkt)
-            action = np.where(capped, 1, 0).astype(np.int32)
+        return True
+
+    def _restart_check(self, live):
+        """pdhg.py:115-146 for every live LP: three KKT passes, one host read -> (action, capped, the residuals at the chosen iterate)"""
+        be, t = self.be, self.t
+        be.average(self.adaptive)                                            # pdhg.py:118-119
+        for slot, which in enumerate((N.CUR, N.AVG, N.PREV)):               # pdhg.py:122-125
+            be.kkt(which, slot)
+        out = be.read_out()
+        r = [kkt_from_sums(out[s], self.omega, t) for s in range(3)]
+        self.j[live] += 3                                                    # pdhg.py:128
+        dec = restart_decision(r[0]["kkt"], r[1]["kkt"], r[2]["kkt"], self.kkt_first, self.tt, self.k, self.j, live, self.max_kkt, t)
+        if self.traces is not None:
+            for i in np.flatnonzero(live):
+                tr = self.traces[i]
+                tr["kkt"] += [float(r[0]["kkt"][i]), float(r[1]["kkt"][i]), float(r[2]["kkt"][i])]
+                if dec["crit"][i] >= 0:
+                    tr["restarts"].append((int(dec["crit"][i]), int(self.tt[i]), int(dec["use_avg"][i])))
+        chosen = {key: np.where(dec["use_avg"], r[1][key], r[0][key]) for key in r[0]}
+        return dec["action"], dec["capped"], chosen
+
+    def _after_restart(self, action, capped, chosen):
+        """pdhg.py:148-177 for the LPs that leave their inner loop: n += 1, primal weight, KKT_first, residuals, termination test"""
+        be, t = self.be, self.t
         act = np.flatnonzero(action)
-        if act.size == 0:
-            return
-        # pdhg.py:133-165 for the LPs that leave their inner loop
         be.set_scalars(action=action)
         be.restart(0)
         if capped.any():           # no check chose their point: a pass at the current iterate (pdhg.py:153 after the cap)
@@ -262,28 +220,27 @@ class BatchDriver:
         if self.precondition:
             be.kkt(N.CUR, 1, unscaled=True)                                  # pdhg.py:157-163
         out = be.read_out()
-        be.set_scalars(action=np.zeros(B, np.int32))
+        be.set_scalars(action=np.zeros(be.B, np.int32))
         self.n[act] += 1
         self.tt[act] = 0
         if self.primal_update:                                               # pdhg.py:150-151
-            for i in act:
-                self.omega[i] = primal_weight_from_distances(out[0, i, 0], out[0, i, 1], self.omega[i], 0.5, t)
+            self.omega[act] = primal_weight(out[0, act, 0], out[0, act, 1], self.omega[act], 0.5, t)
             be.set_scalars(omega=self.omega)
             if self.traces is not None:
                 for i in act:
                     self.traces[i]["omega"].append(float(self.omega[i]))
         if capped.any():
-            rc = kkt_finish(out[2], self.omega, t)
+            rc = kkt_from_sums(out[2], self.omega, t)
             chosen = rc if chosen is None else {key: np.where(capped, rc[key], chosen[key]) for key in rc}
-        kf = kkt_reweight(chosen, self.omega, t)                             # pdhg.py:153-154
+        kf = kkt_error(chosen, self.omega, t)                                # pdhg.py:153-154
         self.kkt_first[act] = kf[act]
         self.j[act] += 2                                                     # pdhg.py:154,165
         if self.traces is not None:
             for i in act:
                 self.traces[i]["kkt"].append(float(kf[i]))
-        res = kkt_finish(out[1], self.omega, t) if self.precondition else chosen
+        res = kkt_from_sums(out[1], self.omega, t) if self.precondition else chosen
         self.obj[act] = res["p"][act].astype(np.float64)
-        solved = termination(res, self.q_norm, self.c_norm, self.tol, t)     # pdhg.py:173
+        solved = terminated(res, self.q_norm, self.c_norm, self.tol, t)      # pdhg.py:173
         done_s = act[solved[act]]
         done_k = act[~solved[act] & (self.j[act] >= self.max_kkt)]
         self._finish(done_s, STATUS_SOLVED)
@@ -310,27 +267,21 @@ def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, t
     Returns ``(X, Y, obj, k, n, j, status, total_time)`` with X [n, B], Y [m, B] (the scaled iterates when preconditioned, like
     ``pdlp_algorithm``'s x) and numpy arrays / a list of status strings per LP."""
     t0 = time.time()
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    Kp = CsrPair.from_any(K, device=device)
+    Kp = CsrPair.from_any(K, device=resolve_device(device))
     B = batch_size(C_, Q, L, U)
     for name, v, ln in (("x_init", x_init, Kp.n), ("y_init", y_init, Kp.m)):
         if v is not None and (v.dim() not in (1, 2) or v.shape[0] != ln or (v.dim() == 2 and v.shape[1] != B)):
             raise ValueError(f"{name} must have shape ({ln},) or ({ln}, {B}), got {tuple(v.shape)}")
-    d_col = d_row = None
-    if precondition:
-        if data_precond is None:
-            raise ValueError("precondition=True needs data_precond from ruiz_precondition")
-        d_col, d_row = data_precond[0], data_precond[1]
+    d_col, d_row = precond_factors(precondition, data_precond)
     be = BatchEngine(Kp, m_ineq, C_, Q, L, U, B, d_col=d_col, d_row=d_row, W=group_width)
-    t = _np_t(Kp.dtype)
+    t = np_type(Kp.dtype)
     # pdhg.py:19-20 per LP (as solver._global_norm: the float64 norm, rounded to the working precision)
     colnorm = lambda v: np.broadcast_to(np.sqrt((v.double().reshape(v.shape[0], -1) ** 2).sum(0).cpu().numpy()), (B,)).astype(t)
     qn, cn = colnorm(Q), colnorm(C_)
     if sigma is None:                                                        # pdhg.py:22: K only, once for the batch
         sigma = estimate_sigma(be.eng, b0, 100, seed)
-    drv = BatchDriver(be, qn, cn, restart_period, primal_update, adaptive, precondition, tol, max_kkt, traces)
+    drv = BatchDriver(be, qn, cn, restart_period, primal_update=primal_update, adaptive=adaptive, precondition=precondition, tol=tol,
+                      max_kkt=max_kkt, traces=traces)
     drv.start(sigma, x_init, y_init)
     while drv.live.any():
         drv.step(time.time() - t0 + time_used < time_limit)

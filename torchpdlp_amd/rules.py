@@ -1,0 +1,107 @@
+"""The host-side rules of the reference's ``pdlp_algorithm`` (``/root/reference/PDLP/primal_dual_hybrid_gradient.py:7-181``,
+``helpers.py:84-128``, ``enhancements.py:73-78``): when to restart, with which primal weight, and when to stop.
+
+Pure numpy, no torch and no native library.  Every function takes scalars or arrays of any shape and returns the kind of thing it
+was given: ``PdhgDriver`` (solver.py) calls them with its scalars, ``BatchDriver`` (batch.py) with its ``[B]`` arrays.  Every
+intermediate is rounded to the working precision ``t`` (np.float32 / np.float64; ``t(v)`` of an array is an array of that type).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+BETA = (0.2, 0.8, 0.36)                                       # pdhg.py:28: sufficient, necessary, artificial
+STATUS_KKT_LIMIT = "Unsolved (KKT passes limit exceeded)"     # pdhg.py:51
+STATUS_TIME_LIMIT = "Unsolved (Time limit exceeded)"          # pdhg.py:71
+STATUS_SOLVED = "Solved"                                      # pdhg.py:174
+
+
+def np_type(dtype):
+    """the numpy scalar type of a working precision given as a torch or numpy dtype"""
+    return np.float32 if str(dtype).endswith("float32") else np.float64
+
+
+def kkt_error(res: dict, omega, t=np.float32):
+    """KKT_error (helpers.py:98-108) of known residuals under ``omega``: the residuals do not depend on the primal weight, so a
+    change of omega (pdhg.py:153) is a re-weighting of numbers already there"""
+    w2 = t(omega) * t(omega)
+    pr, dr, gap = t(res["pr"]), t(res["dr"]), t(res["gap"])
+    return np.sqrt(w2 * (pr * pr) + (dr * dr) / w2 + gap * gap)
+
+
+def kkt_from_sums(red, omega, t=np.float32) -> dict:
+    """helpers.py:84-106 from the six sums of a KKT pass (``red[..., 6]`` in the order of PDLP_BUF_RED) -- the library's kkt_finish"""
+    red = np.asarray(red)
+    p, d, lp, un = (t(red[..., i]) for i in (3, 5, 1, 2))
+    adj = d + lp + un
+    res = dict(pr=t(np.sqrt(red[..., 4])), dr=t(np.sqrt(red[..., 0])), gap=adj - p, p=p, d_adj=adj)
+    res["kkt"] = kkt_error(res, omega, t)
+    return res
+
+
+def terminated(res: dict, q_norm, c_norm, tol, t=np.float32):
+    """check_termination (helpers.py:110-128); the gap is signed (reference quirk Q2)"""
+    pr, dr, gap, p, adj, tol = (t(v) for v in (res["pr"], res["dr"], res["gap"], res["p"], res["d_adj"], tol))
+    c1 = pr <= tol * (1 + q_norm)
+    c2 = dr <= tol * (1 + c_norm)
+    c3 = gap <= tol * (1 + abs(p) + abs(adj))
+    return c1 & c2 & c3
+
+
+def previous_kkt_matters(kkt_cur, kkt_avg, kkt_first, t=np.float32):
+    """whether KKT_previous can change ``restart_decision``: it only enters the "necessary" test (pdhg.py:135), which is reached
+    when the sufficient one fails and whose first half does not need it"""
+    kc, ka, kf = t(kkt_cur), t(kkt_avg), t(kkt_first)
+    k_min = t(np.where(ka < kc, ka, kc))
+    return ~(k_min <= t(BETA[0]) * kf) & (k_min <= t(BETA[1]) * kf)
+
+
+def restart_decision(kkt_cur, kkt_avg, kkt_prev, kkt_first, tt, k, j, live=True, max_kkt=np.inf, t=np.float32) -> dict:
+    """The restart decision of one check (pdhg.py:115-146) and the KKT-pass cap (pdhg.py:54,67).
+
+    ``kkt_*`` are the KKT errors at the current, averaged and previous iterates, ``kkt_first`` the one of the last restart point
+    (0 before the first restart: the first check can only restart artificially), ``tt`` the iterations since the last restart,
+    ``k`` the iteration count, ``j`` the KKT-pass count AFTER the check's three passes.  Returns ``crit`` (-1 none, 0 sufficient,
+    1 necessary, 2 artificial), ``use_avg``, ``capped`` (no restart, and ``j`` has reached ``max_kkt``: the reference leaves the
+    inner loop and continues at pdhg.py:148 from the current iterate) and ``action`` (0 keep, 1 restart at the current iterate,
+    2 at the average).  Dead LPs (``live`` false) get -1 / False / 0."""
+    kc, ka, kp, kf = t(kkt_cur), t(kkt_avg), t(kkt_prev), t(kkt_first)
+    live = np.asarray(live, dtype=bool)
+    k_min = np.where(ka < kc, ka, kc)                          # Python's min(KKT_current, KKT_average) of pdhg.py:124
+    use_avg = (kc >= ka) & live
+    suff = k_min <= t(BETA[0]) * kf
+    nec = (k_min <= t(BETA[1]) * kf) & (k_min > kp)
+    art = np.asarray(tt, dtype=np.float64) >= BETA[2] * np.asarray(k, dtype=np.float64)      # in float64, like the int * float there
+    crit = np.where(live, np.where(suff, 0, np.where(nec, 1, np.where(art, 2, -1))), -1)
+    restart = crit >= 0
+    capped = live & ~restart & (np.asarray(j) >= max_kkt)
+    action = np.where(restart, np.where(use_avg, 2, 1), np.where(capped, 1, 0)).astype(np.int32)
+    return dict(crit=crit[()], use_avg=use_avg[()], capped=capped[()], action=action[()])
+
+
+def start_eta(sigma, t=np.float32):
+    """pdhg.py:22: the first step size from the estimate of ||K||_2"""
+    return t(0.9) / t(sigma)
+
+
+def start_omega(q_norm, c_norm, t=np.float32):
+    """pdhg.py:23: the first primal weight ||c|| / ||q||, 1 when either norm is (nearly) zero"""
+    q_norm, c_norm = t(q_norm), t(c_norm)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return t(np.where((q_norm > 1e-6) & (c_norm > 1e-6), c_norm / q_norm, t(1.0)))
+
+
+def primal_weight(dx2, dy2, omega, smooth_theta=0.5, t=np.float32):
+    """primal_weight_update (enhancements.py:73-78) given the two squared restart distances.
+
+    Array input is evaluated element by element (np.vectorize is a Python loop): numpy may use a SIMD ``log`` / ``exp`` for float64
+    arrays whose last bit can differ from the scalar routine's, and an LP's primal weight must not depend on its batch."""
+    if np.ndim(dx2) or np.ndim(dy2) or np.ndim(omega):
+        return np.vectorize(lambda a, b, w: primal_weight(a, b, w, smooth_theta, t), otypes=[t])(dx2, dy2, omega)
+    dxn, dyn = t(np.sqrt(dx2)), t(np.sqrt(dy2))
+    if dxn > 0 and dyn > 0:
+        # every intermediate is rounded to the working precision, as the reference's 0-dim tensors are;
+        # log / exp are evaluated in double and rounded once (same definition as oracle/pdlp_oracle_impl.inc)
+        lr = t(np.log(np.float64(t(dyn / dxn))))
+        lw = t(np.log(np.float64(t(omega))))
+        return t(np.exp(np.float64(t(t(smooth_theta) * lr) + t((t(1) - t(smooth_theta)) * lw))))
+    return t(omega)

@@ -15,42 +15,43 @@ import torch
 
 from . import _native as N
 from .engine import Comm, PdlpEngine
+from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, kkt_error, np_type, previous_kkt_matters,   # noqa: F401
+                    primal_weight, restart_decision, start_eta, start_omega, terminated)
 from .sparse import CsrPair, as_vec
-
-STATUS_KKT_LIMIT = "Unsolved (KKT passes limit exceeded)"     # pdhg.py:51
-STATUS_TIME_LIMIT = "Unsolved (Time limit exceeded)"          # pdhg.py:71
-STATUS_SOLVED = "Solved"                                      # pdhg.py:174
-
-
-def _np_t(dtype):
-    return np.float32 if dtype == torch.float32 else np.float64
 
 
 def check_termination(primal_residual, dual_residual, duality_gap, prim_obj, adjusted_dual, q_norm, c_norm, tol):
-    """check_termination (helpers.py:110-128).  The gap is signed (reference quirk Q2)."""
-    cond1 = primal_residual <= tol * (1 + q_norm)
-    cond2 = dual_residual <= tol * (1 + c_norm)
-    cond3 = duality_gap <= tol * (1 + abs(prim_obj) + abs(adjusted_dual))
-    return bool(cond1 and cond2 and cond3)
+    """check_termination with the reference's signature (helpers.py:110-128): ``rules.terminated`` on the values as they come"""
+    res = dict(pr=primal_residual, dr=dual_residual, gap=duality_gap, p=prim_obj, d_adj=adjusted_dual)
+    return bool(terminated(res, q_norm, c_norm, tol, t=lambda v: v))
 
 
-def kkt_from_residuals(res: dict, omega, t=np.float32):
-    """KKT_error (helpers.py:98-108) from already computed residuals, in the working precision."""
-    w2 = t(omega) * t(omega)
-    pr, dr, gap = t(res["pr"]), t(res["dr"]), t(res["gap"])
-    return t(np.sqrt(w2 * (pr * pr) + (dr * dr) / w2 + gap * gap))
+kkt_from_residuals = kkt_error
+primal_weight_from_distances = primal_weight
 
 
-def primal_weight_from_distances(dx2: float, dy2: float, omega, smooth_theta=0.5, t=np.float32):
-    """primal_weight_update (enhancements.py:73-78) given the two squared restart distances."""
-    dxn, dyn = t(np.sqrt(dx2)), t(np.sqrt(dy2))
-    if dxn > 0 and dyn > 0:
-        # every intermediate is rounded to the working precision, as the reference's 0-dim tensors are;
-        # log / exp are evaluated in double and rounded once (same definition as oracle/pdlp_oracle_impl.inc)
-        lr = t(np.log(np.float64(t(dyn / dxn))))
-        lw = t(np.log(np.float64(t(omega))))
-        return t(np.exp(np.float64(t(t(smooth_theta) * lr) + t((t(1) - t(smooth_theta)) * lw))))
-    return t(omega)
+def resolve_device(device=None) -> torch.device:
+    """the device of a solve: the current HIP device unless given, always with its index"""
+    device = torch.device("cuda") if device is None else torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def precond_factors(precondition, data_precond):
+    """``(D_col, D_row)`` of ``ruiz_precondition``'s ``data_precond`` when ``precondition``, else ``(None, None)``"""
+    if not precondition:
+        return None, None
+    if data_precond is None:
+        raise ValueError("precondition=True needs data_precond from ruiz_precondition")
+    return data_precond[0], data_precond[1]
+
+
+def is_mixed(precision) -> bool:
+    """whether ``precision`` asks for float32 matrix entries under float64 vectors; anything but None / "mixed" is an error"""
+    if precision not in (None, "mixed"):
+        raise ValueError(f"unknown precision {precision!r}")
+    return precision == "mixed"
 
 
 def _global_norm(v_local: torch.Tensor, comm: Optional[Comm]) -> float:
@@ -81,10 +82,9 @@ class PdhgDriver:
         self.trials = 0
         self.primal_update, self.adaptive, self.precondition = bool(primal_update), bool(adaptive), bool(precondition)
         self.tol, self.verbose, self.trace = tol, verbose, trace
-        self.t = _np_t(eng.dtype)
+        self.t = np_type(eng.dtype)
         self.q_norm = self.t(_global_norm(eng.q, eng.comm))                 # pdhg.py:19-20
         self.c_norm = self.t(_global_norm(eng.c, eng.comm))
-        self.beta = (0.2, 0.8, 0.36)                                        # pdhg.py:28
         self.n = self.k = self.j = self.tt = 0
         self.KKT_first = self.t(0)                                          # pdhg.py:48
         self.omega = self.t(1)
@@ -95,9 +95,8 @@ class PdhgDriver:
 
     def start(self, sigma, x_init=None, y_init=None, theta=1.0):
         t, eng = self.t, self.eng
-        eta = t(0.9) / t(sigma)                                             # pdhg.py:22
-        q_norm, c_norm = self.q_norm, self.c_norm
-        self.omega = (c_norm / q_norm) if (q_norm > 1e-6 and c_norm > 1e-6) else t(1.0)   # pdhg.py:23
+        eta = start_eta(sigma, t)                                           # pdhg.py:22
+        self.omega = start_omega(self.q_norm, self.c_norm, t)               # pdhg.py:23
         zeros = lambda ln: torch.zeros(ln, dtype=eng.dtype, device=eng.device)
         if x_init is not None and y_init is not None:                       # pdhg.py:31-36
             eng.set_iterate(x_init, y_init)
@@ -112,9 +111,16 @@ class PdhgDriver:
 
     def advance(self, max_iters: int) -> int:
         """Iterate up to the next restart check (at most ``max_iters``); returns the iterations done."""
-        eng, t = self.eng, self.t
+        iters, at_check = self._segment(int(max_iters))
+        if at_check:
+            self._restart_check()
+        return iters
+
+    def _segment(self, max_iters: int):
+        """PDHG iterations up to the next check, ``max_iters`` at most (pdhg.py:76-112) -> (iterations done, whether a check is due)"""
+        eng = self.eng
         if self.infeasibility_detect:
-            # the detector looks at every iterate (pdhg.py:89-101): one iteration per call, one more pass each
+            # the detector looks at every iterate (pdhg.py:89-101): one iteration per call, one more pass each (max_iters bounds the passes)
             iters, j0 = 0, self.j
             while True:
                 eng.iterate(1, self.adaptive)
@@ -127,16 +133,16 @@ class PdhgDriver:
                     if self.infeasible:
                         if self.verbose:
                             print(f"[PDLP] {self.infeasible} detected at iteration {self.k}")
-                        return iters
+                        return iters, False
                 self.tt += 1
                 if self.tt % self.period == 0:
-                    break
-                if self.j - j0 >= int(max_iters):                           # pdhg.py:67
-                    return iters
-        elif self.adaptive_retry:
-            iters = min(self.period - self.tt % self.period, int(max_iters))
-            if iters <= 0:
-                return 0
+                    return iters, True
+                if self.j - j0 >= max_iters:                                # pdhg.py:67
+                    return iters, False
+        iters = min(self.period - self.tt % self.period, max_iters)
+        if iters <= 0:
+            return 0, False
+        if self.adaptive_retry:                    # every iteration is tried until a step is accepted, one KKT-pass count per trial
             for _ in range(iters):
                 trials = 0
                 while True:
@@ -147,53 +153,39 @@ class PdhgDriver:
                     eng.adaptive_retry()
                 self.j += trials
                 self.trials += trials
-            self.k += iters
-            self.tt += iters
-            if self.tt % self.period != 0:
-                return iters
         else:
-            iters = min(self.period - self.tt % self.period, int(max_iters))
-            if iters <= 0:
-                return 0
-            eng.iterate(iters, self.adaptive)                               # pdhg.py:76-112
-            self.k += iters
+            eng.iterate(iters, self.adaptive)
             self.j += iters
-            self.tt += iters
-            if self.tt % self.period != 0:                                  # pdhg.py:115
-                return iters
+        self.k += iters
+        self.tt += iters
+        return iters, self.tt % self.period == 0                            # pdhg.py:115
+
+    def _restart_check(self):
+        """pdhg.py:115-146: the three KKT errors, the decision and, when it says so, the restart with its work"""
+        eng, t = self.eng, self.t
         timed = self.check_seconds is not None
         if timed:
             eng.synchronize()
             t_check = time.perf_counter()
         self.checks += 1
-        check_range = N.trace_range("pdlp: restart check (3 KKT evaluations)", getattr(eng, "stream", None))
-        check_range.__enter__()
-        # the current iterate first: its pass keeps K'y, which closes the running sum of K'y_k -- the averaged iterate then
-        # needs no product at all (K x_avg and K'y_avg come out of the sums; include/pdlp_hip.h, pdlp_flush_average)
-        r_cur = eng.kkt(N.CUR, self.omega)                                  # pdhg.py:122-125
-        eng.flush_average(self.adaptive)
-        eng.compute_average()                                               # pdhg.py:118-119
-        r_avg = eng.kkt(N.AVG, self.omega)
-        k_cur, k_avg = t(r_cur["kkt"]), t(r_avg["kkt"])
-        k_min = min(k_cur, k_avg)
-        # KKT_previous only enters the "necessary" test (pdhg.py:135); the reference evaluates it at every check.
-        # Here it is evaluated when that test can fire (or when a trace is recorded); the decision and the pass
-        # counter j are the same either way.
-        need_prev = self.trace is not None or (not k_min <= t(self.beta[0]) * self.KKT_first
-                                               and k_min <= t(self.beta[1]) * self.KKT_first)
-        k_prev = t(eng.kkt(N.PREV, self.omega)["kkt"]) if need_prev else t(np.inf)
-        self.j += 3                                                         # pdhg.py:128
-        if self.trace is not None:
-            self.trace["kkt"] += [float(k_cur), float(k_avg), float(k_prev)]
-        use_avg = bool(k_cur >= k_avg)
-        crit = -1
-        if k_min <= t(self.beta[0]) * self.KKT_first:                       # sufficient, pdhg.py:131
-            crit = 0
-        elif k_min <= t(self.beta[1]) * self.KKT_first and k_min > k_prev:  # necessary, pdhg.py:135
-            crit = 1
-        elif self.tt >= self.beta[2] * self.k:                              # artificial, pdhg.py:139
-            crit = 2
-        check_range.__exit__(None, None, None)
+        with N.trace_range("pdlp: restart check (3 KKT evaluations)", getattr(eng, "stream", None)):
+            # the current iterate first: its pass keeps K'y, which closes the running sum of K'y_k -- the averaged iterate then
+            # needs no product at all (K x_avg and K'y_avg come out of the sums; include/pdlp_hip.h, pdlp_flush_average)
+            r_cur = eng.kkt(N.CUR, self.omega)                              # pdhg.py:122-125
+            eng.flush_average(self.adaptive)
+            eng.compute_average()                                           # pdhg.py:118-119
+            r_avg = eng.kkt(N.AVG, self.omega)
+            k_cur, k_avg = t(r_cur["kkt"]), t(r_avg["kkt"])
+            # KKT_previous only enters the "necessary" test (pdhg.py:135); the reference evaluates it at every check.
+            # Here it is evaluated when that test can fire (or when a trace is recorded); the decision and the pass
+            # counter j are the same either way.
+            need_prev = self.trace is not None or previous_kkt_matters(k_cur, k_avg, self.KKT_first, t)
+            k_prev = t(eng.kkt(N.PREV, self.omega)["kkt"]) if need_prev else t(np.inf)
+            self.j += 3                                                     # pdhg.py:128
+            if self.trace is not None:
+                self.trace["kkt"] += [float(k_cur), float(k_avg), float(k_prev)]
+            dec = restart_decision(k_cur, k_avg, k_prev, self.KKT_first, self.tt, self.k, self.j, live=True, t=t)
+        crit, use_avg = int(dec["crit"]), bool(dec["use_avg"])
         if crit >= 0:
             if self.verbose:
                 print(f"{('Sufficient', 'Necessary', 'Artificial')[crit]} restart at iteration {self.tt} using the",
@@ -206,7 +198,6 @@ class PdhgDriver:
         if timed:
             eng.synchronize()
             self.check_seconds += time.perf_counter() - t_check
-        return iters
 
     def after_restart(self, chosen=None):
         """pdhg.py:148-177: n += 1, primal weight, KKT_first, residuals, termination test."""
@@ -217,7 +208,7 @@ class PdhgDriver:
             eng.restart(N.CUR)
         if self.primal_update:                                              # pdhg.py:150-151
             dx2, dy2 = eng.restart_distance()
-            self.omega = primal_weight_from_distances(dx2, dy2, self.omega, 0.5, t)
+            self.omega = primal_weight(dx2, dy2, self.omega, 0.5, t)
             eng.set_omega(self.omega)
             if self.trace is not None:
                 self.trace["omega"].append(float(self.omega))
@@ -231,7 +222,7 @@ class PdhgDriver:
             chosen = eng.kkt(N.CUR, self.omega)
         # KKT_first at the restart point with the (new) omega: the residuals do not depend on omega, so
         # the pass the reference repeats here (pdhg.py:153) is a re-weighting of numbers already known
-        self.KKT_first = kkt_from_residuals(chosen, self.omega, t)
+        self.KKT_first = kkt_error(chosen, self.omega, t)
         self.j += 1                                                         # pdhg.py:154
         if self.trace is not None:
             self.trace["kkt"].append(float(self.KKT_first))
@@ -242,8 +233,7 @@ class PdhgDriver:
             print(f"[{self.k}] Primal Obj: {res['p']:.4f}, Adjusted Dual Obj: {res['d_adj']:.4f}, "
                   f"Gap: {res['gap'] / (1 + abs(res['p']) + abs(res['d_adj'])):.2e}, "
                   f"Prim Res: {res['pr'] / (1 + self.q_norm):.2e}, Dual Res: {res['dr'] / (1 + self.c_norm):.2e}\n")
-        self.solved = check_termination(t(res["pr"]), t(res["dr"]), t(res["gap"]), t(res["p"]), t(res["d_adj"]),
-                                        self.q_norm, self.c_norm, t(self.tol))
+        self.solved = bool(terminated(res, self.q_norm, self.c_norm, self.tol, t))
 
 
 def estimate_sigma(eng: PdlpEngine, b0=None, power_iters=100, seed=None) -> float:
@@ -270,8 +260,9 @@ def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_p
     t0 = time.time()
     if adaptive_retry and (getattr(eng, "delta", False) or infeasibility_detect):
         raise ValueError("adaptive_retry works on float32 / float64 engines without the infeasibility detector")
-    drv = PdhgDriver(eng, restart_period, primal_update, adaptive, precondition, tol, verbose, trace,
-                     infeasibility_detect, infeas_tol, adaptive_retry=adaptive_retry)
+    drv = PdhgDriver(eng, restart_period, primal_update=primal_update, adaptive=adaptive, precondition=precondition, tol=tol,
+                     verbose=verbose, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
+                     adaptive_retry=adaptive_retry)
     if sigma is None:                                                       # pdhg.py:22
         sigma = estimate_sigma(eng, b0, power_iters, seed)
     drv.start(sigma, x_init, y_init)
@@ -345,16 +336,12 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     full problem and the same ``seed``/``b0``; each keeps its row blocks of K and K', the iterations exchange
     ``xbar`` and ``y`` over RCCL, and every rank returns the full solution.
     """
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = resolve_device(device)
     Kp = CsrPair.from_any(K, device=device)
     dtype = Kp.dtype
     vec_dtype = None
     exact_K = None
-    if precision is not None:
-        if precision != "mixed":
-            raise ValueError(f"unknown precision {precision!r}")
+    if is_mixed(precision):
         from .engine import values_are_float32
         if not (values_are_float32(Kp.val) and values_are_float32(Kp.t_val)):
             # any float64 matrix (e.g. a Ruiz-scaled one): the iterations run on its float32 ROUNDING (they only multiply
@@ -363,14 +350,11 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
             exact_K = Kp
         Kp = Kp.to(dtype=torch.float32)
         dtype = vec_dtype = torch.float64
-    d_col = d_row = None
-    if precondition:
-        if data_precond is None:
-            raise ValueError("precondition=True needs data_precond from ruiz_precondition")
-        d_col, d_row = data_precond[0], data_precond[1]
+    d_col, d_row = precond_factors(precondition, data_precond)
     if comm is True:
         comm = Comm()
-    if comm is not None and comm.world > 1:
+    sharded = comm is not None and comm.world > 1
+    if sharded:
         from .distributed import gather_solution, shard_engine
         if seed is None and b0 is None and sigma is None:
             seed = 0                                   # the ranks must draw the same power-iteration start
@@ -382,13 +366,13 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
         if b0 is not None:
             b0 = eng.part.pad_cols(as_vec(b0, Kp.n, device, torch.float32))
         verbose = verbose and comm.rank == 0
-        x, obj, k, n, j, status, total = run_pdlp(eng, max_kkt, tol, verbose, restart_period, precondition, primal_update,
-                                                  adaptive, time_limit, time_used, x_init, y_init, b0=b0, sigma=sigma,
-                                                  seed=seed, trace=trace, infeasibility_detect=infeasibility_detect,
-                                                  infeas_tol=infeas_tol, adaptive_retry=adaptive_retry)
-        return gather_solution(eng, x, Kp.n).view(-1, 1), obj, k, n, j, status, total
-    eng = PdlpEngine.from_full(Kp, c, q, l, u, m_ineq, d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, exact=exact_K)
-    x, obj, k, n, j, status, total = run_pdlp(eng, max_kkt, tol, verbose, restart_period, precondition, primal_update, adaptive,
-                                              time_limit, time_used, x_init, y_init, b0=b0, sigma=sigma, seed=seed, trace=trace,
-                                              infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol, adaptive_retry=adaptive_retry)
+    else:
+        eng = PdlpEngine.from_full(Kp, c, q, l, u, m_ineq, d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, exact=exact_K)
+    x, obj, k, n, j, status, total = run_pdlp(
+        eng, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period, precondition=precondition,
+        primal_update=primal_update, adaptive=adaptive, time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init,
+        b0=b0, sigma=sigma, seed=seed, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
+        adaptive_retry=adaptive_retry)
+    if sharded:
+        x = gather_solution(eng, x, Kp.n)
     return x.view(-1, 1), obj, k, n, j, status, total
