@@ -352,6 +352,18 @@ int pdlp_kkt_local(pdlp_handle h, int which, int unscaled);
  * {primal_residual, dual_residual, duality_gap (signed), prim_obj, adjusted_dual, KKT_error}
  * -- helpers.py:84-94, KKT_error helpers.py:98-108.  Synchronises the stream. */
 int pdlp_kkt_finish(pdlp_handle h, double omega, double out[6]);
+/* Solution report of the iterate PDLP_CUR / PDLP_AVG / PDLP_PREV: what a KKT pass forms entry by entry and drops, kept.
+ *   rc_local[col1-col0]  = lam = project_lambda_box(c - K'y) (helpers.py:3-39,75-79): the reduced costs
+ *   act_local[row1-row0] = K x (helpers.py:77): the row activities
+ * in the working precision (device arrays of the caller; either may be NULL: not stored), and the six sums of pdlp_kkt_local of
+ * this rank's block in PDLP_BUF_RED[0..5] (compute_residuals_and_duality_gap helpers.py:53-96), so that
+ * [all-reduce] -> pdlp_kkt_finish completes it as after pdlp_kkt_local.  unscaled != 0 (needs d_col/d_row): of the
+ * un-preconditioned problem (pdhg.py:157-161): lam_u = lam_s / D_col, act_u = (K_s x_s) / D_row.  Two plain products (the kernels of
+ * pdlp_spmv; in mixed precision float64 sums over the float32 matrix, never the anchors of delta mode) written into the caller's
+ * vectors, then one vector pass over each.  The x and y of `which` must be complete (all-gathered).  Changes nothing of the
+ * solver's state: a report taken anywhere between two calls of an iteration loop leaves every later result bit-identical.
+ * PDLP_ERR_STATE in the middle of a split half-step (between pdlp_*_half_begin and its half-step). */
+int pdlp_report_local(pdlp_handle h, int which, int unscaled, void* rc_local, void* act_local);
 /* make PDLP_AVG (or keep PDLP_CUR) the current iterate and zero the sums -- pdhg.py:57-60,131-142 */
 int pdlp_restart(pdlp_handle h, int which);
 /* ||x - x_last_restart||^2, ||y - y_last_restart||^2 of this rank's block into PDLP_BUF_RED[0..1]
@@ -439,6 +451,12 @@ int pdlp_batch_kkt(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, 
  * out[slot][b][0..1] = ||x - x_last||^2, ||y - y_last||^2 (primal_weight_update enhancements.py:74-75) and x_last = x,
  * y_last = y (pdhg.py:63-64) for every LP with action != 0 */
 int pdlp_batch_restart(pdlp_handle h, const pdlp_batch* b, int slot);
+
+/* The solution report per LP (pdlp_report_local per column): rc [n][Bp] receives lam = project_lambda_box(c - K'y)
+ * (helpers.py:3-39,75-79), act [m][Bp] receives K x (helpers.py:77) (either may be NULL: not stored), out[slot][b][0..5] the six
+ * sums of pdlp_batch_kkt -- for EVERY LP b < B whatever live[b] says (the report is wanted when the batch has finished and every
+ * column is frozen).  Padding columns b >= B of rc, act and out are never written; nothing else of the batch is. */
+int pdlp_batch_report(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot, void* rc, void* act);
 
 /* ---- plain products (power iteration helpers.py:41-51, tests) ------------------------------- */
 /* out_local = K in_full (transpose=0, out has row1-row0 values) or K' in_full (transpose=1) */

@@ -1,10 +1,12 @@
 """Batch driver with the reference's command line and CSV schema (``/root/reference/PDLP/main.py:11-174``):
 
     python -m torchpdlp_amd --instance_path DIR [--tolerance 1e-4] [--output_path output] [--precondition]
-        [--primal_weight_update] [--adaptive_stepsize] [--verbose] [--max_kkt N] [--time_limit S]
+        [--primal_weight_update] [--adaptive_stepsize] [--verbose] [--max_kkt N] [--time_limit S] [--solution_dir DIR]
 
 Solves every ``*.mps`` in the folder (sorted), continues past failures and writes ``solver_results.csv`` with the
-columns ``File, Objective, Iterations (k), Restarts (n), KKT Passes (j), Time (s), Status``.
+columns ``File, Objective, Iterations (k), Restarts (n), KKT Passes (j), Time (s), Status``.  ``--solution_dir`` (not in the
+reference's CLI) also writes ``<instance>.npz`` per solved instance: ``x, y, reduced_costs, row_activity`` and the scalars of the
+solution report (``LPResult``).
 """
 import argparse
 import csv
@@ -47,7 +49,24 @@ def parse_args(argv=None):
                    help="for tolerances below float32 resolution: mixed (float32 matrix entries under float64 vectors, the fast way) or fp64")
     p.add_argument("--seed", type=int, default=None, help="pins the power-iteration start vector (unseeded in the reference)")
     p.add_argument("--standard_mps", action="store_true", help="standard meaning of FR/MI/PL/BV bounds instead of the reference's")
+    p.add_argument("--solution_dir", type=str, default=None,
+                   help="not in the reference's CLI: write <instance>.npz per instance with x, y, reduced_costs, row_activity and the "
+                        "residuals and gap of the original problem at the returned point")
     return p.parse_args(argv)
+
+
+SOLUTION_SCALARS = ("objective", "dual_objective", "primal_residual", "dual_residual", "gap", "rel_primal_residual", "rel_dual_residual",
+                    "rel_gap", "iterations", "restarts", "kkt_passes", "time")
+
+
+def write_solution(directory, name, r):
+    """``<directory>/<name without .mps>.npz``: the vectors and scalars of an ``LPResult`` that carries a solution report"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, os.path.splitext(name)[0] + ".npz")
+    vec = {k: getattr(r, k).detach().cpu().numpy().reshape(-1) for k in ("x", "y", "reduced_costs", "row_activity")}
+    np.savez(path, status=np.asarray(r.status), **vec, **{k: np.asarray(getattr(r, k)) for k in SOLUTION_SCALARS})
+    return path
 
 
 def _fail_row(name, what, e):
@@ -120,8 +139,10 @@ def main(argv=None) -> int:
                          adaptive_stepsize=args.adaptive_stepsize, adaptive_retry=args.adaptive_retry, max_kkt=args.max_kkt, time_limit=args.time_limit,
                          verbose=args.verbose, dtype=dtype, seed=args.seed, fishnet=args.fishnet, comm=comm,
                          infeasibility_detect=args.infeasibility_detect, precision="mixed" if args.dtype == "mixed" else None,
-                         direct_exchange=args.direct_exchange)
+                         direct_exchange=args.direct_exchange, report=args.solution_dir is not None)
             print(f"Solver uses {r.time:.4f} seconds.\nStatus: {r.status}")
+            if args.solution_dir is not None and rank == 0:
+                print(f"Solution saved to {write_solution(args.solution_dir, name, r)}")
             results.append({"File": name, "Objective": f"{r.objective:.6f}", "Iterations (k)": r.iterations, "Restarts (n)": r.restarts,
                             "KKT Passes (j)": r.kkt_passes, "Time (s)": f"{r.time:.4f}", "Status": r.status})      # main.py:142-150
             failed = False

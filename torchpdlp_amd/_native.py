@@ -109,6 +109,7 @@ SIGNATURES = {
     "pdlp_flush_average": (_I, [_H, _I]),
     "pdlp_compute_average": (_I, [_H]),
     "pdlp_kkt_local": (_I, [_H, _I, _I]),
+    "pdlp_report_local": (_I, [_H, _I, _I, _P, _P]),
     "pdlp_kkt_finish": (_I, [_H, _D, C.POINTER(_D)]),
     "pdlp_restart": (_I, [_H, _I]),
     "pdlp_restart_distance_local": (_I, [_H]),
@@ -126,6 +127,7 @@ SIGNATURES = {
     "pdlp_batch_average": (_I, [_H, C.POINTER(PdlpBatch), _I]),
     "pdlp_batch_kkt": (_I, [_H, C.POINTER(PdlpBatch), _I, _I, _I]),
     "pdlp_batch_restart": (_I, [_H, C.POINTER(PdlpBatch), _I]),
+    "pdlp_batch_report": (_I, [_H, C.POINTER(PdlpBatch), _I, _I, _I, _P, _P]),
     "pdlp_spmv": (_I, [_H, _I, _P, _P]),
     "pdlp_power_iteration": (_I, [_H, _P, _I, _P, _P, C.POINTER(_D)]),
     "pdlp_probe_stream_read": (_I, [_P, _I64, _I, _P, C.POINTER(_D)]),

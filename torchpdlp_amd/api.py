@@ -25,10 +25,40 @@ class LPResult:
     status: str                # "Solved" | "Unsolved (KKT passes limit exceeded)" | "Unsolved (Time limit exceeded)"
                                # | "DUAL_INFEASIBLE" | "PRIMAL_INFEASIBLE" (only with infeasibility_detect)
     time: float                # seconds, preconditioning included (main.py:107,136)
+    # the solution report (solve_lp(report=True), the default), all of the ORIGINAL problem; None without it.  Conventions, for the
+    # form K x >= q with y >= 0 on the inequality rows: y_i = d(objective)/d(q_i); reduced cost lam_j > 0: x_j at its lower bound,
+    # lam_j < 0: at its upper bound
+    y: Optional[torch.Tensor] = None                # (m, 1) dual values
+    reduced_costs: Optional[torch.Tensor] = None    # (n, 1) lam = project_lambda_box(c - K'y) (helpers.py:3-39,75-79)
+    row_activity: Optional[torch.Tensor] = None     # (m, 1) K x
+    dual_objective: Optional[float] = None          # q'y + l'max(lam,0) + u'min(lam,0) over the finite bounds (helpers.py:93-95)
+    primal_residual: Optional[float] = None         # ||[K_eq x - q_eq; min(K_in x - q_in, 0)]|| (helpers.py:87-91)
+    dual_residual: Optional[float] = None           # ||c - K'y - lam|| (helpers.py:84)
+    gap: Optional[float] = None                     # dual_objective - objective, signed as the reference's (helpers.py:94)
+    # the left-hand sides of the solver's check_termination (helpers.py:110-128): compare with tol; "Solved" means all three pass.
+    # ||q||, ||c|| are the norms that test is given (pdhg.py:19-20): of the original q and c, or -- like the reference -- of the
+    # Ruiz-scaled ones when preconditioned (the residuals above are of the original problem either way)
+    rel_primal_residual: Optional[float] = None     # primal_residual / (1 + ||q||)
+    rel_dual_residual: Optional[float] = None       # dual_residual / (1 + ||c||)
+    rel_gap: Optional[float] = None                 # gap / (1 + |objective| + |dual_objective|)
 
     def as_tuple(self):
         """the reference's result tuple (pdhg.py:181)"""
         return self.x, self.objective, self.iterations, self.restarts, self.kkt_passes, self.status, self.time
+
+
+def report_fields(rep: Optional[dict]) -> dict:
+    """the report fields of ``LPResult`` / ``BatchResult`` from a solver report (``pdlp_algorithm(report=...)``: scalars, or a
+    batch's [B] arrays).  The relative figures divide by the norms the solver's termination test was given (``q_norm``, ``c_norm``
+    of the report), so they ARE the left-hand sides of its check_termination call: "Solved" means all three pass ``tol``."""
+    if not rep:
+        return {}
+    import numpy as np
+    f = lambda v: float(v) if np.ndim(v) == 0 else np.asarray(v, dtype=np.float64)
+    pr, dr, gap, p, d = (f(rep[k]) for k in ("pr", "dr", "gap", "p", "d_adj"))
+    return dict(y=rep["y"], reduced_costs=rep["reduced_costs"], row_activity=rep["row_activity"], dual_objective=d,
+                primal_residual=pr, dual_residual=dr, gap=gap, rel_primal_residual=pr / (1 + f(rep["q_norm"])),
+                rel_dual_residual=dr / (1 + f(rep["c_norm"])), rel_gap=gap / (1 + abs(p) + abs(d)))
 
 
 def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 1e-4, precondition: bool = False,
@@ -36,7 +66,8 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
              time_limit: float = 3600, verbose: bool = False, restart_period: int = 40, dtype=torch.float32,
              seed: Optional[int] = None, compat: bool = True, x_init=None, y_init=None, trace=None,
              fishnet: bool = False, comm=None, infeasibility_detect: bool = False, infeas_tol: float = 1e-4,
-             precision: Optional[str] = None, adaptive_retry: bool = False, direct_exchange: bool = False) -> LPResult:
+             precision: Optional[str] = None, adaptive_retry: bool = False, direct_exchange: bool = False,
+             report: bool = True) -> LPResult:
     """Solve ``min c'x, K[:m_ineq]x >= q[:m_ineq], K[m_ineq:]x = q[m_ineq:], l <= x <= u`` on the current HIP device.
 
     ``problem`` is an MPS path or ``(c, K, q, m_ineq, l, u)`` with ``K`` dense / COO / scipy-sparse / ``CsrPair``.
@@ -47,6 +78,9 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     (enhancements.py:80-161) after every iteration, with its behaviour as it is.  Under ``torchrun`` (one process per GPU, process
     group initialised) pass ``comm=True``: every rank reads the same problem ON THE HOST, puts only its row blocks of K and K'
     on its GPU (the Ruiz sweeps run on the shards), and all return the full solution -- no GPU ever holds the whole LP.
+    ``report`` (default on): the result also carries the dual values, reduced costs, row activities and the residuals and gap of
+    the ORIGINAL problem at the returned point, whatever the status (two products at the end of the solve; ``LPResult``'s fields
+    say the conventions); ``report=False`` leaves them ``None``.
     ``direct_exchange`` (sharded solves, the ranks of ONE node, at most 8): the iterations run without collectives -- every half-step
     stores its block straight into the other ranks' memory over HIP IPC / xGMI (``PdlpEngine.enable_peer_exchange``, DESIGN.md
     section 5); connected and cross-checked against the collective-driven loop first, which stays in charge if anything differs.
@@ -63,7 +97,7 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
         cm = Comm() if comm is True else comm
         if cm.world > 1:
             return _solve_lp_sharded(problem, cm, device, run, dtype=dtype, verbose=verbose, seed=seed, compat=compat, x_init=x_init,
-                                     y_init=y_init, precision=precision, direct_exchange=direct_exchange)
+                                     y_init=y_init, precision=precision, direct_exchange=direct_exchange, report=report)
     c, K, q, m_ineq, l, u = load_problem(problem, device, dtype, verbose, compat)
     time_used, data_precond = 0.0, None
     Ks, cs, qs, ls, us = K, c, q, l, u
@@ -76,12 +110,13 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
         gen = None if seed is None else torch.Generator().manual_seed(int(seed))
         x_init, y_init = spectral_cast(Ks, cs, qs, ls, us, m_ineq, k=32, device=device, generator=gen)
         time_used += _time.time() - t0
+    rep = {} if report else None
     x, obj, k, n, j, status, total = pdlp_algorithm(
         Ks, m_ineq, cs, qs, ls, us, device, verbose=verbose, data_precond=data_precond, time_used=time_used, x_init=x_init,
-        y_init=y_init, seed=seed, comm=comm, precision=precision, **run)
+        y_init=y_init, seed=seed, comm=comm, precision=precision, report=rep, **run)
     if precondition:        # the reference returns the scaled iterate (quirk Q4); solve_lp un-scales: x = D_col x_s (pdhg.py:161)
         x = data_precond[0].view(-1, 1).to(x.dtype) * x
-    return LPResult(x, obj, k, n, j, status, total)
+    return LPResult(x, obj, k, n, j, status, total, **report_fields(rep))
 
 
 def load_problem(problem, device, dtype, verbose=False, compat=True):
@@ -94,11 +129,12 @@ def load_problem(problem, device, dtype, verbose=False, compat=True):
     return c, CsrPair.from_any(K, device=device, dtype=dtype), q, m_ineq, l, u
 
 
-def _solve_lp_sharded(problem, comm, device, run, *, dtype, verbose, seed, compat, x_init, y_init, precision, direct_exchange) -> LPResult:
+def _solve_lp_sharded(problem, comm, device, run, *, dtype, verbose, seed, compat, x_init, y_init, precision, direct_exchange,
+                      report=True) -> LPResult:
     """``solve_lp`` over the ranks of ``comm``: the problem is read (or taken) on the host by every rank, cut into blocks balanced
     by non-zeros, and only this rank's blocks go to its GPU; Ruiz (enhancements.py:4-71) runs on the shards, the solve is
     ``run_pdlp`` (with the options ``run``) on the sharded engine (pdhg.py:7-181), and every rank returns the full un-scaled solution."""
-    from .distributed import engine_from_shard, gather_solution, shard_arrays
+    from .distributed import engine_from_shard, gather_report, gather_solution, shard_arrays
     from .solver import run_pdlp
     from .sparse import as_vec
     verbose = verbose and comm.rank == 0
@@ -120,11 +156,16 @@ def _solve_lp_sharded(problem, comm, device, run, *, dtype, verbose, seed, compa
     if x_init is not None and y_init is not None:          # full vectors in (of the scaled problem when preconditioned, like the
         x_init = part.pad_cols(as_vec(x_init, n, device, vdt))[eng.cols[0]:eng.cols[1]]    # one-GPU path and main.py:114-130);
         y_init = part.pad_rows(as_vec(y_init, m, device, vdt))[eng.rows[0]:eng.rows[1]]    # this rank's blocks of the padded layout on
+    rep = {} if report else None
     x, obj, k, nr, j, status, total = run_pdlp(eng, verbose=verbose, time_used=time_used, x_init=x_init, y_init=y_init,
-                                               seed=0 if seed is None else seed, **run)
+                                               seed=0 if seed is None else seed, report=rep, **run)
     if run["precondition"]:
         x = x * eng.d_col
-    return LPResult(gather_solution(eng, x, n).view(-1, 1), obj, k, nr, j, status, total)
+    if rep is not None:
+        rep = gather_report(eng, rep, n, m)
+        for key in ("y", "reduced_costs", "row_activity"):
+            rep[key] = rep[key].view(-1, 1)
+    return LPResult(gather_solution(eng, x, n).view(-1, 1), obj, k, nr, j, status, total, **report_fields(rep))
 
 
 @dataclass
@@ -137,13 +178,30 @@ class BatchResult:
     kkt_passes: "np.ndarray"   # (B,) j
     status: list               # B status strings of the reference
     time: float                # seconds for the whole batch
+    # the solution report per LP (solve_lp_batch(report=True), the default; LPResult's fields of the same names): (n, B) / (m, B)
+    # tensors and (B,) arrays, of the ORIGINAL problems; None without it
+    reduced_costs: Optional[torch.Tensor] = None
+    row_activity: Optional[torch.Tensor] = None
+    dual_objective: Optional["np.ndarray"] = None
+    primal_residual: Optional["np.ndarray"] = None
+    dual_residual: Optional["np.ndarray"] = None
+    gap: Optional["np.ndarray"] = None
+    rel_primal_residual: Optional["np.ndarray"] = None
+    rel_dual_residual: Optional["np.ndarray"] = None
+    rel_gap: Optional["np.ndarray"] = None
 
     def __len__(self):
         return len(self.status)
 
     def __getitem__(self, i) -> LPResult:
-        return LPResult(self.x[:, i:i + 1], float(self.objective[i]), int(self.iterations[i]), int(self.restarts[i]),
-                        int(self.kkt_passes[i]), self.status[i], self.time)
+        r = LPResult(self.x[:, i:i + 1], float(self.objective[i]), int(self.iterations[i]), int(self.restarts[i]),
+                     int(self.kkt_passes[i]), self.status[i], self.time)
+        if self.reduced_costs is not None:
+            r.y, r.reduced_costs, r.row_activity = self.y[:, i:i + 1], self.reduced_costs[:, i:i + 1], self.row_activity[:, i:i + 1]
+            for name in ("dual_objective", "primal_residual", "dual_residual", "gap", "rel_primal_residual", "rel_dual_residual",
+                         "rel_gap"):
+                setattr(r, name, float(getattr(self, name)[i]))
+        return r
 
 
 _BATCH_UNSUPPORTED = ("comm", "fishnet", "infeasibility_detect", "adaptive_retry", "direct_exchange")
@@ -153,14 +211,15 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
                    precondition: bool = False, primal_weight_update: bool = False, adaptive_stepsize: bool = False,
                    max_kkt: int = 100_000, time_limit: float = 3600, restart_period: int = 40, dtype=torch.float32,
                    seed: Optional[int] = None, compat: bool = True, x_init=None, y_init=None, trace=None, verbose: bool = False,
-                   group_width: Optional[int] = None, b0=None, **unsupported) -> BatchResult:
+                   group_width: Optional[int] = None, b0=None, report: bool = True, **unsupported) -> BatchResult:
     """Solve B LPs that share ``K`` (and ``m_ineq``) of ``problem`` and differ in ``c``, ``q``, ``l``, ``u`` in one batch.
 
     ``problem`` (an MPS path or ``(c, K, q, m_ineq, l, u)``) supplies K and the default vectors; each of ``c, q, l, u`` may be
     omitted, 1-D (shared) or 2-D ``(len, B)`` (one column per LP; the 2-D arguments must agree on B).  Every LP runs through the
     reference's ``pdlp_algorithm`` with the same flags, its own step sizes, primal weight, restarts and KKT-pass count; ``max_kkt``
     applies per LP, ``time_limit`` to the whole batch.  With ``precondition`` one Ruiz equilibration of K serves every LP and each
-    column of c, q, l, u is scaled.  ``trace``: a list that receives B dicts (``kkt``, ``omega``, ``restarts``).  Flags of
+    column of c, q, l, u is scaled.  ``report`` (default on): the reduced costs, row activities, residuals and gaps of every LP
+    (``BatchResult``'s fields; ``res[i]`` passes them on).  ``trace``: a list that receives B dicts (``kkt``, ``omega``, ``restarts``).  Flags of
     ``solve_lp`` that have no batched form (sharding, fishnet, infeasibility detection, ``adaptive_retry``, the direct exchange,
     ``precision="mixed"``) raise ``ValueError``."""
     import numpy as np
@@ -208,17 +267,20 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     traces = None
     if trace is not None:
         traces = [dict(kkt=[], omega=[], restarts=[]) for _ in range(B)]
+    rep = {} if report else None
     X, Y, obj, k, n, j, status, total = pdlp_algorithm_batch(
         Ks, m_ineq, C_, Q, L, U, device, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period,
         precondition=precondition, primal_update=primal_weight_update, adaptive=adaptive_stepsize, data_precond=data_precond,
         time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init, seed=seed, traces=traces, group_width=group_width,
-        b0=b0)
+        b0=b0, report=rep)
     if trace is not None:
         trace.extend(traces)
     if precondition:                         # x = D_col x_s, y = D_row y_s (pdhg.py:161-162)
         X = data_precond[0].view(-1, 1).to(X.dtype) * X
         Y = data_precond[1].view(-1, 1).to(Y.dtype) * Y
-    return BatchResult(X, Y, np.asarray(obj), np.asarray(k), np.asarray(n), np.asarray(j), status, total)
+    fields = report_fields(rep)
+    fields.pop("y", None)                    # (the report's y is the same un-scaled Y)
+    return BatchResult(X, Y, np.asarray(obj), np.asarray(k), np.asarray(n), np.asarray(j), status, total, **fields)
 
 
 def _check_start_width(B, x_init, y_init):

@@ -118,6 +118,16 @@ class BatchEngine:
     def kkt(self, which: int, slot: int, unscaled: bool = False):
         N.check(self.lib.pdlp_batch_kkt(self.eng.h, C.byref(self.desc), int(which), int(unscaled), int(slot)), "pdlp_batch_kkt")
 
+    def report(self, which: int = N.CUR, unscaled: bool = False, slot: int = 0):
+        """``pdlp_batch_report``: (reduced costs [n, B], row activities [m, B], the six sums [B, 6]) of EVERY LP, frozen or not
+        (one host read)"""
+        rc = torch.zeros(self.n, self.Bp, dtype=self.dtype, device=self.device)
+        act = torch.zeros(self.m, self.Bp, dtype=self.dtype, device=self.device)
+        with torch.cuda.stream(self.stream):
+            N.check(self.lib.pdlp_batch_report(self.eng.h, C.byref(self.desc), int(which), int(bool(unscaled)), int(slot),
+                                               rc.data_ptr(), act.data_ptr()), "pdlp_batch_report")
+        return rc[:, :self.B], act[:, :self.B], self.read_out()[slot]
+
     def restart(self, slot: int):
         N.check(self.lib.pdlp_batch_restart(self.eng.h, C.byref(self.desc), int(slot)), "pdlp_batch_restart")
 
@@ -259,11 +269,15 @@ def batch_size(*vecs) -> int:
 
 def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, tol=1e-4, verbose=False, restart_period=40,
                          precondition=False, primal_update=False, adaptive=False, data_precond=None, time_limit=3600, time_used=0,
-                         x_init=None, y_init=None, *, b0=None, sigma=None, seed=None, traces=None, group_width=None):
+                         x_init=None, y_init=None, *, b0=None, sigma=None, seed=None, traces=None, group_width=None,
+                         report=None):
     """``pdlp_algorithm`` on B LPs with the same ``K`` at once.  ``C_``, ``Q``, ``L``, ``U``: 1-D (shared) or [len, B] (one column
     per LP), of the scaled problem when ``precondition`` (then ``data_precond`` = ``ruiz_precondition``'s: ``D_col``, ``D_row``
     give the un-scaled residuals).  ``traces``: a list of B dicts (``kkt``, ``omega``, ``restarts``) that receive every LP's trace.
     ``group_width``: W (8, 16, 32; default by B and dtype) -- results are bit-identical across batches of the same W.
+    ``report``: a dict that receives the solution report of the returned iterates -- ``y`` [m, B], ``reduced_costs`` [n, B],
+    ``row_activity`` [m, B] and [B] arrays ``pr, dr, gap, p, d_adj, kkt`` (helpers.py:53-108), of the ORIGINAL problems when
+    ``precondition`` -- whatever each LP's status; ``q_norm``, ``c_norm`` [B]: the norms the termination test used.
     Returns ``(X, Y, obj, k, n, j, status, total_time)`` with X [n, B], Y [m, B] (the scaled iterates when preconditioned, like
     ``pdlp_algorithm``'s x) and numpy arrays / a list of status strings per LP."""
     t0 = time.time()
@@ -287,5 +301,9 @@ def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, t
         drv.step(time.time() - t0 + time_used < time_limit)
         if verbose:
             print(f"[batch] k={drv.k_global} live={int(drv.live.sum())}/{B}")
+    if report is not None:
+        rc, act, sums = be.report(N.CUR, unscaled=bool(precondition))
+        Yr = be.y[:, :B] * be.eng.d_row.view(-1, 1) if precondition else be.y[:, :B].clone()
+        report.update(y=Yr, reduced_costs=rc.clone(), row_activity=act.clone(), q_norm=qn, c_norm=cn, **kkt_from_sums(sums, drv.omega, t))
     be.synchronize()
     return (be.x[:, :B].clone(), be.y[:, :B].clone(), drv.obj, drv.k, drv.n, drv.j, list(drv.status), time.time() - t0 + time_used)

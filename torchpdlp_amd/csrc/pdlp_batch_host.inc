@@ -129,6 +129,38 @@ template <typename T> int batch_kkt_t(pdlp_handle h, const pdlp_batch* b, int wh
     return batch_kkt_w<T, 32, false>(h, b, which, slot);
 }
 
+// the report of every LP b < B: the two products of a KKT pass over all columns, lam and K x stored, the sums of columns b < B
+// into out[slot] (padding columns of rc, act and out are never written: the finalize launch ends at column B)
+template <typename T, int W, bool U> int batch_report_w(pdlp_handle h, const pdlp_batch* b, int which, int slot, void* rc, void* act)
+{
+    const T* X = (const T*)(which == PDLP_CUR ? b->x : which == PDLP_AVG ? b->x_avg : b->x_prev);
+    const T* Y = (const T*)(which == PDLP_CUR ? b->y : which == PDLP_AVG ? b->y_avg : b->y_prev);
+    const pdlp_problem& p = h->p;
+    double* out = b->out + (size_t)slot * b->Bp * 6;
+    BReportDual<T, U> ed{{X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp, (const T*)p.d_col}, (T*)rc};
+    hipLaunchKernelGGL((k_batch_mv_all<T, W, BReportDual<T, U>>), dim3(batch_grid(p.n, W), b->Bp / W), dim3(BLOCK), 0, h->stream, (int)p.n,
+                       p.KT_rowptr, p.KT_colidx, (const T*)p.KT_val, Y, b->Bp, b->B, ed, b->part);
+    hipLaunchKernelGGL(k_batch_finalize, dim3(b->B * 4), dim3(BLOCK), 0, h->stream, (const double*)b->part, batch_grid(p.n, W), b->Bp, 4, out, 6, 0);
+    BReportPrimal<T, U> ep{{Y, (const T*)b->q, b->q_per_lp, (const T*)p.d_row, (int)p.m_ineq}, (T*)act};
+    hipLaunchKernelGGL((k_batch_mv_all<T, W, BReportPrimal<T, U>>), dim3(batch_grid(p.m, W), b->Bp / W), dim3(BLOCK), 0, h->stream, (int)p.m,
+                       p.K_rowptr, p.K_colidx, (const T*)p.K_val, X, b->Bp, b->B, ep, batch_part2(b));
+    hipLaunchKernelGGL(k_batch_finalize, dim3(b->B * 2), dim3(BLOCK), 0, h->stream, (const double*)batch_part2(b), batch_grid(p.m, W), b->Bp, 2, out, 6, 4);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+template <typename T> int batch_report_t(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot, void* rc, void* act)
+{
+    if (unscaled) {
+        if (b->W == 8) return batch_report_w<T, 8, true>(h, b, which, slot, rc, act);
+        if (b->W == 16) return batch_report_w<T, 16, true>(h, b, which, slot, rc, act);
+        return batch_report_w<T, 32, true>(h, b, which, slot, rc, act);
+    }
+    if (b->W == 8) return batch_report_w<T, 8, false>(h, b, which, slot, rc, act);
+    if (b->W == 16) return batch_report_w<T, 16, false>(h, b, which, slot, rc, act);
+    return batch_report_w<T, 32, false>(h, b, which, slot, rc, act);
+}
+
 template <typename T, int W> int batch_restart_w(pdlp_handle h, const pdlp_batch* b, int slot)
 {
     const dim3 gn(batch_grid(h->p.n, W), b->Bp / W), gm(batch_grid(h->p.m, W), b->Bp / W);
@@ -177,6 +209,16 @@ int pdlp_batch_kkt(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, 
     if (unscaled && (!h->p.d_col || !h->p.d_row)) return PDLP_ERR_STATE;
     Range range("pdlp: batch KKT pass", h->stream);
     return DISPATCH(h, batch_kkt_t, h, b, which, unscaled, slot);
+}
+
+int pdlp_batch_report(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot, void* rc, void* act)
+{
+    if ((which != PDLP_CUR && which != PDLP_AVG && which != PDLP_PREV) || slot < 0 || slot > 2) return PDLP_ERR_INVALID;
+    const int r = batch_check(h, b);
+    if (r != PDLP_OK) return r;
+    if (unscaled && (!h->p.d_col || !h->p.d_row)) return PDLP_ERR_STATE;
+    Range range("pdlp: batch solution report", h->stream);
+    return DISPATCH(h, batch_report_t, h, b, which, unscaled, slot, rc, act);
 }
 
 int pdlp_batch_restart(pdlp_handle h, const pdlp_batch* b, int slot)

@@ -180,6 +180,66 @@ template <typename T, bool UNSCALE> struct KktPrimalEpi {
     }
 };
 
+// Solution report, variable side (pdlp_report_local): the vector pass that follows a plain product K'y stored into `buf`.  Reads
+// (K'y)_j from buf, forms the sums of KktDualEpi with the same arithmetic (helpers.py:75-84,94; project_lambda_box helpers.py:21-37)
+// and leaves the reduced cost lam_j in buf[j] -- UNSCALE: of the un-preconditioned problem, lam_u = lam_s / D_col (pdhg.py:157-161).
+// The product is an operand of pre(), not the kernel's row sum (k_rowsum_epilogue runs with no groups): buf is read and written
+// through this one pointer.
+template <typename T, bool UNSCALE> struct ReportDualEpi {
+    static constexpr int NA = 4;
+    T* buf; const T* x; const T* c; const T* l; const T* u; const T* dcol;
+    __device__ void load() {}
+    struct Pre { T kty; typename KktDualEpi<T, UNSCALE>::Pre kp; };
+    __device__ Pre pre(int j) const { return Pre{buf[j], {c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1}}; }
+    __device__ void operator()(int j, T, double* acc) const { (*this)(j, (T)0, pre(j), acc); }
+    __device__ void operator()(int j, T, const Pre& p, double* acc) const
+    {
+        T cj = p.kp.cj, lo = p.kp.lo, hi = p.kp.hi, xj = p.kp.xj;
+        T g = cj - p.kty;
+        if (UNSCALE) {
+            const T d = p.kp.d;
+            g = g / d; cj = cj / d; lo = lo * d; hi = hi * d; xj = xj * d;
+        }
+        const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
+        T lam;
+        if (ninf && pinf) lam = (T)0;
+        else if (ninf) lam = g < (T)0 ? g : (T)0;
+        else if (pinf) lam = g > (T)0 ? g : (T)0;
+        else lam = g;
+        buf[j] = lam;
+        const T ld = ninf ? (T)0 : lo, ud = pinf ? (T)0 : hi;
+        const T r = g - lam;
+        acc[0] += (double)r * (double)r;
+        acc[1] += (double)ld * (double)(lam > (T)0 ? lam : (T)0);
+        acc[2] += (double)ud * (double)(lam < (T)0 ? lam : (T)0);
+        acc[3] += (double)cj * (double)xj;
+    }
+};
+
+// Solution report, constraint side: the same after K x stored into `buf`.  The sums of KktPrimalEpi (helpers.py:77,87-91); buf[i]
+// keeps the row activity (K x)_i -- UNSCALE: act_u = (K_s x_s) / D_row.
+template <typename T, bool UNSCALE> struct ReportPrimalEpi {
+    static constexpr int NA = 2;
+    T* buf; const T* y; const T* q; const T* drow; int ineq_end;
+    __device__ void load() {}
+    struct Pre { T kx, qi, yi, d; };
+    __device__ Pre pre(int i) const { return Pre{buf[i], q[i], y[i], UNSCALE ? drow[i] : (T)1}; }
+    __device__ void operator()(int i, T, double* acc) const { (*this)(i, (T)0, pre(i), acc); }
+    __device__ void operator()(int i, T, const Pre& p, double* acc) const
+    {
+        T qi = p.qi, yi = p.yi;
+        T r = p.kx - qi;
+        if (UNSCALE) {
+            const T d = p.d;
+            r = r / d; qi = qi / d; yi = yi * d;
+            buf[i] = p.kx / d;
+        }
+        if (i < ineq_end && r > (T)0) r = (T)0;
+        acc[0] += (double)r * (double)r;
+        acc[1] += (double)qi * (double)yi;
+    }
+};
+
 // infeasibility detection (opt-in), variable side -- detect_infeasibility enhancements.py:108-114,124-139,146-157 for
 // the step just taken, with lam = project_lambda_box(c - K'y) (pdhg.py:90, helpers.py:21-37).  Rows of K'.
 // partial sums: ||K'dy - dlam||^2, l_f'dlam_minus + u_f'dlam_plus, c'dx, #{variables failing the bound test}

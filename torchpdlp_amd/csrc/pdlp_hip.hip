@@ -738,6 +738,58 @@ template <typename T> int kkt_local_t(pdlp_handle h, int which, int unscaled)
     return unscaled ? kkt_local_u<T, true>(h, which) : kkt_local_u<T, false>(h, which);
 }
 
+// Solution report (pdlp_report_local): reduced costs and row activities of an iterate stored, with the six KKT sums.  The two
+// products are the plain ones of pdlp_spmv (StoreEpi: instantiated for every kernel family; float64 accumulation over the float32
+// matrix in mixed precision, never the delta-mode anchors) written straight into the caller's vectors; a vector pass over each
+// then forms the sums and turns K'y into lam in place.  A vector the caller does not want (null) costs nothing extra: that side
+// runs the KKT pass's own fused epilogue without its stores.  Nothing of the solver's state is read except the iterate and
+// nothing is written except scratch (partial sums, row sums, PDLP_BUF_RED).
+template <typename T, class Epi> int report_pass(pdlp_handle h, int64_t rows, Epi e, double* partials)
+{
+    if (rows == 0) return PDLP_OK;
+    hipLaunchKernelGGL((k_rowsum_epilogue<T, Epi>), dim3(grid_for(rows)), dim3(BLOCK), 0, h->stream, (const T*)nullptr, 0, (int64_t)0,
+                       (int)rows, (const T*)nullptr, e, partials);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+template <typename T, bool UNSCALE> int report_local_u(pdlp_handle h, int which, void* rc_local, void* act_local)
+{
+    const int ix = which == PDLP_CUR ? h->ix_cur : (which == PDLP_AVG ? h->ix_avg : h->ix_prev);
+    const T* dcol = UNSCALE ? (const T*)h->p.d_col : nullptr;
+    const T* drow = UNSCALE ? (const T*)h->p.d_row : nullptr;
+    int rc, gridA = grid_of(h->sKT, h->nl), gridB = grid_of(h->sK, h->ml);
+    if (rc_local) {
+        StoreEpi<T> st{(T*)rc_local};
+        if ((rc = launch_csr<T>(h, true, h->yb[ix], st, h->partA)) != PDLP_OK) return rc;
+        ReportDualEpi<T, UNSCALE> ed{(T*)rc_local, xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol};
+        if ((rc = report_pass<T>(h, h->nl, ed, h->partA)) != PDLP_OK) return rc;
+        gridA = h->nl > 0 ? grid_for(h->nl) : 0;
+    } else {
+        KktDualEpi<T, UNSCALE> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, nullptr};
+        if ((rc = launch_csr<T>(h, true, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
+    }
+    if (act_local) {
+        StoreEpi<T> st{(T*)act_local};
+        if ((rc = launch_csr<T>(h, false, h->xb[ix], st, h->partB)) != PDLP_OK) return rc;
+        ReportPrimalEpi<T, UNSCALE> ep{(T*)act_local, yloc<T>(h, ix), (const T*)h->p.q, drow, h->ineq_end};
+        if ((rc = report_pass<T>(h, h->ml, ep, h->partB)) != PDLP_OK) return rc;
+        gridB = h->ml > 0 ? grid_for(h->ml) : 0;
+    } else {
+        KktPrimalEpi<T, UNSCALE> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, nullptr, h->ineq_end};
+        if ((rc = launch_csr<T>(h, false, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
+    }
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partA, gridA, 4, h->red, 0);
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partB, gridB, 2, h->red, 4);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+template <typename T> int report_local_t(pdlp_handle h, int which, int unscaled, void* rc_local, void* act_local)
+{
+    return unscaled ? report_local_u<T, true>(h, which, rc_local, act_local) : report_local_u<T, false>(h, which, rc_local, act_local);
+}
+
 template <typename T> void kkt_finish_t(const double* r, double omega_d, double* out)
 {
     // helpers.py:84-94,102-106 in the working precision
@@ -2497,6 +2549,15 @@ int pdlp_kkt_local(pdlp_handle h, int which, int unscaled)
     if (unscaled && (!h->p.d_col || !h->p.d_row)) return PDLP_ERR_STATE;
     if (h->delta) return delta_kkt_local(h, which, unscaled);
     return DISPATCH(h, kkt_local_t, h, which, unscaled);
+}
+
+int pdlp_report_local(pdlp_handle h, int which, int unscaled, void* rc_local, void* act_local)
+{
+    if (!h || which < PDLP_CUR || which > PDLP_PREV) return PDLP_ERR_INVALID;
+    if (unscaled && (!h->p.d_col || !h->p.d_row)) return PDLP_ERR_STATE;
+    if (h->sK.pending || h->sKT.pending || h->range_sel >= 0) return PDLP_ERR_STATE;     // not in the middle of a split half-step
+    Range range("pdlp: solution report", h->stream);
+    return DISPATCH(h, report_local_t, h, which, unscaled, rc_local, act_local);
 }
 
 int pdlp_read_red(pdlp_handle h, double out[PDLP_NRED])

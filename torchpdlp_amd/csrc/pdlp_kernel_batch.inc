@@ -154,28 +154,83 @@ template <typename T, bool UNSCALE> struct BKktPrimal {
     }
 };
 
+// Solution report per column (pdlp_batch_report): the KKT sums of BKktDual / BKktPrimal with the reduced cost lam resp. the row
+// activity K x stored beside them (null: not stored) -- UNSCALE: lam_u = lam_s / D_col, act_u = (K_s x_s) / D_row
+template <typename T, bool UNSCALE> struct BReportDual {
+    static constexpr int NA = 4;
+    BKktDual<T, UNSCALE> kkt; T* RC;
+    __device__ void operator()(int j, size_t at, int b, T kty, double* acc) const
+    {
+        if (RC) {
+            T lo = BCOL(kkt.l, kkt.ls, j, at), hi = BCOL(kkt.u, kkt.us, j, at);
+            T g = BCOL(kkt.c, kkt.cs, j, at) - kty;
+            if (UNSCALE) {
+                const T d = kkt.dcol[j];
+                g = g / d; lo = lo * d; hi = hi * d;
+            }
+            const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
+            T lam;
+            if (ninf && pinf) lam = (T)0;
+            else if (ninf) lam = g < (T)0 ? g : (T)0;
+            else if (pinf) lam = g > (T)0 ? g : (T)0;
+            else lam = g;
+            RC[at] = lam;
+        }
+        kkt(j, at, b, kty, acc);
+    }
+};
+template <typename T, bool UNSCALE> struct BReportPrimal {
+    static constexpr int NA = 2;
+    BKktPrimal<T, UNSCALE> kkt; T* ACT;
+    __device__ void operator()(int i, size_t at, int b, T kx, double* acc) const
+    {
+        if (ACT) ACT[at] = UNSCALE ? kx / kkt.drow[i] : kx;
+        kkt(i, at, b, kx, acc);
+    }
+};
+
+// the row walk of a launch for column b of its group: the matrix (rows x cols, CSR) times column b of Vin[cols][Bp], the epilogue
+// per row
+template <typename T, int W, class Epi>
+__device__ __forceinline__ void batch_rows(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                           const T* __restrict__ va, const T* __restrict__ Vin, int Bp, int b, const Epi& epi, double* acc)
+{
+    constexpr int RPW = 64 / W;
+    const int sub = (threadIdx.x & 63) / W;
+    const int wave = (blockIdx.x * BLOCK + threadIdx.x) >> 6, nwaves = gridDim.x * (BLOCK / 64);
+    for (int r0 = wave * RPW; r0 < rows; r0 += nwaves * RPW) {
+        const int r = r0 + sub;
+        if (r < rows) {
+            T s = (T)0;
+            const int64_t e = rp[r + 1];
+            for (int64_t p = rp[r]; p < e; ++p) s += va[p] * Vin[(size_t)ci[p] * Bp + b];
+            epi(r, (size_t)r * Bp + b, b, s, acc);
+        }
+    }
+}
+
 // one product of the matrix (rows x cols, CSR) with a population Vin[cols][Bp], the epilogue per (row, live column)
 template <typename T, int W, class Epi>
 __global__ __launch_bounds__(BLOCK) void k_batch_mv(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
                                                     const T* __restrict__ va, const T* __restrict__ Vin, int Bp,
                                                     const int32_t* __restrict__ live, Epi epi, double* __restrict__ partials)
 {
-    constexpr int RPW = 64 / W;
-    const int lane = threadIdx.x & 63, sub = lane / W;
-    const int b = blockIdx.y * W + lane % W;
-    const int wave = (blockIdx.x * BLOCK + threadIdx.x) >> 6, nwaves = gridDim.x * (BLOCK / 64);
+    const int b = blockIdx.y * W + (threadIdx.x & 63) % W;
     double acc[Epi::NA > 0 ? Epi::NA : 1] = {0.0};
-    if (live[b]) {
-        for (int r0 = wave * RPW; r0 < rows; r0 += nwaves * RPW) {
-            const int r = r0 + sub;
-            if (r < rows) {
-                T s = (T)0;
-                const int64_t e = rp[r + 1];
-                for (int64_t p = rp[r]; p < e; ++p) s += va[p] * Vin[(size_t)ci[p] * Bp + b];
-                epi(r, (size_t)r * Bp + b, b, s, acc);
-            }
-        }
-    }
+    if (live[b]) batch_rows<T, W>(rows, rp, ci, va, Vin, Bp, b, epi, acc);
+    if (Epi::NA > 0) batch_store_partials<W, Epi::NA>(acc, partials, Bp);
+}
+
+// the same over every LP of the batch, b < B, frozen or not (the report is wanted when all are frozen); padding columns are
+// neither read nor written
+template <typename T, int W, class Epi>
+__global__ __launch_bounds__(BLOCK) void k_batch_mv_all(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                        const T* __restrict__ va, const T* __restrict__ Vin, int Bp, int B, Epi epi,
+                                                        double* __restrict__ partials)
+{
+    const int b = blockIdx.y * W + (threadIdx.x & 63) % W;
+    double acc[Epi::NA > 0 ? Epi::NA : 1] = {0.0};
+    if (b < B) batch_rows<T, W>(rows, rp, ci, va, Vin, Bp, b, epi, acc);
     if (Epi::NA > 0) batch_store_partials<W, Epi::NA>(acc, partials, Bp);
 }
 

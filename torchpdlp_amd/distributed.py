@@ -234,6 +234,25 @@ def gather_solution(eng: PdlpEngine, x_local: torch.Tensor, n_true: int) -> torc
     return full[:n_true] if part is None else part.unpad_cols(full)
 
 
+def gather_report(eng: PdlpEngine, rep: dict, n_true: int, m_true: int) -> dict:
+    """``PdlpEngine.report``'s dict with the full ``y``, ``reduced_costs`` and ``row_activity`` in the ORIGINAL order on every rank
+    (the scalars are already those of the whole problem)"""
+    if eng.comm is None:
+        return rep
+    part = getattr(eng, "part", None)
+
+    def full(v_local, ln, blk, ln_true, unpad):
+        out = torch.empty(ln, dtype=v_local.dtype, device=v_local.device)
+        out[blk[0]:blk[1]] = v_local
+        eng.comm.all_gather(out)
+        return out[:ln_true] if part is None else unpad(out)
+    rep = dict(rep)
+    rep["y"] = full(rep["y"], eng.m, eng.rows, m_true, part and part.unpad_rows)
+    rep["row_activity"] = full(rep["row_activity"], eng.m, eng.rows, m_true, part and part.unpad_rows)
+    rep["reduced_costs"] = full(rep["reduced_costs"], eng.n, eng.cols, n_true, part and part.unpad_cols)
+    return rep
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # building a shard without ever holding the whole matrix
 # ---------------------------------------------------------------------------------------------------------------------

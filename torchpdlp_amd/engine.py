@@ -189,7 +189,8 @@ class PdlpEngine:
             self.set_option(N.OPT_GRAPH, 1)
         self.exact = None
         if exact is not None:          # the true float64 matrix, CSR kernels only: two products per restart
-            self.exact = PdlpEngine(m, n, m_ineq, exact[0], exact[1], c, q, l, u, rows=rows, cols=cols, comm=comm, tiles=False)
+            self.exact = PdlpEngine(m, n, m_ineq, exact[0], exact[1], c, q, l, u, rows=rows, cols=cols, d_col=d_col, d_row=d_row,
+                                    comm=comm, tiles=False)       # (d_col / d_row: the un-scaled solution report)
         self._sorted = [None, None]
         self._mv_work = {}
         self.xchunks, self._plans = 1, {}
@@ -954,6 +955,34 @@ class PdlpEngine:
         N.check(self.lib.pdlp_kkt_finish(self.h, float(omega), out), "pdlp_kkt_finish")
         self._peer_check()                       # (the stream has been synchronised: a wait that gave up shows now)
         return dict(pr=out[0], dr=out[1], gap=out[2], p=out[3], d_adj=out[4], kkt=out[5])
+
+    def report(self, which: int = N.CUR, unscaled: bool = False, omega: float = 1.0) -> dict:
+        """The solution report of an iterate (``pdlp_report_local``, include/pdlp_hip.h): ``y``, ``reduced_costs`` =
+        project_lambda_box(c - K'y) and ``row_activity`` = K x (this rank's blocks when sharded; of the un-preconditioned problem
+        with ``unscaled``: y_u = D_row y, lam_u = lam / D_col, (K x)_u = (K x) / D_row), and the residual dict of ``kkt``
+        (helpers.py:53-108).  The products are always multiplied out (never the carried or running ones) and the solver's state is
+        left as it is: a report taken between two ``iterate`` calls changes no later bit."""
+        if self.exact is not None:
+            # the handle's matrix is the float32 rounding of the true one: the report comes from the true matrix (the float64
+            # engine behind the anchors, which holds no state of the solve)
+            x, y = self.get_iterate(which)
+            self.exact.set_iterate(x, y)
+            return self.exact.report(N.CUR, unscaled, omega)
+        if self.comm is not None:
+            self._gather({N.CUR: N.BUF_X_CUR, N.AVG: N.BUF_X_AVG, N.PREV: N.BUF_X_PREV}[which])
+            self._gather({N.CUR: N.BUF_Y_CUR, N.AVG: N.BUF_Y_AVG, N.PREV: N.BUF_Y_PREV}[which])
+        rc = torch.empty(self.nl, dtype=self.dtype, device=self.device)
+        act = torch.empty(self.ml, dtype=self.dtype, device=self.device)
+        N.check(self.lib.pdlp_report_local(self.h, int(which), int(bool(unscaled)), rc.data_ptr(), act.data_ptr()), "pdlp_report_local")
+        if self.comm is not None:
+            self.comm.all_reduce_sum(self.buffer(N.BUF_RED))
+        out = (C.c_double * 6)()
+        N.check(self.lib.pdlp_kkt_finish(self.h, float(omega), out), "pdlp_kkt_finish")
+        self._peer_check()
+        _, y = self.get_iterate(which)
+        if unscaled:
+            y = y * self.d_row
+        return dict(y=y, reduced_costs=rc, row_activity=act, pr=out[0], dr=out[1], gap=out[2], p=out[3], d_adj=out[4], kkt=out[5])
 
     def restart(self, which: int):
         N.check(self.lib.pdlp_restart(self.h, which), "pdlp_restart")

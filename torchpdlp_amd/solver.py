@@ -255,8 +255,11 @@ def estimate_sigma(eng: PdlpEngine, b0=None, power_iters=100, seed=None) -> floa
 def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_period=40, precondition=False,
              primal_update=False, adaptive=False, time_limit=3600, time_used=0, x_init=None, y_init=None,
              b0=None, sigma=None, power_iters=100, seed=None, trace=None, infeasibility_detect=False, infeas_tol=1e-4,
-             adaptive_retry=False):
-    """The outer loop over an existing engine.  Returns (x_local, prim_obj, k, n, j, status, total_time)."""
+             adaptive_retry=False, *, report=None):
+    """The outer loop over an existing engine.  Returns (x_local, prim_obj, k, n, j, status, total_time).
+    ``report``: a dict that receives ``PdlpEngine.report`` of the returned iterate (this rank's blocks; of the un-preconditioned
+    problem when ``precondition``) whatever the status, and ``q_norm`` / ``c_norm`` as the termination test used them -- in the
+    style of ``trace``."""
     t0 = time.time()
     if adaptive_retry and (getattr(eng, "delta", False) or infeasibility_detect):
         raise ValueError("adaptive_retry works on float32 / float64 engines without the infeasibility detector")
@@ -303,6 +306,9 @@ def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_p
                 print(f"Converged at iteration {drv.k} restart loop {drv.n}")
             break
     x_local, _ = eng.get_iterate(N.CUR)
+    if report is not None:
+        report.update(eng.report(N.CUR, unscaled=bool(precondition), omega=drv.omega))
+        report.update(q_norm=float(drv.q_norm), c_norm=float(drv.c_norm))      # as the exit test took them (pdhg.py:19-20)
     eng.synchronize()                                  # the reference reads its clock without a sync (Q10)
     prim_obj = float(drv.res["p"]) if drv.res is not None else float("nan")
     return x_local, prim_obj, drv.k, drv.n, drv.j, status, time.time() - t0 + time_used
@@ -311,7 +317,7 @@ def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_p
 def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4, verbose=True, restart_period=40,
                    precondition=False, primal_update=False, adaptive=False, data_precond=None, infeasibility_detect=False,
                    infeas_tol=1e-4, time_limit=3600, time_used=0, x_init=None, y_init=None, *, b0=None, sigma=None,
-                   seed=None, trace=None, comm=None, precision=None, adaptive_retry=False):
+                   seed=None, trace=None, comm=None, precision=None, adaptive_retry=False, report=None):
     """Drop-in for the reference's ``pdlp_algorithm`` (primal_dual_hybrid_gradient.py:7) on one MI355X.
 
     ``K`` may be a dense / COO torch tensor (as the reference takes), a scipy sparse matrix or a
@@ -331,6 +337,11 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     ``c, q, l, u`` are taken in float64.  A matrix that is NOT float32-valued (any float64 ``K``, a Ruiz-scaled one with
     ``precondition=True``) works too, sharded included: the iterations then run on its float32 rounding and the anchors of delta
     mode and the termination test are evaluated with the true float64 matrix after every restart.
+
+    ``report``: a dict that receives the solution report of the returned iterate -- ``y``, ``reduced_costs``, ``row_activity``
+    (full (m,1) / (n,1) tensors) and ``pr, dr, gap, p, d_adj, kkt`` (helpers.py:53-108), of the ORIGINAL problem when
+    ``precondition`` (un-like ``x``) -- for every exit status; ``q_norm``, ``c_norm``: the norms check_termination was given
+    (pdhg.py:19-20,173: of the ``q`` and ``c`` passed in, i.e. of the scaled vectors when ``precondition``).
 
     ``comm`` (a ``Comm``, or ``True`` for the default ``torch.distributed`` group): every rank calls with the SAME
     full problem and the same ``seed``/``b0``; each keeps its row blocks of K and K', the iterations exchange
@@ -372,7 +383,13 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
         eng, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period, precondition=precondition,
         primal_update=primal_update, adaptive=adaptive, time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init,
         b0=b0, sigma=sigma, seed=seed, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
-        adaptive_retry=adaptive_retry)
+        adaptive_retry=adaptive_retry, report=report)
     if sharded:
         x = gather_solution(eng, x, Kp.n)
+        if report is not None:
+            from .distributed import gather_report
+            report.update(gather_report(eng, report, Kp.n, Kp.m))
+    if report is not None:
+        for key in ("y", "reduced_costs", "row_activity"):
+            report[key] = report[key].view(-1, 1)
     return x.view(-1, 1), obj, k, n, j, status, total
