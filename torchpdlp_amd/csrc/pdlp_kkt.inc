@@ -1,0 +1,284 @@
+// pdlp_kkt.inc -- everything a restart check evaluates: the KKT pass (kkt_local_*: six sums of a candidate, from products or from
+// the running sums), the solution report, the finish of the sums in the working precision, the running average's flush and
+// division, the restart distance, infeasibility detection and the power iteration; and pdlp_restart, which adopts a candidate
+// together with the products its KKT pass left behind.
+// Part of pdlp_hip.hip (included at file scope; not a translation unit of its own).  Needs: pdlp_products.inc and what is before it.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+template <typename T, bool UNSCALE> int kkt_local_u(pdlp_handle h, int which)
+{
+    const int ix = iterate_index(h, which);
+    const T* dcol = UNSCALE ? (const T*)h->p.d_col : nullptr;
+    const T* drow = UNSCALE ? (const T*)h->p.d_row : nullptr;
+    int rc, gridA = grid_of(h->sKT, h->nl), gridB = grid_of(h->sK, h->ml);
+    if (which == PDLP_AVG && h->avg_products) {
+        // K'y_avg (ktyb[1]) and K x_avg (kxb[2]) were formed from the running sums by pdlp_compute_average: two vector passes
+        KktDualEpi<T, UNSCALE> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, nullptr};
+        if ((rc = epilogue_pass<T>(h, h->nl, h->ktyb[1], ed, h->partA)) != PDLP_OK) return rc;
+        KktPrimalEpi<T, UNSCALE> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, nullptr, h->ineq_end};
+        if ((rc = epilogue_pass<T>(h, h->ml, h->kxb[2], ep, h->partB)) != PDLP_OK) return rc;
+        gridA = rows_grid(h->nl);
+        gridB = rows_grid(h->ml);
+    } else {
+        T* kx_out = which == PDLP_CUR ? (T*)h->kxb[1] : (which == PDLP_AVG ? (T*)h->kxb[2] : nullptr);
+        // K'y of a candidate is the product the first primal half-step after the check needs again (same kernel, same
+        // sums): keep it.  (A pass at the current iterate after a restart to the average supersedes that restart's copy.)
+        T* kty_out = which == PDLP_CUR ? (T*)h->ktyb[0] : (which == PDLP_AVG ? (T*)h->ktyb[1] : nullptr);
+        if (which == PDLP_CUR || (which == PDLP_AVG && h->kty_cur == 1)) h->kty_cur = -1;     // (the copy about to be overwritten)
+        KktDualEpi<T, UNSCALE> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, kty_out};
+        if ((rc = launch_csr<T>(h, true, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
+        if (which == PDLP_CUR && h->kx_valid && !h->no_running) {
+            // K x of the current iterate is carried along by the dual half-steps (kxb[0]): no product
+            KktPrimalEpi<T, UNSCALE> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, nullptr, h->ineq_end};
+            if ((rc = epilogue_pass<T>(h, h->ml, h->kxb[0], ep, h->partB)) != PDLP_OK) return rc;
+            gridB = rows_grid(h->ml);
+            h->cur_kx_cached = true;
+        } else {
+            KktPrimalEpi<T, UNSCALE> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, kx_out, h->ineq_end};
+            if ((rc = launch_csr<T>(h, false, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
+            if (which == PDLP_CUR) h->cur_kx_cached = false;
+        }
+    }
+    if ((rc = finalize_kkt(h, gridA, gridB)) != PDLP_OK) return rc;
+    if (which != PDLP_PREV) h->cand_valid[which == PDLP_CUR ? 0 : 1] = true;
+    return PDLP_OK;
+}
+
+template <typename T> int kkt_local_t(pdlp_handle h, int which, int unscaled)
+{
+    return unscaled ? kkt_local_u<T, true>(h, which) : kkt_local_u<T, false>(h, which);
+}
+
+// Solution report (pdlp_report_local): reduced costs and row activities of an iterate stored, with the six KKT sums.  The two
+// products are the plain ones of pdlp_spmv (StoreEpi: instantiated for every kernel family; float64 accumulation over the float32
+// matrix in mixed precision, never the delta-mode anchors) written straight into the caller's vectors; a vector pass over each
+// then forms the sums and turns K'y into lam in place.  A vector the caller does not want (null) costs nothing extra: that side
+// runs the KKT pass's own fused epilogue without its stores.  Nothing of the solver's state is read except the iterate and
+// nothing is written except scratch (partial sums, row sums, PDLP_BUF_RED).
+template <typename T, bool UNSCALE> int report_local_u(pdlp_handle h, int which, void* rc_local, void* act_local)
+{
+    const int ix = iterate_index(h, which);
+    const T* dcol = UNSCALE ? (const T*)h->p.d_col : nullptr;
+    const T* drow = UNSCALE ? (const T*)h->p.d_row : nullptr;
+    int rc, gridA = grid_of(h->sKT, h->nl), gridB = grid_of(h->sK, h->ml);
+    if (rc_local) {
+        StoreEpi<T> st{(T*)rc_local};
+        if ((rc = launch_csr<T>(h, true, h->yb[ix], st, h->partA)) != PDLP_OK) return rc;
+        ReportDualEpi<T, UNSCALE> ed{(T*)rc_local, xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol};
+        if ((rc = epilogue_pass<T>(h, h->nl, nullptr, ed, h->partA)) != PDLP_OK) return rc;
+        gridA = rows_grid(h->nl);
+    } else {
+        KktDualEpi<T, UNSCALE> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, nullptr};
+        if ((rc = launch_csr<T>(h, true, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
+    }
+    if (act_local) {
+        StoreEpi<T> st{(T*)act_local};
+        if ((rc = launch_csr<T>(h, false, h->xb[ix], st, h->partB)) != PDLP_OK) return rc;
+        ReportPrimalEpi<T, UNSCALE> ep{(T*)act_local, yloc<T>(h, ix), (const T*)h->p.q, drow, h->ineq_end};
+        if ((rc = epilogue_pass<T>(h, h->ml, nullptr, ep, h->partB)) != PDLP_OK) return rc;
+        gridB = rows_grid(h->ml);
+    } else {
+        KktPrimalEpi<T, UNSCALE> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, nullptr, h->ineq_end};
+        if ((rc = launch_csr<T>(h, false, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
+    }
+    return finalize_kkt(h, gridA, gridB);
+}
+
+template <typename T> int report_local_t(pdlp_handle h, int which, int unscaled, void* rc_local, void* act_local)
+{
+    return unscaled ? report_local_u<T, true>(h, which, rc_local, act_local) : report_local_u<T, false>(h, which, rc_local, act_local);
+}
+
+template <typename T> void kkt_finish_t(const double* r, double omega_d, double* out)
+{
+    // helpers.py:84-94,102-106 in the working precision
+    const T p = (T)r[3], d = (T)r[5], lp = (T)r[1], un = (T)r[2];
+    const T adj = d + lp + un;
+    const T gap = adj - p;
+    const T pr = (T)std::sqrt(r[4]), dr = (T)std::sqrt(r[0]);
+    const T w = (T)omega_d, w2 = w * w;
+    const T kkt = (T)std::sqrt((double)(w2 * (pr * pr) + (dr * dr) / w2 + gap * gap));
+    out[0] = pr; out[1] = dr; out[2] = gap; out[3] = p; out[4] = adj; out[5] = kkt;
+}
+
+template <typename T> int flush_t(pdlp_handle h, int adaptive)
+{
+    const bool running = !h->delta && !h->sums_broken && !h->no_running && !h->graph_ok && h->since_reset > 0;
+    if (adaptive) {
+        // the weight of the current iterate became known only after its step-size rule: add it now
+        hipLaunchKernelGGL(k_flush<T>, dim3(grid_for(h->nl)), dim3(BLOCK), 0, h->stream, h->nl, (T*)h->x_sum,
+                           (const T*)xloc<T>(h, h->ix_cur), h->sc, (int)S_WPEND);
+        hipLaunchKernelGGL(k_flush<T>, dim3(grid_for(h->ml)), dim3(BLOCK), 0, h->stream, h->ml, (T*)h->y_sum,
+                           (const T*)yloc<T>(h, h->ix_cur), h->sc, (int)S_WPEND);
+        if (running && h->kx_valid)
+            hipLaunchKernelGGL(k_flush<T>, dim3(grid_for(h->ml)), dim3(BLOCK), 0, h->stream, h->ml, (T*)h->kx_sum, (const T*)h->kxb[0],
+                               h->sc, (int)S_WPEND);
+    }
+    // K'y of the current y exists only if the KKT pass of the current iterate ran before this call (it keeps it in ktyb[0])
+    if (running && !h->kty_tail_done) {
+        if (h->cand_valid[0] && h->kty_cur < 0) {
+            hipLaunchKernelGGL(k_flush<T>, dim3(grid_for(h->nl)), dim3(BLOCK), 0, h->stream, h->nl, (T*)h->kty_sum, (const T*)h->ktyb[0],
+                               h->sc, (int)(adaptive ? S_WPEND : S_ETA));
+            h->kty_tail_done = true;
+        } else if (adaptive) {
+            h->sums_broken = true;       // the pending weight is cleared below: that term of the sum is lost until the next restart
+        }
+    }
+    if (adaptive) hipLaunchKernelGGL(k_clear_pending, dim3(1), dim3(1), 0, h->stream, h->sc);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+template <typename T> int average_t(pdlp_handle h)
+{
+    hipLaunchKernelGGL(k_average<T>, dim3(grid_for(h->nl)), dim3(BLOCK), 0, h->stream, h->nl, xloc<T>(h, h->ix_avg),
+                       (const T*)h->x_sum, h->sc);
+    hipLaunchKernelGGL(k_average<T>, dim3(grid_for(h->ml)), dim3(BLOCK), 0, h->stream, h->ml, yloc<T>(h, h->ix_avg),
+                       (const T*)h->y_sum, h->sc);
+    // the products of the average from the running sums (K is linear): K x_avg = sum w_k K x_k / sum w_k, the same for K'y
+    h->avg_products = false;
+    if (!h->delta && !h->sums_broken && !h->no_running && !h->graph_ok && h->since_reset > 0 && h->kty_tail_done && h->kx_valid) {
+        hipLaunchKernelGGL(k_average<T>, dim3(grid_for(h->ml)), dim3(BLOCK), 0, h->stream, h->ml, (T*)h->kxb[2], (const T*)h->kx_sum, h->sc);
+        hipLaunchKernelGGL(k_average<T>, dim3(grid_for(h->nl)), dim3(BLOCK), 0, h->stream, h->nl, (T*)h->ktyb[1], (const T*)h->kty_sum, h->sc);
+        if (h->kty_cur == 1) h->kty_cur = -1;
+        h->avg_products = true;
+    }
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+template <typename T> int distance_t(pdlp_handle h)
+{
+    const int ga = grid_for(h->nl), gb = grid_for(h->ml);
+    hipLaunchKernelGGL(k_sqdiff<T>, dim3(ga), dim3(BLOCK), 0, h->stream, h->nl, (const T*)h->x_last,
+                       (const T*)xloc<T>(h, h->ix_cur), h->partA);
+    hipLaunchKernelGGL(k_sqdiff<T>, dim3(gb), dim3(BLOCK), 0, h->stream, h->ml, (const T*)h->y_last,
+                       (const T*)yloc<T>(h, h->ix_cur), h->partB);
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partA, ga, 1, h->red, 0);
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partB, gb, 1, h->red, 1);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+// dx, dy of the step just taken (cur vs prev) into this rank's blocks of the full-length buffers
+template <typename T> int infeas_begin_t(pdlp_handle h)
+{
+    if (h->nl > 0)
+        hipLaunchKernelGGL(k_sub<T>, dim3(grid_for(h->nl)), dim3(BLOCK), 0, h->stream, h->nl, (T*)h->dxf + h->p.col0,
+                           (const T*)xloc<T>(h, h->ix_cur), (const T*)xloc<T>(h, h->ix_prev));
+    if (h->ml > 0)
+        hipLaunchKernelGGL(k_sub<T>, dim3(grid_for(h->ml)), dim3(BLOCK), 0, h->stream, h->ml, (T*)h->dyf + h->p.row0,
+                           (const T*)yloc<T>(h, h->ix_cur), (const T*)yloc<T>(h, h->ix_prev));
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+// three products (K'dy, K'y with the variable-side tests fused, K dx with the constraint-side tests fused) and the
+// eight partial sums of detect_infeasibility into red[0..7]
+template <typename T> int infeas_local_t(pdlp_handle h, double tol)
+{
+    int rc;
+    if ((rc = spmv_t<T>(h, 1, h->dyf, h->ktdy)) != PDLP_OK) return rc;
+    InfeasDualEpi<T> ed{xloc<T>(h, h->ix_cur), xloc<T>(h, h->ix_prev), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u,
+                        (const T*)h->ktdy, (T*)h->lam_prev, (T)tol};
+    if ((rc = launch_csr<T>(h, true, h->yb[h->ix_cur], ed, h->partA)) != PDLP_OK) return rc;
+    InfeasPrimalEpi<T> ep{yloc<T>(h, h->ix_cur), yloc<T>(h, h->ix_prev), (const T*)h->p.q, (T)tol, h->ineq_end};
+    if ((rc = launch_csr<T>(h, false, h->dxf, ep, h->partB)) != PDLP_OK) return rc;
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partA, grid_of(h->sKT, h->nl), 4, h->red, 0);
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partB, grid_of(h->sK, h->ml), 4, h->red, 4);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+// the decisions of enhancements.py:118-142 and :148-159 from the eight sums, in the working precision
+template <typename T> int infeas_decide_t(const double* r, double tol, double* diag)
+{
+    const T t = (T)tol;
+    const T dres = (T)std::sqrt(r[0]), lu = (T)r[1], cdx = (T)r[2], eqn = (T)std::sqrt(r[4]), qdy = (T)r[7];
+    diag[0] = eqn; diag[1] = r[5]; diag[2] = cdx; diag[3] = r[3]; diag[4] = dres; diag[5] = r[6]; diag[6] = qdy; diag[7] = lu;
+    if (eqn < t && r[5] == 0.0 && cdx < t && r[3] == 0.0) return 1;                      // "DUAL_INFEASIBLE"
+    if (dres < t && r[6] == 0.0 && (double)qdy - (double)lu > -tol) return 2;            // "PRIMAL_INFEASIBLE"
+    return 0;
+}
+
+template <typename T> int power_iteration_t(pdlp_handle h, const void* b0, int iters, void* work_n, void* work_m, double* sigma)
+{
+    T* b = (T*)work_n;
+    T* t = (T*)work_m;
+    int rc;
+    HIP_TRY(hipMemcpyAsync(b, b0, (size_t)h->p.n * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+    const int g = grid_for(h->p.n);
+    for (int it = 0; it < iters; ++it) {                                   // helpers.py:48-50
+        if ((rc = spmv_t<T>(h, 0, b, t)) != PDLP_OK) return rc;
+        if ((rc = spmv_t<T>(h, 1, t, b)) != PDLP_OK) return rc;
+        hipLaunchKernelGGL(k_sqdiff<T>, dim3(g), dim3(BLOCK), 0, h->stream, h->p.n, (const T*)b, (const T*)nullptr, h->partA);
+        hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partA, g, 1, h->red, 0);
+        hipLaunchKernelGGL(k_div_by_norm<T>, dim3(g), dim3(BLOCK), 0, h->stream, h->p.n, b, h->red, 0);
+    }
+    if ((rc = spmv_t<T>(h, 0, b, t)) != PDLP_OK) return rc;               // helpers.py:51
+    const int gm = grid_for(h->p.m);
+    hipLaunchKernelGGL(k_sqdiff<T>, dim3(gm), dim3(BLOCK), 0, h->stream, h->p.m, (const T*)t, (const T*)nullptr, h->partA);
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partA, gm, 1, h->red, 0);
+    HIP_TRY(hipGetLastError());
+    double r = 0.0;
+    HIP_TRY(hipMemcpyAsync(&r, h->red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *sigma = (double)(T)std::sqrt(r);
+    return PDLP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pdlp_restart(pdlp_handle h, int which)
+{
+    if (!h || (which != PDLP_CUR && which != PDLP_AVG)) return PDLP_ERR_INVALID;
+    const int cand = which == PDLP_CUR ? 0 : 1;
+    if (which == PDLP_AVG) {       // the averaged iterate becomes current (pdhg.py:133,137,141)
+        const int t = h->ix_cur;
+        h->ix_cur = h->ix_avg;
+        h->ix_avg = t;
+    }
+    if (h->delta) {                // the anchors follow the iterate: K x and K'y of the average were kept by its KKT pass
+        if (which == PDLP_AVG) {
+            if (h->cand_valid[1]) {
+                char* t = h->kxb[0]; h->kxb[0] = h->kxb[2]; h->kxb[2] = t;
+                t = h->ktyr; h->ktyr = h->ktyb[1]; h->ktyb[1] = t;
+                h->dy_folded = true;
+            } else {
+                h->anchors_valid = false;
+            }
+        }
+        h->cand_valid[0] = h->cand_valid[1] = false;
+        HIP_TRY(hipMemsetAsync(h->x_sum, 0, h->nl * h->es, h->stream));
+        HIP_TRY(hipMemsetAsync(h->y_sum, 0, h->ml * h->es, h->stream));
+        hipLaunchKernelGGL(k_reset_average, dim3(1), dim3(1), 0, h->stream, h->sc);
+        HIP_TRY(hipGetLastError());
+        return PDLP_OK;
+    }
+    if (h->cand_valid[cand]) {     // K x and K'y of the chosen point were produced by its KKT pass (or carried along)
+        if (!(cand == 0 && h->cur_kx_cached)) {
+            char* t = h->kxb[0];
+            h->kxb[0] = h->kxb[1 + cand];
+            h->kxb[1 + cand] = t;
+        }
+        h->kx_valid = true;
+        h->kty_cur = cand;
+    } else {
+        h->kx_valid = false;
+        if (which == PDLP_AVG) h->kty_cur = -1;
+    }
+    h->cand_valid[0] = h->cand_valid[1] = false;
+    HIP_TRY(hipMemsetAsync(h->x_sum, 0, h->nl * h->es, h->stream));          // pdhg.py:58-60
+    HIP_TRY(hipMemsetAsync(h->y_sum, 0, h->ml * h->es, h->stream));
+    HIP_TRY(hipMemsetAsync(h->kx_sum, 0, h->ml * h->es, h->stream));
+    HIP_TRY(hipMemsetAsync(h->kty_sum, 0, h->nl * h->es, h->stream));
+    h->since_reset = 0; h->kty_tail_done = false; h->avg_products = false; h->sums_broken = false; h->cur_kx_cached = false;
+    hipLaunchKernelGGL(k_reset_average, dim3(1), dim3(1), 0, h->stream, h->sc);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+}  // extern "C"
