@@ -411,7 +411,8 @@ int pdlp_mv_product(pdlp_handle h, int nvp, const void* X, void* Y);
 int pdlp_mv_combine(int dtype, int64_t rows, int j, const void* V, const void* W, int nw, void* OUT, void* stream);
 
 /* ---- batched solves: B LPs over ONE constraint matrix (pdlp_algorithm_batch, torchpdlp_amd/batch.py) -------------------- */
-/* The LPs share K (the handle's CSR arrays, single GPU, PDLP_F32 or PDLP_F64) and differ in c, q, l, u.  Every population is a
+/* The LPs share K (the handle's CSR arrays, single GPU, PDLP_F32 or PDLP_F64; or its pattern only: pdlp_batch_attach_matrices
+ * below) and differ in c, q, l, u.  Every population is a
  * row-major device array [rows][Bp] in the working precision: column b is LP b; Bp = B rounded up to a multiple of the group
  * width W (8, 16 or 32); a launch covers all Bp / W groups.  c, q, l, u are each one shared vector ([len], *_per_lp = 0) or one
  * column per LP ([len][Bp], *_per_lp = 1).  The per-LP scalars are [Bp] arrays in the working precision: eta (the step of the
@@ -457,6 +458,23 @@ int pdlp_batch_restart(pdlp_handle h, const pdlp_batch* b, int slot);
  * sums of pdlp_batch_kkt -- for EVERY LP b < B whatever live[b] says (the report is wanted when the batch has finished and every
  * column is frozen).  Padding columns b >= B of rc, act and out are never written; nothing else of the batch is. */
 int pdlp_batch_report(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot, void* rc, void* act);
+
+/* A constraint matrix per LP over ONE sparsity pattern (no counterpart in the reference, which solves one LP per call): the LPs
+ * share the handle's row pointers and column indices, m, n and m_ineq, and each has its own non-zero values (an entry that some
+ * LPs lack is a stored zero in them).  K_valB holds the values of K in the order of the handle's CSR arrays and KT_valB those of
+ * K' in the order of its transposed copy, each a population [nnz][Bp] like every other (item p of LP b at [p * Bp + b]); d_colB
+ * [n][Bp] and d_rowB [m][Bp] are the per-LP Ruiz factors (both or neither; without them an un-scaled pass uses the problem's
+ * shared d_col / d_row).  Caller-owned device memory in the handle's precision that must outlive its use; struct pdlp_batch is
+ * unchanged.  While attached, EVERY pdlp_batch_* call multiplies with the per-LP values (the iterations with the adaptive rule's
+ * K'dy, the KKT passes, the report, the plain product) and un-scales per LP; a batch whose Bp differs from the attached one is
+ * PDLP_ERR_INVALID.  The row walk and its summation order are those of the shared matrix: an LP over its own matrix gets the bits
+ * of a shared-matrix batch over that matrix at the same W.  K_valB = KT_valB = NULL detaches.  Memory: 2 nnz Bp values. */
+int pdlp_batch_attach_matrices(pdlp_handle h, int Bp, const void* K_valB, const void* KT_valB, const void* d_colB, const void* d_rowB);
+/* The plain population product (no counterpart in the reference; the per-LP power iteration helpers.py:41-51 runs on it column by
+ * column, and the tests): Vout[rows][Bp] = K Vin (transpose = 0: Vin [n][Bp], Vout [m][Bp]) or K' Vin (transpose = 1) for every
+ * LP b < B whatever live[b] says, with the shared or the attached per-LP values; padding columns of Vout are never written, no
+ * state of the batch is read or written.  Vin and Vout must not alias. */
+int pdlp_batch_product(pdlp_handle h, const pdlp_batch* b, int transpose, const void* Vin, void* Vout);
 
 /* ---- plain products (power iteration helpers.py:41-51, tests) ------------------------------- */
 /* out_local = K in_full (transpose=0, out has row1-row0 values) or K' in_full (transpose=1) */

@@ -5,10 +5,14 @@ Rates: LP-iterations per second of ``pdlp_batch_iterate`` for B in --batches, ag
 same run, fixed and adaptive step, on a launch-bound 50k x 50k LP and on BASELINE configs[1] (1M x 1M), both 5 non-zeros per row
 (``gen_lp(..., recipe="box")``, the batch varies q per LP).  Every timed region is warmed up first and ends in a device
 synchronise; the best of --reps repetitions is reported.  End to end: the wall time of ``solve_lp_batch`` on a 32-LP
-``gen_lp_family`` to 1e-4 against 32 sequential ``solve_lp`` calls (50k shape).  Prints one JSON document.
+``gen_lp_family`` to 1e-4 against 32 sequential ``solve_lp`` calls (50k shape).  ``--per-lp-values`` runs the same shapes once more
+with a matrix per LP over the shared pattern (``K_values``: every value perturbed by 1 %) beside the shared-matrix rates of the
+same run, and the end-to-end comparison on a ``matrix_noise`` family (set-up -- the per-LP power iteration, the value populations
+-- included on both sides).  Prints one JSON document.
 
     python tools/bench_batch.py                         # everything
     python tools/bench_batch.py --shapes 1m --batches 8 --skip-e2e --reps 1   # the rocprofv3 --kernel-trace --stats run
+    python tools/bench_batch.py --per-lp-values         # + a matrix per LP
 """
 import argparse
 import json
@@ -50,7 +54,18 @@ def bytes_per_lp_iteration(n, m, nnz, B, W, es=4):
     return dict(matrix=matrix, gathers=gathers, stream=stream, total=matrix + gathers + stream)
 
 
-def rates(shape, batches, steps, reps, warm):
+def bytes_per_lp_iteration_per_lp_values(n, m, nnz, B, W, es=4):
+    """the same with a matrix per LP: the shared stream keeps its indices and row pointers (4 + 8 bytes) and every item reads
+    es bytes of ITS LP's value beside the gather -- 2 nnz es more per LP-iteration, as much as the gathers"""
+    groups = -(-B // W)
+    matrix = groups * 2 * (nnz * 4 + (n + m) * 8) / B
+    values = 2 * nnz * es
+    gathers = 2 * nnz * es
+    stream = n * 6 * es + m * 7 * es
+    return dict(matrix=matrix, values=values, gathers=gathers, stream=stream, total=matrix + values + gathers + stream)
+
+
+def rates(shape, batches, steps, reps, warm, per_lp=False):
     rows = SHAPES[shape]
     dev = torch.device("cuda", 0)
     lp = tp.gen_lp(rows, rows, 5, seed=0, device=dev)
@@ -75,22 +90,37 @@ def rates(shape, batches, steps, reps, warm):
         Q = lp.q.view(-1, 1) * (1 + 0.01 * torch.randn(lp.m, B, generator=g, device=dev))
         be = BatchEngine(K, lp.m_ineq, lp.c, Q, lp.l, lp.u, B)
         row = dict(B=B, W=be.W, Bp=be.Bp)
-        for adaptive in (False, True):
-            be.start(np.full(B, eta, np.float32), np.ones(B, np.float32))
-            be.iterate(warm, adaptive, 0)
-            k0 = [warm]
 
-            def go():
-                be.iterate(steps, adaptive, k0[0])
-                k0[0] += steps
-            dt = timed(go, reps)
-            key = "adaptive" if adaptive else "fixed"
-            row[f"{key}_lp_it_per_s"] = B * steps / dt
-            row[f"{key}_speedup"] = B * steps / dt / single[key]
-            row[f"{key}_us_per_iteration"] = dt / steps * 1e6
+        def measure(be, prefix):
+            for adaptive in (False, True):
+                be.start(np.full(B, eta, np.float32), np.ones(B, np.float32))
+                be.iterate(warm, adaptive, 0)
+                k0 = [warm]
+
+                def go():
+                    be.iterate(steps, adaptive, k0[0])
+                    k0[0] += steps
+                dt = timed(go, reps)
+                key = "adaptive" if adaptive else "fixed"
+                row[f"{prefix}{key}_lp_it_per_s"] = B * steps / dt
+                row[f"{prefix}{key}_speedup"] = B * steps / dt / single[key]
+                row[f"{prefix}{key}_us_per_iteration"] = dt / steps * 1e6
+
+        measure(be, "")
         model = bytes_per_lp_iteration(lp.n, lp.m, int(K.nnz), B, be.W)
         row["model_bytes_per_lp_iteration"] = model
         row["fixed_model_GB_per_s"] = model["total"] * row["fixed_lp_it_per_s"] / 1e9
+        if per_lp:
+            del be
+            V = K.val.view(-1, 1) * (1 + 0.01 * torch.randn(K.nnz, B, generator=g, device=dev))
+            be = BatchEngine(K, lp.m_ineq, lp.c, Q, lp.l, lp.u, B, K_values=V)
+            del V
+            measure(be, "per_lp_values_")
+            pm = bytes_per_lp_iteration_per_lp_values(lp.n, lp.m, int(K.nnz), B, be.W)
+            row["per_lp_values_model_bytes_per_lp_iteration"] = pm
+            row["per_lp_values_fixed_model_GB_per_s"] = pm["total"] * row["per_lp_values_fixed_lp_it_per_s"] / 1e9
+            row["per_lp_values_fixed_rate_ratio"] = row["per_lp_values_fixed_lp_it_per_s"] / row["fixed_lp_it_per_s"]
+            row["per_lp_values_model_rate_ratio"] = model["total"] / pm["total"]
         out["batch"].append(row)
         print(json.dumps(dict(shape=shape, **row)), file=sys.stderr, flush=True)
         del be
@@ -120,6 +150,41 @@ def end_to_end(B=32, rows=50_000):
                 max_rel_obj_diff_vs_sequential=max(rel(res.objective[b], seq[b].objective) for b in range(B)))
 
 
+def end_to_end_per_lp_values(B=32, rows=50_000, noise=0.05):
+    """a ``matrix_noise`` family: one ``solve_lp_batch(K_values=...)`` against B sequential ``solve_lp`` calls, each over its own
+    matrix (the transposed copy of every LP's matrix is built inside the timed region on both sides)"""
+    dev = torch.device("cuda", 0)
+    f = tp.gen_lp_family(rows, rows, 5, B, seed=0, matrix_noise=noise)
+    K = tp.CsrPair(f.m, f.n, f.rowptr, f.colidx, f.val).to(dev)
+    C, Q, L, U, V = (v.to(dev) for v in (f.C, f.Q, f.L, f.U, f.vals))
+    prob = (C[:, 0], K, Q[:, 0], f.m_ineq, L[:, 0], U[:, 0])
+    tp.solve_lp_batch(prob, C[:, :2], Q[:, :2], L[:, :2], U[:, :2], device=dev, seed=0, max_kkt=200, K_values=V[:, :2])        # warm-up
+    torch.cuda.synchronize()
+    times = {}
+    t0 = time.perf_counter()
+    res = tp.solve_lp_batch(prob, C, Q, L, U, device=dev, seed=0, time_limit=600, K_values=V, setup_times=times)
+    torch.cuda.synchronize()
+    t_batch = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    seq = []
+    for b in range(B):
+        Kb = tp.CsrPair(f.m, f.n, K.rowptr, K.colidx, V[:, b].contiguous())
+        seq.append(tp.solve_lp((C[:, b], Kb, Q[:, b], f.m_ineq, L[:, b], U[:, b]), device=dev, seed=0, time_limit=600))
+    torch.cuda.synchronize()
+    t_seq = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    tp.precondition.ruiz_precondition_batch(K, V)
+    torch.cuda.synchronize()
+    t_ruiz = time.perf_counter() - t0
+    rel = lambda a, b: abs(a - b) / (1 + abs(b))
+    return dict(B=B, shape=f"{rows}x{rows}", matrix_noise=noise, batch_seconds=t_batch, sequential_seconds=t_seq, speedup=t_seq / t_batch,
+                batch_solved=sum(s == "Solved" for s in res.status), sequential_solved=sum(r.status == "Solved" for r in seq),
+                batch_iterations_max=int(res.iterations.max()), sequential_iterations_sum=int(sum(r.iterations for r in seq)),
+                max_rel_obj_diff_vs_sequential=max(rel(res.objective[b], seq[b].objective) for b in range(B)),
+                max_rel_obj_diff_vs_optimum=max(rel(res.objective[b], f.opt_obj[b]) for b in range(B)),
+                power_iteration_seconds=times.get("power_iteration_seconds"), ruiz_per_lp_seconds_not_in_the_solve=t_ruiz)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="50k,1m")
@@ -128,13 +193,16 @@ def main():
     ap.add_argument("--warm", type=int, default=40)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip-e2e", action="store_true")
+    ap.add_argument("--per-lp-values", action="store_true", help="the same shapes with a matrix per LP (K_values) as well")
     a = ap.parse_args()
     batches = [int(b) for b in a.batches.split(",")]
     doc = dict(device=torch.cuda.get_device_name(0), dtype="float32", rates={})
     for s in a.shapes.split(","):
-        doc["rates"][s] = rates(s, batches, a.steps, a.reps, a.warm)
+        doc["rates"][s] = rates(s, batches, a.steps, a.reps, a.warm, a.per_lp_values)
     if not a.skip_e2e:
         doc["end_to_end"] = end_to_end()
+        if a.per_lp_values:
+            doc["end_to_end_per_lp_values"] = end_to_end_per_lp_values()
     print(json.dumps(doc, indent=1))
 
 

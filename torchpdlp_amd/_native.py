@@ -128,6 +128,8 @@ SIGNATURES = {
     "pdlp_batch_kkt": (_I, [_H, C.POINTER(PdlpBatch), _I, _I, _I]),
     "pdlp_batch_restart": (_I, [_H, C.POINTER(PdlpBatch), _I]),
     "pdlp_batch_report": (_I, [_H, C.POINTER(PdlpBatch), _I, _I, _I, _P, _P]),
+    "pdlp_batch_attach_matrices": (_I, [_H, _I, _P, _P, _P, _P]),
+    "pdlp_batch_product": (_I, [_H, C.POINTER(PdlpBatch), _I, _P, _P]),
     "pdlp_spmv": (_I, [_H, _I, _P, _P]),
     "pdlp_power_iteration": (_I, [_H, _P, _I, _P, _P, C.POINTER(_D)]),
     "pdlp_probe_stream_read": (_I, [_P, _I64, _I, _P, C.POINTER(_D)]),

@@ -211,8 +211,16 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
                    precondition: bool = False, primal_weight_update: bool = False, adaptive_stepsize: bool = False,
                    max_kkt: int = 100_000, time_limit: float = 3600, restart_period: int = 40, dtype=torch.float32,
                    seed: Optional[int] = None, compat: bool = True, x_init=None, y_init=None, trace=None, verbose: bool = False,
-                   group_width: Optional[int] = None, b0=None, report: bool = True, **unsupported) -> BatchResult:
+                   group_width: Optional[int] = None, b0=None, report: bool = True, K_values=None, setup_times: Optional[dict] = None,
+                   **unsupported) -> BatchResult:
     """Solve B LPs that share ``K`` (and ``m_ineq``) of ``problem`` and differ in ``c``, ``q``, ``l``, ``u`` in one batch.
+
+    ``K_values`` ``(nnz, B)``: a constraint matrix per LP.  The LPs then share only the sparsity pattern of ``problem``'s K (its row
+    pointers and column indices, m, n, m_ineq); column b holds the non-zero values of LP b in the order of the problem's CSR values
+    (``CsrPair.val``), a stored zero where LP b lacks the entry.  ``sparse.stack_matrices`` builds ``(pattern, values)`` from a list
+    of matrices whose patterns differ.  The step size and, with ``precondition``, the Ruiz equilibration are then per LP
+    (``setup_times`` receives ``ruiz_seconds`` and ``power_iteration_seconds``).  Device memory: ``2 * nnz * Bp * itemsize`` on top
+    of the shared copy.
 
     ``problem`` (an MPS path or ``(c, K, q, m_ineq, l, u)``) supplies K and the default vectors; each of ``c, q, l, u`` may be
     omitted, 1-D (shared) or 2-D ``(len, B)`` (one column per LP; the 2-D arguments must agree on B).  Every LP runs through the
@@ -245,16 +253,33 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     from_file = isinstance(problem, (str, os.PathLike))
     if not from_file:                        # given arrays say their lengths before any device work, a file once it is read
         check_lengths(len(problem[0]), len(problem[2]))
-    _check_start_width(batch_size(*(torch.as_tensor(v) for v in (c, q, l, u) if v is not None)), x_init, y_init)
+    if K_values is not None:
+        K_values = torch.as_tensor(K_values)
+        _check_matrix_values(K_values, problem[1].nnz if not from_file and isinstance(problem[1], CsrPair) else None)
+    _check_start_width(batch_size(*(torch.as_tensor(v) for v in (c, q, l, u, K_values) if v is not None)), x_init, y_init)
     device = resolve_device(device)
     c0, K, q0, m_ineq, l0, u0 = load_problem(problem, device, dtype, verbose, compat)
     if from_file:
         check_lengths(K.n, K.m)
+    _check_matrix_values(K_values, K.nnz)    # (a file or a dense / COO matrix says its pattern once it is CSR)
     vec = lambda v, d: (torch.as_tensor(d).reshape(-1) if v is None else torch.as_tensor(v)).to(device=device, dtype=dtype)
     C_, Q, L, U = vec(c, c0), vec(q, q0), vec(l, l0), vec(u, u0)
-    B = batch_size(C_, Q, L, U)
-    time_used, data_precond, Ks = 0.0, None, K
-    if precondition:                         # main.py:106-110: one equilibration of K, every column of c, q, l, u scaled
+    B = batch_size(C_, Q, L, U, K_values)
+    time_used, data_precond, Ks, KsV, KsTV = 0.0, None, K, None, None
+    if K_values is not None:
+        KsV = K_values.to(device=device, dtype=dtype)
+    if precondition and K_values is not None:    # main.py:106-110 per LP: each matrix equilibrated on its own, each column scaled
+        import time as _time
+        from .precondition import ruiz_precondition_batch
+        KsV, KsTV, D_col, D_row, time_used = ruiz_precondition_batch(K, KsV, device=device)
+        if setup_times is not None:
+            setup_times["ruiz_seconds"] = time_used
+        t0 = _time.time()
+        data_precond = (D_col, D_row)
+        wide = lambda v: v.view(-1, 1) if v.dim() == 1 else v
+        C_, Q, L, U = wide(C_) * D_col, wide(Q) * D_row, wide(L) / D_col, wide(U) / D_col
+        time_used += _time.time() - t0
+    elif precondition:                       # main.py:106-110: one equilibration of K, every column of c, q, l, u scaled
         import time as _time
         ones_n, ones_m = torch.ones(K.n, dtype=dtype, device=device), torch.ones(K.m, dtype=dtype, device=device)
         Ks, _, _, _, _, data_precond, time_used = ruiz_precondition(ones_n, K, ones_m, ones_n, ones_n, device=device)
@@ -272,12 +297,13 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
         Ks, m_ineq, C_, Q, L, U, device, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period,
         precondition=precondition, primal_update=primal_weight_update, adaptive=adaptive_stepsize, data_precond=data_precond,
         time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init, seed=seed, traces=traces, group_width=group_width,
-        b0=b0, report=rep)
+        b0=b0, report=rep, K_values=KsV, KT_values=KsTV, setup_times=setup_times)
     if trace is not None:
         trace.extend(traces)
-    if precondition:                         # x = D_col x_s, y = D_row y_s (pdhg.py:161-162)
-        X = data_precond[0].view(-1, 1).to(X.dtype) * X
-        Y = data_precond[1].view(-1, 1).to(Y.dtype) * Y
+    if precondition:                         # x = D_col x_s, y = D_row y_s (pdhg.py:161-162), per LP with a matrix each
+        wide = lambda d: d.reshape(d.shape[0], -1).to(X.dtype)
+        X = wide(data_precond[0]) * X
+        Y = wide(data_precond[1]) * Y
     fields = report_fields(rep)
     fields.pop("y", None)                    # (the report's y is the same un-scaled Y)
     return BatchResult(X, Y, np.asarray(obj), np.asarray(k), np.asarray(n), np.asarray(j), status, total, **fields)
@@ -288,6 +314,15 @@ def _check_start_width(B, x_init, y_init):
     for name, v in (("x_init", x_init), ("y_init", y_init)):
         if v is not None and len(v.shape) == 2 and v.shape[1] != B:
             raise ValueError(f"{name} has {v.shape[1]} columns for a batch of {B} LPs")
+
+
+def _check_matrix_values(v, nnz):
+    """``K_values``: 2-D, one row per stored entry of the pattern (``nnz``: None while the pattern is not known yet)"""
+    if v is None:
+        return
+    shape = tuple(v.shape)
+    if len(shape) != 2 or shape[1] < 1 or (nnz is not None and shape[0] != nnz):
+        raise ValueError(f"K_values must have shape ({'nnz' if nnz is None else nnz}, B), got {shape}")
 
 
 def _check_batch_arg(name, v, ln):

@@ -1,4 +1,5 @@
-"""Batched solves: B LPs that share one constraint matrix and differ in c, q, l, u, advanced together in every launch.
+"""Batched solves: B LPs that share one constraint matrix (or one sparsity pattern, each with its own values: ``K_values``) and
+differ in c, q, l, u, advanced together in every launch.
 
 ``pdlp_algorithm_batch`` runs the reference's ``pdlp_algorithm`` (``/root/reference/PDLP/primal_dual_hybrid_gradient.py:7-181``) on
 every LP of the batch at once.  A restart check only happens at ``t % restart_period == 0`` and ``t`` resets only at a restart,
@@ -40,7 +41,11 @@ class BatchEngine:
     """The device state of a batch: the populations ``[rows][Bp]`` and per-LP scalars that ``pdlp_batch_*`` work on, over the
     handle of a single-GPU ``PdlpEngine`` (its CSR arrays of K and K', its stream)."""
 
-    def __init__(self, K: CsrPair, m_ineq: int, C_, Q, L, U, B: int, d_col=None, d_row=None, W: Optional[int] = None):
+    def __init__(self, K: CsrPair, m_ineq: int, C_, Q, L, U, B: int, d_col=None, d_row=None, W: Optional[int] = None,
+                 K_values=None, KT_values=None):
+        """``K_values`` ``(nnz, B)``: a matrix per LP over K's pattern, in the order of ``K.val`` (``KT_values``: the same values
+        in the order of ``K.t_val``; default ``K_values[K.transpose_perm()]``); ``d_col`` / ``d_row`` are then ``(n, B)`` /
+        ``(m, B)``, the Ruiz factors of every LP's own matrix."""
         dev, dt = K.val.device, K.val.dtype
         if dt not in _DT:
             raise ValueError(f"unsupported dtype {dt}")
@@ -50,10 +55,28 @@ class BatchEngine:
             raise ValueError("group width must be 8, 16 or 32")
         self.Bp = -(-self.B // self.W) * self.W
         self.m, self.n, self.m_ineq = K.m, K.n, int(m_ineq)
-        first = lambda v: v if v.dim() == 1 else v[:, 0]
+        first = lambda v: v if v is None or v.dim() == 1 or v.shape[1] == 1 else v[:, 0]
         self.eng = PdlpEngine(K.m, K.n, m_ineq, (K.rowptr, K.colidx, K.val), (K.t_rowptr, K.t_colidx, K.t_val),
-                              first(C_), first(Q), first(L), first(U), d_col=d_col, d_row=d_row, tiles=False)
+                              first(C_), first(Q), first(L), first(U), d_col=first(d_col), d_row=first(d_row), tiles=False)
         self.lib, self.stream = self.eng.lib, self.eng.stream
+        self.per_lp_matrices = K_values is not None
+        # the un-scaling factors as columns: [len, 1] shared, [len, B] with a matrix per LP
+        self.d_col, self.d_row = (None if d is None else d.to(device=dev, dtype=dt).reshape(d.shape[0], -1) for d in (d_col, d_row))
+        if self.per_lp_matrices:
+            if tuple(K_values.shape) != (K.nnz, self.B):
+                raise ValueError(f"K_values must have shape ({K.nnz}, {self.B}), got {tuple(K_values.shape)}")
+            # the caller's tensor serves as the population when it already is one ([nnz, Bp], contiguous, on the device); K' is
+            # one gather of the padded K population: beside the caller's tensor at most two populations ever exist
+            self.K_valB = self._population(K_values, K.nnz)
+            self.KT_valB = self.K_valB[K.transpose_perm()] if KT_values is None else self._population(KT_values, K.nnz)
+            fac = [None, None]
+            if self.d_col is not None:
+                if self.d_col.shape[1] != self.B or self.d_row.shape[1] != self.B:
+                    raise ValueError("with K_values, d_col and d_row hold one column per LP")
+                fac = self.d_colB, self.d_rowB = self._pad(self.d_col, self.n), self._pad(self.d_row, self.m)
+            N.check(self.lib.pdlp_batch_attach_matrices(self.eng.h, self.Bp, self.K_valB.data_ptr(), self.KT_valB.data_ptr(),
+                                                        *(None if f is None else f.data_ptr() for f in fac)),
+                    "pdlp_batch_attach_matrices")
         self.vec = [self._col(v, ln) for v, ln in ((C_, self.n), (Q, self.m), (L, self.n), (U, self.n))]
         e = lambda rows: torch.zeros(rows, self.Bp, dtype=dt, device=dev)
         self.x, self.x_prev, self.xbar, self.x_sum, self.x_avg, self.x_last = (e(self.n) for _ in range(6))
@@ -78,6 +101,12 @@ class BatchEngine:
         out = torch.zeros(ln, self.Bp, dtype=self.dtype, device=self.device)
         out[:, :v.shape[1]] = v
         return out
+
+    def _population(self, v: torch.Tensor, ln: int) -> torch.Tensor:
+        """[ln, B] values as a population [ln, Bp]: ``v`` itself when it already is one, else a padded copy"""
+        if v.device == self.device and v.dtype == self.dtype and tuple(v.shape) == (ln, self.Bp) and v.is_contiguous():
+            return v
+        return self._pad(v, ln)
 
     def _pad(self, v: Optional[torch.Tensor], ln: int) -> torch.Tensor:
         out = torch.zeros(ln, self.Bp, dtype=self.dtype, device=self.device)
@@ -128,6 +157,32 @@ class BatchEngine:
                                                rc.data_ptr(), act.data_ptr()), "pdlp_batch_report")
         return rc[:, :self.B], act[:, :self.B], self.read_out()[slot]
 
+    def product(self, V: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+        """``pdlp_batch_product``: K V (V ``[n, Bp]`` -> ``[m, Bp]``) or K'V per column b < B, with every LP's own matrix when the
+        batch has them; padding columns of the result are zero"""
+        rows_in, rows_out = (self.m, self.n) if transpose else (self.n, self.m)
+        if tuple(V.shape) != (rows_in, self.Bp) or V.dtype != self.dtype or not V.is_contiguous():
+            raise ValueError(f"the population must be a contiguous ({rows_in}, {self.Bp}) tensor of {self.dtype}")
+        out = torch.zeros(rows_out, self.Bp, dtype=self.dtype, device=self.device)
+        with torch.cuda.stream(self.stream):
+            N.check(self.lib.pdlp_batch_product(self.eng.h, C.byref(self.desc), int(bool(transpose)), V.data_ptr(), out.data_ptr()),
+                    "pdlp_batch_product")
+        return out
+
+    def power_iteration(self, b0: torch.Tensor, iters: int = 100) -> np.ndarray:
+        """spectral_norm_estimate_torch (helpers.py:41-51) on every LP's matrix at once, the same start vector for each: [B]"""
+        with torch.cuda.stream(self.stream):
+            V = self._pad(b0.reshape(-1), self.n)
+            for _ in range(int(iters)):                                      # helpers.py:48-50
+                V = self.product(self.product(V), transpose=True)
+                V[:, :self.B] /= torch.linalg.vector_norm(V[:, :self.B], dim=0, keepdim=True)
+            s = torch.linalg.vector_norm(self.product(V)[:, :self.B], dim=0)  # helpers.py:51
+        s = s.double().cpu().numpy()
+        if not (np.isfinite(s) & (s > 0)).all():          # K_b'K_b b = 0 on the way (0 / 0): the start step would be NaN
+            bad = np.flatnonzero(~(np.isfinite(s) & (s > 0))).tolist()
+            raise ValueError(f"the power iteration found no norm for the matrices of LPs {bad} (all entries zero?)")
+        return s
+
     def restart(self, slot: int):
         N.check(self.lib.pdlp_batch_restart(self.eng.h, C.byref(self.desc), int(slot)), "pdlp_batch_restart")
 
@@ -163,7 +218,8 @@ class BatchDriver:
     def start(self, sigma, x_init=None, y_init=None):
         t = self.t
         self.omega = start_omega(self.q_norm, self.c_norm, t)                # pdhg.py:23
-        self.be.start(np.full(self.be.B, start_eta(sigma, t), t), self.omega, x_init, y_init)     # pdhg.py:22
+        eta = np.broadcast_to(np.asarray(start_eta(np.asarray(sigma, t), t), t), (self.be.B,))
+        self.be.start(eta, self.omega, x_init, y_init)                       # pdhg.py:22 (sigma: one for the batch, or [B])
 
     def _finish(self, idx, status):
         for i in idx:
@@ -267,10 +323,19 @@ def batch_size(*vecs) -> int:
     return bs.pop() if bs else 1
 
 
+def estimate_sigma_batch(be: BatchEngine, b0=None, power_iters=100, seed=None) -> np.ndarray:
+    """``estimate_sigma`` per LP of a batch with a matrix each: the reference's power iteration column by column on the population
+    product, from the same start vector (``b0``, or drawn from ``seed`` as ``estimate_sigma`` draws it) for every LP"""
+    if b0 is None:
+        g = torch.Generator().manual_seed(int(seed) if seed is not None else int(time.time_ns() % (2 ** 31)))
+        b0 = torch.randn(be.n, generator=g, dtype=torch.float32)
+    return be.power_iteration(b0.to(be.device), power_iters)
+
+
 def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, tol=1e-4, verbose=False, restart_period=40,
                          precondition=False, primal_update=False, adaptive=False, data_precond=None, time_limit=3600, time_used=0,
                          x_init=None, y_init=None, *, b0=None, sigma=None, seed=None, traces=None, group_width=None,
-                         report=None):
+                         report=None, K_values=None, KT_values=None, setup_times=None):
     """``pdlp_algorithm`` on B LPs with the same ``K`` at once.  ``C_``, ``Q``, ``L``, ``U``: 1-D (shared) or [len, B] (one column
     per LP), of the scaled problem when ``precondition`` (then ``data_precond`` = ``ruiz_precondition``'s: ``D_col``, ``D_row``
     give the un-scaled residuals).  ``traces``: a list of B dicts (``kkt``, ``omega``, ``restarts``) that receive every LP's trace.
@@ -278,22 +343,32 @@ def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, t
     ``report``: a dict that receives the solution report of the returned iterates -- ``y`` [m, B], ``reduced_costs`` [n, B],
     ``row_activity`` [m, B] and [B] arrays ``pr, dr, gap, p, d_adj, kkt`` (helpers.py:53-108), of the ORIGINAL problems when
     ``precondition`` -- whatever each LP's status; ``q_norm``, ``c_norm`` [B]: the norms the termination test used.
+    ``K_values`` ``(nnz, B)``: a matrix per LP over K's pattern, column b the values of LP b in the order of ``K.val``
+    (``KT_values``: the same values in the order of ``K.t_val``; permuted here when omitted).  Then ``data_precond`` is
+    ``(D_col (n, B), D_row (m, B))``, every LP's own Ruiz factors (``ruiz_precondition_batch``), the step size comes from a power
+    iteration per LP, and ``sigma`` may be one number or a [B] array.  ``setup_times``: a dict that receives
+    ``power_iteration_seconds`` when sigma is estimated here.
     Returns ``(X, Y, obj, k, n, j, status, total_time)`` with X [n, B], Y [m, B] (the scaled iterates when preconditioned, like
     ``pdlp_algorithm``'s x) and numpy arrays / a list of status strings per LP."""
     t0 = time.time()
     Kp = CsrPair.from_any(K, device=resolve_device(device))
-    B = batch_size(C_, Q, L, U)
+    B = batch_size(C_, Q, L, U, K_values)
+    if K_values is not None and tuple(K_values.shape) != (Kp.nnz, B):
+        raise ValueError(f"K_values must have shape ({Kp.nnz}, {B}), got {tuple(K_values.shape)}")
     for name, v, ln in (("x_init", x_init, Kp.n), ("y_init", y_init, Kp.m)):
         if v is not None and (v.dim() not in (1, 2) or v.shape[0] != ln or (v.dim() == 2 and v.shape[1] != B)):
             raise ValueError(f"{name} must have shape ({ln},) or ({ln}, {B}), got {tuple(v.shape)}")
     d_col, d_row = precond_factors(precondition, data_precond)
-    be = BatchEngine(Kp, m_ineq, C_, Q, L, U, B, d_col=d_col, d_row=d_row, W=group_width)
+    be = BatchEngine(Kp, m_ineq, C_, Q, L, U, B, d_col=d_col, d_row=d_row, W=group_width, K_values=K_values, KT_values=KT_values)
     t = np_type(Kp.dtype)
     # pdhg.py:19-20 per LP (as solver._global_norm: the float64 norm, rounded to the working precision)
     colnorm = lambda v: np.broadcast_to(np.sqrt((v.double().reshape(v.shape[0], -1) ** 2).sum(0).cpu().numpy()), (B,)).astype(t)
     qn, cn = colnorm(Q), colnorm(C_)
-    if sigma is None:                                                        # pdhg.py:22: K only, once for the batch
-        sigma = estimate_sigma(be.eng, b0, 100, seed)
+    if sigma is None:                                                        # pdhg.py:22: K only, once for the batch ...
+        ts = time.time()
+        sigma = estimate_sigma_batch(be, b0, 100, seed) if K_values is not None else estimate_sigma(be.eng, b0, 100, seed)
+        if setup_times is not None:                                          # ... or once per LP's own matrix
+            setup_times["power_iteration_seconds"] = time.time() - ts
     drv = BatchDriver(be, qn, cn, restart_period, primal_update=primal_update, adaptive=adaptive, precondition=precondition, tol=tol,
                       max_kkt=max_kkt, traces=traces)
     drv.start(sigma, x_init, y_init)
@@ -303,7 +378,7 @@ def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, t
             print(f"[batch] k={drv.k_global} live={int(drv.live.sum())}/{B}")
     if report is not None:
         rc, act, sums = be.report(N.CUR, unscaled=bool(precondition))
-        Yr = be.y[:, :B] * be.eng.d_row.view(-1, 1) if precondition else be.y[:, :B].clone()
+        Yr = be.y[:, :B] * be.d_row if precondition else be.y[:, :B].clone()
         report.update(y=Yr, reduced_costs=rc.clone(), row_activity=act.clone(), q_norm=qn, c_norm=cn, **kkt_from_sums(sums, drv.omega, t))
     be.synchronize()
     return (be.x[:, :B].clone(), be.y[:, :B].clone(), drv.obj, drv.k, drv.n, drv.j, list(drv.status), time.time() - t0 + time_used)

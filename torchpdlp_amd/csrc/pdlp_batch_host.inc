@@ -1,7 +1,8 @@
 // pdlp_batch_host.inc -- host side of the batched solves (pdlp_batch_*, include/pdlp_hip.h): launch shapes and the C entry points.
 // Part of pdlp_hip.hip (included at file scope after the other entry points; not a translation unit of its own).
-// Kernels: pdlp_kernel_batch.inc.  Instantiated per (dtype, W, epilogue); every flag (shared or per-LP vectors, the iteration
-// count) is a launch argument.
+// Kernels: pdlp_kernel_batch.inc.  Instantiated per (dtype, W, shared or per-LP matrix values, epilogue); every other flag (shared
+// or per-LP vectors, the iteration count) is a launch argument.  With matrices attached (pdlp_batch_attach_matrices) every product
+// here reads the per-LP values and the un-scaling epilogues the per-LP Ruiz factors.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -16,8 +17,14 @@ int batch_check(pdlp_handle h, const pdlp_batch* b)
         return PDLP_ERR_INVALID;
     if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->delta) return PDLP_ERR_STATE;     // single GPU, one precision
     if (h->p.n < 1 || h->p.m < 1) return PDLP_ERR_INVALID;
+    if (h->bm.K_val && h->bm.Bp != b->Bp) return PDLP_ERR_INVALID;      // the attached populations have another width
     return PDLP_OK;
 }
+
+// the Ruiz factors of the un-scaling epilogues: per LP when attached with the matrices, else the handle's shared ones
+inline const void* batch_dcol(pdlp_handle h) { return h->bm.d_col ? h->bm.d_col : h->p.d_col; }
+inline const void* batch_drow(pdlp_handle h) { return h->bm.d_row ? h->bm.d_row : h->p.d_row; }
+inline int batch_dper(pdlp_handle h) { return h->bm.d_col ? 1 : 0; }
 
 // the second set of partials (the adaptive rule needs two at once)
 inline double* batch_part2(const pdlp_batch* b) { return b->part + (size_t)4 * BATCH_MAXG * b->Bp; }
@@ -29,9 +36,34 @@ int batch_mv(pdlp_handle h, const pdlp_batch* b, bool transpose, const T* Vin, c
     const pdlp_problem& p = h->p;
     const int64_t* rp = transpose ? p.KT_rowptr : p.K_rowptr;
     const int32_t* ci = transpose ? p.KT_colidx : p.K_colidx;
-    const T* va = (const T*)(transpose ? p.KT_val : p.K_val);
     const dim3 grid(batch_grid(rows, W), b->Bp / W);
-    hipLaunchKernelGGL((k_batch_mv<T, W, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, b->live, epi, partials);
+    if (h->bm.K_val) {
+        const T* va = (const T*)(transpose ? h->bm.KT_val : h->bm.K_val);
+        hipLaunchKernelGGL((k_batch_mv<T, W, true, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, b->live, epi, partials);
+    } else {
+        const T* va = (const T*)(transpose ? p.KT_val : p.K_val);
+        hipLaunchKernelGGL((k_batch_mv<T, W, false, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, b->live, epi, partials);
+    }
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+// the same over every column b < B, frozen or not (the report, the plain product)
+template <typename T, int W, class Epi>
+int batch_mv_all(pdlp_handle h, const pdlp_batch* b, bool transpose, const T* Vin, const Epi& epi, double* partials)
+{
+    const int rows = (int)(transpose ? h->p.n : h->p.m);
+    const pdlp_problem& p = h->p;
+    const int64_t* rp = transpose ? p.KT_rowptr : p.K_rowptr;
+    const int32_t* ci = transpose ? p.KT_colidx : p.K_colidx;
+    const dim3 grid(batch_grid(rows, W), b->Bp / W);
+    if (h->bm.K_val) {
+        const T* va = (const T*)(transpose ? h->bm.KT_val : h->bm.K_val);
+        hipLaunchKernelGGL((k_batch_mv_all<T, W, true, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, b->B, epi, partials);
+    } else {
+        const T* va = (const T*)(transpose ? p.KT_val : p.K_val);
+        hipLaunchKernelGGL((k_batch_mv_all<T, W, false, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, b->B, epi, partials);
+    }
     HIP_TRY(hipGetLastError());
     return PDLP_OK;
 }
@@ -109,10 +141,11 @@ template <typename T, int W, bool U> int batch_kkt_w(pdlp_handle h, const pdlp_b
 {
     const T* X = (const T*)(which == PDLP_CUR ? b->x : which == PDLP_AVG ? b->x_avg : b->x_prev);
     const T* Y = (const T*)(which == PDLP_CUR ? b->y : which == PDLP_AVG ? b->y_avg : b->y_prev);
-    BKktDual<T, U> ed{X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp, (const T*)h->p.d_col};
+    BKktDual<T, U> ed{X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp, (const T*)batch_dcol(h),
+                       batch_dper(h)};
     BATCH_TRY((batch_mv<T, W>(h, b, true, Y, ed, b->part)));
     BATCH_TRY(batch_finalize(h, b, b->part, h->p.n, 4, slot, 0));
-    BKktPrimal<T, U> ep{Y, (const T*)b->q, b->q_per_lp, (const T*)h->p.d_row, (int)h->p.m_ineq};
+    BKktPrimal<T, U> ep{Y, (const T*)b->q, b->q_per_lp, (const T*)batch_drow(h), batch_dper(h), (int)h->p.m_ineq};
     BATCH_TRY((batch_mv<T, W>(h, b, false, X, ep, batch_part2(b))));
     return batch_finalize(h, b, batch_part2(b), h->p.m, 2, slot, 4);
 }
@@ -137,13 +170,12 @@ template <typename T, int W, bool U> int batch_report_w(pdlp_handle h, const pdl
     const T* Y = (const T*)(which == PDLP_CUR ? b->y : which == PDLP_AVG ? b->y_avg : b->y_prev);
     const pdlp_problem& p = h->p;
     double* out = b->out + (size_t)slot * b->Bp * 6;
-    BReportDual<T, U> ed{{X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp, (const T*)p.d_col}, (T*)rc};
-    hipLaunchKernelGGL((k_batch_mv_all<T, W, BReportDual<T, U>>), dim3(batch_grid(p.n, W), b->Bp / W), dim3(BLOCK), 0, h->stream, (int)p.n,
-                       p.KT_rowptr, p.KT_colidx, (const T*)p.KT_val, Y, b->Bp, b->B, ed, b->part);
+    BReportDual<T, U> ed{{X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp,
+                          (const T*)batch_dcol(h), batch_dper(h)}, (T*)rc};
+    BATCH_TRY((batch_mv_all<T, W>(h, b, true, Y, ed, b->part)));
     hipLaunchKernelGGL(k_batch_finalize, dim3(b->B * 4), dim3(BLOCK), 0, h->stream, (const double*)b->part, batch_grid(p.n, W), b->Bp, 4, out, 6, 0);
-    BReportPrimal<T, U> ep{{Y, (const T*)b->q, b->q_per_lp, (const T*)p.d_row, (int)p.m_ineq}, (T*)act};
-    hipLaunchKernelGGL((k_batch_mv_all<T, W, BReportPrimal<T, U>>), dim3(batch_grid(p.m, W), b->Bp / W), dim3(BLOCK), 0, h->stream, (int)p.m,
-                       p.K_rowptr, p.K_colidx, (const T*)p.K_val, X, b->Bp, b->B, ep, batch_part2(b));
+    BReportPrimal<T, U> ep{{Y, (const T*)b->q, b->q_per_lp, (const T*)batch_drow(h), batch_dper(h), (int)p.m_ineq}, (T*)act};
+    BATCH_TRY((batch_mv_all<T, W>(h, b, false, X, ep, batch_part2(b))));
     hipLaunchKernelGGL(k_batch_finalize, dim3(b->B * 2), dim3(BLOCK), 0, h->stream, (const double*)batch_part2(b), batch_grid(p.m, W), b->Bp, 2, out, 6, 4);
     HIP_TRY(hipGetLastError());
     return PDLP_OK;
@@ -159,6 +191,14 @@ template <typename T> int batch_report_t(pdlp_handle h, const pdlp_batch* b, int
     if (b->W == 8) return batch_report_w<T, 8, false>(h, b, which, slot, rc, act);
     if (b->W == 16) return batch_report_w<T, 16, false>(h, b, which, slot, rc, act);
     return batch_report_w<T, 32, false>(h, b, which, slot, rc, act);
+}
+
+template <typename T> int batch_product_t(pdlp_handle h, const pdlp_batch* b, int transpose, const void* Vin, void* Vout)
+{
+    BStore<T> es{(T*)Vout};
+    if (b->W == 8) return batch_mv_all<T, 8>(h, b, transpose != 0, (const T*)Vin, es, nullptr);
+    if (b->W == 16) return batch_mv_all<T, 16>(h, b, transpose != 0, (const T*)Vin, es, nullptr);
+    return batch_mv_all<T, 32>(h, b, transpose != 0, (const T*)Vin, es, nullptr);
 }
 
 template <typename T, int W> int batch_restart_w(pdlp_handle h, const pdlp_batch* b, int slot)
@@ -206,7 +246,7 @@ int pdlp_batch_kkt(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, 
     if ((which != PDLP_CUR && which != PDLP_AVG && which != PDLP_PREV) || slot < 0 || slot > 2) return PDLP_ERR_INVALID;
     const int rc = batch_check(h, b);
     if (rc != PDLP_OK) return rc;
-    if (unscaled && (!h->p.d_col || !h->p.d_row)) return PDLP_ERR_STATE;
+    if (unscaled && (!batch_dcol(h) || !batch_drow(h))) return PDLP_ERR_STATE;
     Range range("pdlp: batch KKT pass", h->stream);
     return DISPATCH(h, batch_kkt_t, h, b, which, unscaled, slot);
 }
@@ -216,7 +256,7 @@ int pdlp_batch_report(pdlp_handle h, const pdlp_batch* b, int which, int unscale
     if ((which != PDLP_CUR && which != PDLP_AVG && which != PDLP_PREV) || slot < 0 || slot > 2) return PDLP_ERR_INVALID;
     const int r = batch_check(h, b);
     if (r != PDLP_OK) return r;
-    if (unscaled && (!h->p.d_col || !h->p.d_row)) return PDLP_ERR_STATE;
+    if (unscaled && (!batch_dcol(h) || !batch_drow(h))) return PDLP_ERR_STATE;
     Range range("pdlp: batch solution report", h->stream);
     return DISPATCH(h, batch_report_t, h, b, which, unscaled, slot, rc, act);
 }
@@ -227,4 +267,29 @@ int pdlp_batch_restart(pdlp_handle h, const pdlp_batch* b, int slot)
     const int rc = batch_check(h, b);
     if (rc != PDLP_OK) return rc;
     return DISPATCH(h, batch_restart_t, h, b, slot);
+}
+
+int pdlp_batch_attach_matrices(pdlp_handle h, int Bp, const void* K_valB, const void* KT_valB, const void* d_colB, const void* d_rowB)
+{
+    if (!h) return PDLP_ERR_INVALID;
+    if (!K_valB && !KT_valB) {                                  // detach: back to the handle's shared matrix and factors
+        if (d_colB || d_rowB) return PDLP_ERR_INVALID;
+        h->bm = pdlp_solver::BatchMatrices();
+        return PDLP_OK;
+    }
+    if (!K_valB || !KT_valB || Bp < 8 || Bp % 8 != 0 || (d_colB == nullptr) != (d_rowB == nullptr)) return PDLP_ERR_INVALID;
+    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->delta) return PDLP_ERR_STATE;     // single GPU, one precision
+    h->bm.Bp = Bp;
+    h->bm.K_val = K_valB; h->bm.KT_val = KT_valB;
+    h->bm.d_col = d_colB; h->bm.d_row = d_rowB;
+    return PDLP_OK;
+}
+
+int pdlp_batch_product(pdlp_handle h, const pdlp_batch* b, int transpose, const void* Vin, void* Vout)
+{
+    if (!Vin || !Vout || Vin == Vout) return PDLP_ERR_INVALID;
+    const int rc = batch_check(h, b);
+    if (rc != PDLP_OK) return rc;
+    Range range("pdlp: batch product", h->stream);
+    return DISPATCH(h, batch_product_t, h, b, transpose, Vin, Vout);
 }

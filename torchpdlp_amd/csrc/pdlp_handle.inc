@@ -154,6 +154,9 @@ struct pdlp_solver {
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     bool graph_ok = false;        // pdlp_set_option(PDLP_OPT_GRAPH) turns the replay on
     struct IterGraph { bool valid = false; int ix_cur = 0, ix_prev = 0, adaptive = 0; hipGraphExec_t exec = nullptr; } graphs[12];
+    // batched solves with a matrix per LP (optional, attached by the caller: pdlp_batch_attach_matrices): the values of K and K'
+    // as populations [nnz][Bp] over the handle's pattern, the Ruiz factors as [n][Bp] / [m][Bp]; used by every pdlp_batch_* call
+    struct BatchMatrices { int Bp = 0; const void *K_val = nullptr, *KT_val = nullptr, *d_col = nullptr, *d_row = nullptr; } bm;
 };
 
 namespace {

@@ -148,7 +148,8 @@ inline int rows_grid(int64_t rows) { return rows > 0 ? grid_for(rows) : 0; }    
 // ================================================================================================
 extern "C" {
 
-// 18: pdlp_batch_* (batched solves over one matrix)
+// 18: pdlp_batch_* (batched solves over one matrix); pdlp_batch_attach_matrices and pdlp_batch_product joined them without a
+//     change to any existing signature or struct, so the number stands
 // 17: pdlp_peer_* (direct exchange over HIP IPC), PDLP_OPT_BEGIN_INLINE
 // 16: pdlp_set_option (the library reads no environment variables), pdlp_mv_product, pdlp_mv_combine, pdlp_vec_sqdist,
 //     pdlp_probe_gather, pdlp_tile_limits reports the threads per workgroup, pdlp_primal_half_piece / pdlp_dual_half_piece (results

@@ -1,4 +1,5 @@
-// pdlp_kernel_batch.inc -- batched solves: B LPs over ONE constraint matrix advanced together (pdlp_batch_*).
+// pdlp_kernel_batch.inc -- batched solves: B LPs over ONE constraint matrix, or one matrix each over one shared pattern, advanced
+// together (pdlp_batch_*).
 // Part of pdlp_hip.hip (included inside its anonymous namespace; not a translation unit of its own).
 //
 // Populations are row-major V[row][Bp]: column b is LP b, Bp is B rounded up to a multiple of the group width W (8, 16, 32).
@@ -10,6 +11,12 @@
 // four waves, then the blocks in a fixed tree (batch_block_sum: one workgroup per sum).  gridDim.x is a function of the row
 // count and W only, so an LP's
 // arithmetic does not depend on B, on its position in the batch or on the other LPs.
+//
+// Per-LP matrices (PERLP): the LPs share the pattern (row pointers, column indices) and each has its own values, a population
+// vaB[nnz][Bp] like every other: item p of column b is vaB[p * Bp + b] (64-bit index), so the W lanes of a row read one contiguous
+// segment per item, as the gather does, and the summation order of a row is the shared-matrix one.  Without the flag the kernels
+// are the shared-matrix code unchanged.  The Ruiz factors are then per LP as well (dcol[n][Bp], drow[m][Bp]: `dper` of the
+// un-scaling epilogues).
 //
 // Per-LP device scalars (working precision, [Bp]): eta (the step of the next iteration), omega, eta_sum (of the running
 // average), wpend (adaptive: the weight of the current iterate, added to the sums by the next iteration); live[Bp] (int32):
@@ -112,13 +119,13 @@ template <typename T> struct BDen {
 // arithmetic of KktDualEpi per column
 template <typename T, bool UNSCALE> struct BKktDual {
     static constexpr int NA = 4;
-    const T* X; const T* c; const T* l; const T* u; int cs, ls, us; const T* dcol;
+    const T* X; const T* c; const T* l; const T* u; int cs, ls, us; const T* dcol; int dper;
     __device__ void operator()(int j, size_t at, int, T kty, double* acc) const
     {
         T cj = BCOL(c, cs, j, at), lo = BCOL(l, ls, j, at), hi = BCOL(u, us, j, at), xj = X[at];
         T g = cj - kty;
         if (UNSCALE) {            // K_u'(D_row y) = (K_s'y)/D_col, c_u = c_s/D_col, l_u = l_s D_col, x_u = D_col x
-            const T d = dcol[j];
+            const T d = BCOL(dcol, dper, j, at);
             g = g / d; cj = cj / d; lo = lo * d; hi = hi * d; xj = xj * d;
         }
         const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
@@ -139,13 +146,13 @@ template <typename T, bool UNSCALE> struct BKktDual {
 // KKT, constraint side (helpers.py:77,87-91): ||(K x - q) with inequality rows clipped at 0||^2, q'y
 template <typename T, bool UNSCALE> struct BKktPrimal {
     static constexpr int NA = 2;
-    const T* Y; const T* q; int qs; const T* drow; int ineq_end;
+    const T* Y; const T* q; int qs; const T* drow; int dper; int ineq_end;
     __device__ void operator()(int i, size_t at, int, T kx, double* acc) const
     {
         T qi = BCOL(q, qs, i, at), yi = Y[at];
         T r = kx - qi;
         if (UNSCALE) {            // K_u (D_col x) = (K_s x)/D_row, q_u = q_s/D_row, y_u = D_row y
-            const T d = drow[i];
+            const T d = BCOL(drow, dper, i, at);
             r = r / d; qi = qi / d; yi = yi * d;
         }
         if (i < ineq_end && r > (T)0) r = (T)0;
@@ -165,7 +172,7 @@ template <typename T, bool UNSCALE> struct BReportDual {
             T lo = BCOL(kkt.l, kkt.ls, j, at), hi = BCOL(kkt.u, kkt.us, j, at);
             T g = BCOL(kkt.c, kkt.cs, j, at) - kty;
             if (UNSCALE) {
-                const T d = kkt.dcol[j];
+                const T d = BCOL(kkt.dcol, kkt.dper, j, at);
                 g = g / d; lo = lo * d; hi = hi * d;
             }
             const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
@@ -184,14 +191,21 @@ template <typename T, bool UNSCALE> struct BReportPrimal {
     BKktPrimal<T, UNSCALE> kkt; T* ACT;
     __device__ void operator()(int i, size_t at, int b, T kx, double* acc) const
     {
-        if (ACT) ACT[at] = UNSCALE ? kx / kkt.drow[i] : kx;
+        if (ACT) ACT[at] = UNSCALE ? kx / BCOL(kkt.drow, kkt.dper, i, at) : kx;
         kkt(i, at, b, kx, acc);
     }
 };
 
+// the plain population product (pdlp_batch_product): Vout[row][b] = the row sum, no state
+template <typename T> struct BStore {
+    static constexpr int NA = 0;
+    T* Vout;
+    __device__ void operator()(int, size_t at, int, T s, double*) const { Vout[at] = s; }
+};
+
 // the row walk of a launch for column b of its group: the matrix (rows x cols, CSR) times column b of Vin[cols][Bp], the epilogue
-// per row
-template <typename T, int W, class Epi>
+// per row.  PERLP: va is the population of values [nnz][Bp] and item p of this column is va[p * Bp + b]; else va[p] serves all
+template <typename T, int W, bool PERLP, class Epi>
 __device__ __forceinline__ void batch_rows(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
                                            const T* __restrict__ va, const T* __restrict__ Vin, int Bp, int b, const Epi& epi, double* acc)
 {
@@ -203,34 +217,38 @@ __device__ __forceinline__ void batch_rows(int rows, const int64_t* __restrict__
         if (r < rows) {
             T s = (T)0;
             const int64_t e = rp[r + 1];
-            for (int64_t p = rp[r]; p < e; ++p) s += va[p] * Vin[(size_t)ci[p] * Bp + b];
+            if (PERLP) {
+                for (int64_t p = rp[r]; p < e; ++p) s += va[(size_t)p * Bp + b] * Vin[(size_t)ci[p] * Bp + b];
+            } else {
+                for (int64_t p = rp[r]; p < e; ++p) s += va[p] * Vin[(size_t)ci[p] * Bp + b];
+            }
             epi(r, (size_t)r * Bp + b, b, s, acc);
         }
     }
 }
 
 // one product of the matrix (rows x cols, CSR) with a population Vin[cols][Bp], the epilogue per (row, live column)
-template <typename T, int W, class Epi>
+template <typename T, int W, bool PERLP, class Epi>
 __global__ __launch_bounds__(BLOCK) void k_batch_mv(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
                                                     const T* __restrict__ va, const T* __restrict__ Vin, int Bp,
                                                     const int32_t* __restrict__ live, Epi epi, double* __restrict__ partials)
 {
     const int b = blockIdx.y * W + (threadIdx.x & 63) % W;
     double acc[Epi::NA > 0 ? Epi::NA : 1] = {0.0};
-    if (live[b]) batch_rows<T, W>(rows, rp, ci, va, Vin, Bp, b, epi, acc);
+    if (live[b]) batch_rows<T, W, PERLP>(rows, rp, ci, va, Vin, Bp, b, epi, acc);
     if (Epi::NA > 0) batch_store_partials<W, Epi::NA>(acc, partials, Bp);
 }
 
 // the same over every LP of the batch, b < B, frozen or not (the report is wanted when all are frozen); padding columns are
 // neither read nor written
-template <typename T, int W, class Epi>
+template <typename T, int W, bool PERLP, class Epi>
 __global__ __launch_bounds__(BLOCK) void k_batch_mv_all(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
                                                         const T* __restrict__ va, const T* __restrict__ Vin, int Bp, int B, Epi epi,
                                                         double* __restrict__ partials)
 {
     const int b = blockIdx.y * W + (threadIdx.x & 63) % W;
     double acc[Epi::NA > 0 ? Epi::NA : 1] = {0.0};
-    if (b < B) batch_rows<T, W>(rows, rp, ci, va, Vin, Bp, b, epi, acc);
+    if (b < B) batch_rows<T, W, PERLP>(rows, rp, ci, va, Vin, Bp, b, epi, acc);
     if (Epi::NA > 0) batch_store_partials<W, Epi::NA>(acc, partials, Bp);
 }
 

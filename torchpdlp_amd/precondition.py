@@ -135,3 +135,21 @@ def ruiz_precondition(c, K, q, l, u, device=None, max_iter=20, eps=1e-6):
     torch.cuda.current_stream(dev).synchronize()
     col = lambda v: v.view(-1, 1)
     return (Ks, col(c_s), col(q_s), col(l_s), col(u_s), (col(D_col), col(D_row), K, c, q, l, u), time.time() - t0)
+
+
+def ruiz_precondition_batch(K, K_values, device=None, max_iter=20, eps=1e-6):
+    """``ruiz_precondition`` of every LP's matrix of a batch over one pattern: ``K`` (a ``CsrPair``) gives the pattern, column b of
+    ``K_values`` ``(nnz, B)`` the values of LP b in its CSR order.  A host loop over the LPs (set-up, once per solve).  Returns
+    ``(Ks_values (nnz, B), KsT_values (nnz, B) in the order of K', D_col (n, B), D_row (m, B), seconds)``."""
+    t0 = time.time()
+    Kp = CsrPair.from_any(K, device=device)
+    vals = K_values.to(device=Kp.device, dtype=Kp.dtype)
+    perm = Kp.transpose_perm()
+    ones_n, ones_m = torch.ones(Kp.n, dtype=Kp.dtype, device=Kp.device), torch.ones(Kp.m, dtype=Kp.dtype, device=Kp.device)
+    sv, stv, dc, dr = [], [], [], []
+    for b in range(vals.shape[1]):
+        Ks, _, _, _, _, dp, _ = ruiz_precondition(ones_n, Kp.with_values(vals[:, b].contiguous(), perm), ones_m, ones_n, ones_n,
+                                                  device=Kp.device, max_iter=max_iter, eps=eps)
+        sv.append(Ks.val); stv.append(Ks.t_val); dc.append(dp[0].view(-1)); dr.append(dp[1].view(-1))
+    st = lambda cols: torch.stack(cols, dim=1).contiguous()
+    return st(sv), st(stv), st(dc), st(dr), time.time() - t0

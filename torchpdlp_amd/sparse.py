@@ -78,6 +78,13 @@ def csr_transpose(rowptr: torch.Tensor, colidx: torch.Tensor, val: torch.Tensor,
     return t_rowptr, t_col, t_val
 
 
+def transpose_perm(rowptr: torch.Tensor, colidx: torch.Tensor, m: int, n: int) -> torch.Tensor:
+    """int64 [nnz]: where every item of CSR(K') sits in CSR(K) -- ``t_val = val[perm]`` for any values over the same pattern, in
+    the order ``csr_transpose`` gives.  The positions travel as int64 (as float32 values they would only be exact below 2^24)."""
+    pos = torch.arange(int(colidx.numel()), dtype=torch.int64, device=colidx.device)
+    return csr_transpose(rowptr, colidx, pos, m, n)[2]
+
+
 class CsrPair:
     """K (m x n) as CSR plus K' as CSR, on one device, values in ``dtype``."""
 
@@ -161,6 +168,15 @@ class CsrPair:
         return CsrPair(self.m, self.n, mv(self.rowptr), mv(self.colidx), mv(self.val).to(dtype),
                        mv(self.t_rowptr), mv(self.t_colidx), mv(self.t_val).to(dtype))
 
+    def transpose_perm(self) -> torch.Tensor:
+        """``t_val = val[perm]`` (``sparse.transpose_perm`` of this pattern)"""
+        return transpose_perm(self.rowptr, self.colidx, self.m, self.n)
+
+    def with_values(self, val: torch.Tensor, perm: Optional[torch.Tensor] = None) -> "CsrPair":
+        """the same pattern (index arrays shared, not copied) with other values, given in the order of ``val``"""
+        perm = self.transpose_perm() if perm is None else perm
+        return CsrPair(self.m, self.n, self.rowptr, self.colidx, val, self.t_rowptr, self.t_colidx, val[perm])
+
     def clone(self) -> "CsrPair":
         return CsrPair(self.m, self.n, self.rowptr, self.colidx, self.val.clone(), self.t_rowptr, self.t_colidx,
                        self.t_val.clone())
@@ -183,6 +199,32 @@ class CsrPair:
         K = torch.zeros(self.m, self.n, dtype=self.dtype, device=self.device)
         K.index_put_((rows, self.colidx.long()), self.val, accumulate=True)
         return K
+
+
+def stack_matrices(mats, device=None, dtype=None) -> Tuple[CsrPair, torch.Tensor]:
+    """B matrices of one shape (dense / COO / CSR tensors, scipy sparse, ``CsrPair``) -> ``(pattern, values)``: a ``CsrPair`` over
+    the UNION of their sparsity patterns (columns sorted inside each row; its own values are those of the first matrix) and
+    ``values`` ``(nnz, B)`` in its CSR order, column b the values of matrix b -- an entry a matrix lacks is a stored zero, an entry
+    it holds twice is summed.  What ``solve_lp_batch(K_values=...)`` takes for LPs whose matrices differ."""
+    ks = [CsrPair.from_any(K, device=device, dtype=dtype) for K in mats]
+    if not ks:
+        raise ValueError("stack_matrices needs at least one matrix")
+    m, n, dev, dt = ks[0].m, ks[0].n, ks[0].device, ks[0].dtype
+    for b, k in enumerate(ks):
+        if (k.m, k.n) != (m, n):
+            raise ValueError(f"matrix {b} has shape {(k.m, k.n)}, matrix 0 has {(m, n)}")
+        if k.device != dev or k.dtype != dt:
+            raise ValueError("the matrices must share a device and a dtype (pass device= / dtype=)")
+    keys = []
+    for k in ks:            # (row, column) of every item as one integer: row-major order is the order of the keys
+        rows = torch.repeat_interleave(torch.arange(m, dtype=torch.int64, device=dev), k.rowptr[1:] - k.rowptr[:-1])
+        keys.append(rows * n + k.colidx.long())
+    union = torch.unique(torch.cat(keys))                      # sorted
+    vals = torch.zeros(union.numel(), len(ks), dtype=dt, device=dev)
+    for b, (k, key) in enumerate(zip(ks, keys)):
+        vals[:, b].index_add_(0, torch.searchsorted(union, key), k.val)
+    rowptr = _counts_to_rowptr(torch.bincount(torch.div(union, n, rounding_mode="floor"), minlength=m))
+    return CsrPair(m, n, rowptr, (union % n).to(torch.int32), vals[:, 0].contiguous()), vals
 
 
 def as_vec(v: torch.Tensor, length: Optional[int] = None, device=None, dtype=None) -> torch.Tensor:

@@ -231,6 +231,7 @@ class LPFamily:
     X_opt: torch.Tensor    # [n, B]
     Y_opt: torch.Tensor    # [m, B]
     opt_obj: list          # B floats
+    vals: Optional[torch.Tensor] = None    # dtype [nnz, B]: a matrix per LP over the pattern (matrix_noise > 0), else None
 
     @property
     def B(self) -> int:
@@ -238,9 +239,13 @@ class LPFamily:
 
 
 def gen_lp_family(n: int, m: int, nnz_per_row: int, B: int, seed: int = 0, dtype=torch.float32, device="cpu",
-                  ineq_frac: float = 0.8) -> LPFamily:
+                  ineq_frac: float = 0.8, matrix_noise: float = 0.0) -> LPFamily:
     """One K of the "mixed" recipe and B columns (c, q, l, u), each drawn with that recipe's complementary-slackness construction
-    from a generator of its own (seed, column): all four bound classes of project_lambda_box, an optimal pair built in."""
+    from a generator of its own (seed, column): all four bound classes of project_lambda_box, an optimal pair built in.
+    ``matrix_noise`` > 0: every LP gets a matrix of its own over K's pattern, ``K_b = K o (1 + matrix_noise E_b)`` with
+    ``E_b ~ U(-1, 1)`` per entry from one more generator of its own (``vals[:, b]``, rounded to ``dtype``); ``q_b`` and ``c_b``
+    are built from ``K_b`` by the same construction, so ``X_opt[:, b]``, ``Y_opt[:, b]`` are optimal for LP b over ``K_b`` (the
+    draws of x, y, the bounds and the slacks are those of ``matrix_noise = 0``)."""
     device = torch.device(device)
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
@@ -250,7 +255,7 @@ def gen_lp_family(n: int, m: int, nnz_per_row: int, B: int, seed: int = 0, dtype
     rowptr = torch.arange(0, (m + 1) * k, k, dtype=torch.int64, device=device)
     val = torch.randn(m * k, generator=gen, device=device, dtype=torch.float64).to(dtype)
     cols = {key: [] for key in ("c", "q", "l", "u", "x", "y")}
-    objs = []
+    objs, mats = [], []
     for b in range(int(B)):
         g = torch.Generator(device=device)
         g.manual_seed(int(seed) * 1_000_003 + 7919 * (b + 1))
@@ -269,16 +274,24 @@ def gen_lp_family(n: int, m: int, nnz_per_row: int, B: int, seed: int = 0, dtype
         lam = torch.zeros(n, dtype=torch.float64, device=device)
         lam = torch.where(at_bound & ((cls == 0) | (cls == 1)), lam_mag, lam)
         lam = torch.where(at_bound & (cls == 2), -lam_mag, lam)
-        kx = _regular_matvec(col, val, x, m, k, 1 << 20)
+        val_b = val
+        if matrix_noise:
+            gk = torch.Generator(device=device)
+            gk.manual_seed(int(seed) * 1_000_003 + 7919 * (b + 1) + 104_729)
+            E = torch.rand(m * k, generator=gk, device=device, dtype=torch.float64) * 2.0 - 1.0
+            val_b = (val.double() * (1.0 + float(matrix_noise) * E)).to(dtype)
+            mats.append(val_b)
+        kx = _regular_matvec(col, val_b, x, m, k, 1 << 20)
         active = torch.rand(m, generator=g, device=device) < 0.5
         slack = torch.where(active, torch.zeros(m, dtype=torch.float64, device=device), U_(m, 0.1, 2.0))
         q = kx.clone()
         q[:m_ineq] -= slack[:m_ineq]
         y = torch.randn(m, generator=g, device=device, dtype=torch.float64)
         y[:m_ineq] = torch.where(active[:m_ineq], y[:m_ineq].abs(), torch.zeros_like(y[:m_ineq]))
-        c = _regular_rmatvec(col, val, y, m, n, k, 1 << 20) + lam
+        c = _regular_rmatvec(col, val_b, y, m, n, k, 1 << 20) + lam
         objs.append(float((c * x).sum()))
         for key, v in (("c", c), ("q", q), ("l", lo), ("u", hi), ("x", x), ("y", y)):
             cols[key].append(v)
     st = lambda key: torch.stack(cols[key], dim=1).to(dtype)
-    return LPFamily(m, n, m_ineq, rowptr, col, val, st("c"), st("q"), st("l"), st("u"), st("x"), st("y"), objs)
+    return LPFamily(m, n, m_ineq, rowptr, col, val, st("c"), st("q"), st("l"), st("u"), st("x"), st("y"), objs,
+                    torch.stack(mats, dim=1).contiguous() if mats else None)
