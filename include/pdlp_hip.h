@@ -476,6 +476,45 @@ int pdlp_batch_attach_matrices(pdlp_handle h, int Bp, const void* K_valB, const 
  * state of the batch is read or written.  Vin and Vout must not alias. */
 int pdlp_batch_product(pdlp_handle h, const pdlp_batch* b, int transpose, const void* Vin, void* Vout);
 
+/* ---- streaming a family through the columns of a batch (pdlp_algorithm_batch(slots=...), torchpdlp_amd/batch.py) ------------ */
+/* A family of N LPs longer than the batch is wide: a column whose LP has finished is retired (its results stored into column id of
+ * the caller's [len][N] arrays) and given to the next LP of the family (admitted from column id of the feed).  Restart checks fall
+ * on multiples of the restart period of each LP's own iteration count, so an LP admitted at a check runs the control flow -- and,
+ * with the calls below, gets the bits -- it would have in a batch that started with it, at the same W.  struct pdlp_batch is
+ * unchanged; live[] stays the caller's to set. */
+/* pdlp_batch_iterate for columns that entered the batch at different times: k_start[Bp] (device, int64) is the batch's iteration
+ * count at which the LP of column b was admitted, and the adaptive rule of column b uses k0 + it + 1 - k_start[b] where
+ * pdlp_batch_iterate uses k0 + it + 1.  k_start = NULL: pdlp_batch_iterate, bit for bit. */
+int pdlp_batch_iterate_from(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0, const int64_t* k_start);
+/* The source of an admission: N columns, in the working precision, on the device. */
+typedef struct pdlp_batch_feed {
+    int32_t N;                  /* columns of every array below                                                      */
+    const void* c;              /* [n][N], or NULL where the batch shares the vector (c_per_lp = 0)                  */
+    const void* q;              /* [m][N], or NULL                                                                   */
+    const void* l;              /* [n][N], or NULL                                                                   */
+    const void* u;              /* [n][N], or NULL                                                                   */
+    const void* x0;             /* [n][N] start points, or NULL: zeros                                               */
+    const void* y0;             /* [m][N], or NULL: zeros                                                            */
+    const void* K_val;          /* [nnz][N] values in the order of K's CSR arrays; both or neither, given exactly    */
+    const void* KT_val;         /* [nnz][N] values in the order of K' ... when matrices are attached                 */
+    const void* eta;            /* [N] first step sizes                                                              */
+    const void* omega;          /* [N] first primal weights                                                          */
+} pdlp_batch_feed;
+/* For i < count (device arrays cols, ids), column cols[i] of the batch receives column ids[i] of the feed: c, q, l, u (where per
+ * LP) and both value populations (where attached) are copied; x = x_last = x0, y = y_last = y0 (pdhg.py:22-48, 63-64); x_sum,
+ * y_sum, eta_sum and wpend are zeroed; eta and omega are set.  No other column and no other byte is written (x_prev, xbar, x_avg,
+ * y_prev, y_avg, dy of the column keep what they held: every one is written before it is read).  One launch per side (n rows,
+ * m rows, nnz items).  A column must not be listed twice; entries with a column outside [0, Bp) or an id outside [0, N) are
+ * skipped.  PDLP_ERR_INVALID when the feed lacks a vector the batch holds per LP or brings one it shares. */
+int pdlp_batch_admit(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids, const pdlp_batch_feed* f);
+/* pdlp_batch_report for the listed columns only, stored where the results of the family live: for i < count, column ids[i] of
+ * X_out [n][N] and Y_out [m][N] receives the iterate `which` of column cols[i], of rc_out [n][N] / act_out [m][N] (either may be
+ * NULL) lam resp. K x, and out[slot][cols[i]][0..5] the six sums -- through the partial sums and the tree of pdlp_batch_report, so
+ * the numbers are its numbers.  unscaled as there (x and y are stored as they are: the scaled iterates).  Groups of columns
+ * without a listed one do no work; nothing of the batch but part and out is written. */
+int pdlp_batch_retire(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids, int which, int unscaled,
+                      int slot, void* X_out, void* Y_out, void* rc_out, void* act_out, int N);
+
 /* ---- plain products (power iteration helpers.py:41-51, tests) ------------------------------- */
 /* out_local = K in_full (transpose=0, out has row1-row0 values) or K' in_full (transpose=1) */
 int pdlp_spmv(pdlp_handle h, int transpose, const void* in_full, void* out_local);

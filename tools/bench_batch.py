@@ -13,6 +13,13 @@ same run, and the end-to-end comparison on a ``matrix_noise`` family (set-up -- 
     python tools/bench_batch.py                         # everything
     python tools/bench_batch.py --shapes 1m --batches 8 --skip-e2e --reps 1   # the rocprofv3 --kernel-trace --stats run
     python tools/bench_batch.py --per-lp-values         # + a matrix per LP
+    python tools/bench_batch.py --stream 32             # a family of 256 LPs: streamed, chunked loop, one plain batch
+
+``--stream SLOTS`` solves one ``gen_lp_family`` of ``--family`` LPs (50k x 50k) three ways in one process -- streamed through SLOTS
+columns (``solve_lp_batch(slots=SLOTS)``), as the loop of plain ``solve_lp_batch`` calls over chunks of SLOTS LPs that a user writes
+without it, and as one plain batch -- each timed ``--reps`` times after a warm-up, all at the group width the chunks get.  It
+prints the three lists of wall times, the distribution of the per-LP iteration counts, and whether the three agree bit for bit.
+``--spread F``: that fraction of the LPs starts at its built-in optimum (solved at its first check), which spreads the counts.
 """
 import argparse
 import json
@@ -185,6 +192,67 @@ def end_to_end_per_lp_values(B=32, rows=50_000, noise=0.05):
                 power_iteration_seconds=times.get("power_iteration_seconds"), ruiz_per_lp_seconds_not_in_the_solve=t_ruiz)
 
 
+def stream_family(slots, family, spread, reps, rows=50_000, only_streamed=False):
+    dev = torch.device("cuda", 0)
+    t0 = time.perf_counter()
+    f = tp.gen_lp_family(rows, rows, 5, family, seed=0)
+    print(f"family of {family} generated in {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
+    K = tp.CsrPair(f.m, f.n, f.rowptr, f.colidx, f.val).to(dev)
+    C, Q, L, U = (v.to(dev) for v in (f.C, f.Q, f.L, f.U))
+    X0, Y0 = torch.zeros(f.n, family, device=dev), torch.zeros(f.m, family, device=dev)
+    if spread > 0:
+        step = max(1, round(1 / spread))
+        X0[:, ::step], Y0[:, ::step] = f.X_opt[:, ::step].float().to(dev), f.Y_opt[:, ::step].float().to(dev)
+    prob = (C[:, 0], K, Q[:, 0], f.m_ineq, L[:, 0], U[:, 0])
+    W = tp.batch.group_width(slots, torch.float32)
+    kw = dict(device=dev, seed=0, time_limit=600, group_width=W)
+    cols = lambda a, b: dict(c=C[:, a:b], q=Q[:, a:b], l=L[:, a:b], u=U[:, a:b], x_init=X0[:, a:b], y_init=Y0[:, a:b])
+    tp.solve_lp_batch(prob, **cols(0, 2 * slots), slots=slots, max_kkt=200, **kw)          # warm-up (every kernel of the three ways)
+    torch.cuda.synchronize()
+
+    def streamed():
+        return [tp.solve_lp_batch(prob, **cols(0, family), slots=slots, **kw)]
+
+    def chunked():
+        return [tp.solve_lp_batch(prob, **cols(a, min(a + slots, family)), **kw) for a in range(0, family, slots)]
+
+    def plain():
+        return [tp.solve_lp_batch(prob, **cols(0, family), **kw)]
+
+    out = dict(slots=slots, family=family, W=W, shape=f"{rows}x{rows}", spread=spread, reps=reps)
+    results = {}
+    for name, fn in (("streamed", streamed), ("chunked", chunked), ("plain", plain)):
+        if only_streamed and name != "streamed":
+            continue
+        times = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        results[name] = res
+        out[f"{name}_seconds"] = times
+        out[f"{name}_best"] = min(times)
+        print(json.dumps({name: times}), file=sys.stderr, flush=True)
+    cat = lambda rs, key: np.concatenate([np.asarray(getattr(r, key)) for r in rs])
+    its = cat(results["streamed"], "iterations")
+    out["iterations"] = dict(min=int(its.min()), p25=int(np.percentile(its, 25)), median=int(np.median(its)),
+                             p75=int(np.percentile(its, 75)), max=int(its.max()), sum=int(its.sum()))
+    out["solved"] = int(sum(s == "Solved" for r in results["streamed"] for s in r.status))
+    if not only_streamed:
+        # the iterations a column spends waiting for the slowest LP of its chunk / of the whole batch
+        per_chunk = [int(r.iterations.max()) * len(r) for r in results["chunked"]]
+        out["column_iterations"] = dict(useful=int(its.sum()), chunked=int(sum(per_chunk)), plain=int(its.max()) * family)
+        out["streamed_over_chunked"] = out["streamed_best"] / out["chunked_best"]
+        out["chunked_spread"] = (max(out["chunked_seconds"]) - min(out["chunked_seconds"])) / min(out["chunked_seconds"])
+        same = lambda a, b: bool(torch.equal(torch.cat([r.x for r in a], 1), torch.cat([r.x for r in b], 1)) and
+                                 (cat(a, "iterations") == cat(b, "iterations")).all())
+        out["streamed_equals_plain"] = same(results["streamed"], results["plain"])
+        out["chunked_equals_plain"] = same(results["chunked"], results["plain"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="50k,1m")
@@ -194,7 +262,16 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip-e2e", action="store_true")
     ap.add_argument("--per-lp-values", action="store_true", help="the same shapes with a matrix per LP (K_values) as well")
+    ap.add_argument("--stream", type=int, default=0, metavar="SLOTS", help="a long family streamed through SLOTS columns, against "
+                    "the loop over chunks of SLOTS and one plain batch (nothing else is run)")
+    ap.add_argument("--family", type=int, default=256, help="LPs of the --stream family")
+    ap.add_argument("--spread", type=float, default=0.0, help="fraction of the --stream family that starts at its optimum")
+    ap.add_argument("--stream-only", action="store_true", help="--stream: the streamed solve alone (the kernel-trace run)")
     a = ap.parse_args()
+    if a.stream:
+        print(json.dumps(dict(device=torch.cuda.get_device_name(0), dtype="float32",
+                              stream=stream_family(a.stream, a.family, a.spread, a.reps, only_streamed=a.stream_only)), indent=1))
+        return
     batches = [int(b) for b in a.batches.split(",")]
     doc = dict(device=torch.cuda.get_device_name(0), dtype="float32", rates={})
     for s in a.shapes.split(","):

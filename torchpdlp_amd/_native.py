@@ -55,6 +55,13 @@ class PdlpBatch(C.Structure):
                 ("live", C.c_void_p), ("action", C.c_void_p), ("part", C.c_void_p), ("out", C.c_void_p)]
 
 
+class PdlpBatchFeed(C.Structure):
+    """mirror of ``struct pdlp_batch_feed`` (the source of ``pdlp_batch_admit``)"""
+    _fields_ = [("N", C.c_int32), ("c", C.c_void_p), ("q", C.c_void_p), ("l", C.c_void_p), ("u", C.c_void_p),
+                ("x0", C.c_void_p), ("y0", C.c_void_p), ("K_val", C.c_void_p), ("KT_val", C.c_void_p),
+                ("eta", C.c_void_p), ("omega", C.c_void_p)]
+
+
 BATCH_PART_PER_COL = 2 * 4 * 8192          # PDLP_BATCH_PART_PER_COL
 
 
@@ -130,6 +137,9 @@ SIGNATURES = {
     "pdlp_batch_report": (_I, [_H, C.POINTER(PdlpBatch), _I, _I, _I, _P, _P]),
     "pdlp_batch_attach_matrices": (_I, [_H, _I, _P, _P, _P, _P]),
     "pdlp_batch_product": (_I, [_H, C.POINTER(PdlpBatch), _I, _P, _P]),
+    "pdlp_batch_iterate_from": (_I, [_H, C.POINTER(PdlpBatch), _I, _I, _I64, _P]),
+    "pdlp_batch_admit": (_I, [_H, C.POINTER(PdlpBatch), _I, _P, _P, C.POINTER(PdlpBatchFeed)]),
+    "pdlp_batch_retire": (_I, [_H, C.POINTER(PdlpBatch), _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I]),
     "pdlp_spmv": (_I, [_H, _I, _P, _P]),
     "pdlp_power_iteration": (_I, [_H, _P, _I, _P, _P, C.POINTER(_D)]),
     "pdlp_probe_stream_read": (_I, [_P, _I64, _I, _P, C.POINTER(_D)]),

@@ -212,7 +212,7 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
                    max_kkt: int = 100_000, time_limit: float = 3600, restart_period: int = 40, dtype=torch.float32,
                    seed: Optional[int] = None, compat: bool = True, x_init=None, y_init=None, trace=None, verbose: bool = False,
                    group_width: Optional[int] = None, b0=None, report: bool = True, K_values=None, setup_times: Optional[dict] = None,
-                   **unsupported) -> BatchResult:
+                   slots: Optional[int] = None, schedule: Optional[dict] = None, **unsupported) -> BatchResult:
     """Solve B LPs that share ``K`` (and ``m_ineq``) of ``problem`` and differ in ``c``, ``q``, ``l``, ``u`` in one batch.
 
     ``K_values`` ``(nnz, B)``: a constraint matrix per LP.  The LPs then share only the sparsity pattern of ``problem``'s K (its row
@@ -221,6 +221,14 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     of matrices whose patterns differ.  The step size and, with ``precondition``, the Ruiz equilibration are then per LP
     (``setup_times`` receives ``ruiz_seconds`` and ``power_iteration_seconds``).  Device memory: ``2 * nnz * Bp * itemsize`` on top
     of the shared copy.
+
+    ``slots`` < B streams the family through ``slots`` columns (a positive multiple of the group width): the LPs wait in index order,
+    and after every restart check the columns whose LP has finished are handed to the next ones.  The results are those of the plain
+    batch at the same ``group_width``, bit for bit, in input order; device memory is that of ``slots`` LPs (with ``K_values``:
+    ``2 * nnz * slots * itemsize``) plus the results, and the 2-D arguments (``K_values`` included) may stay on the host: they are
+    copied ``slots`` columns at a time.  ``time_limit`` is for the whole run: LPs still waiting when it expires come back with the
+    time-limit status, ``iterations == 0`` and their start point.  ``K_values`` with ``precondition`` has no streamed form.
+    ``schedule``: a dict that receives ``column``, ``admitted_at``, ``retired_at`` per LP.
 
     ``problem`` (an MPS path or ``(c, K, q, m_ineq, l, u)``) supplies K and the default vectors; each of ``c, q, l, u`` may be
     omitted, 1-D (shared) or 2-D ``(len, B)`` (one column per LP; the 2-D arguments must agree on B).  Every LP runs through the
@@ -231,7 +239,7 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     ``solve_lp`` that have no batched form (sharding, fishnet, infeasibility detection, ``adaptive_retry``, the direct exchange,
     ``precision="mixed"``) raise ``ValueError``."""
     import numpy as np
-    from .batch import batch_size, pdlp_algorithm_batch
+    from .batch import batch_size, check_slots, pdlp_algorithm_batch
     for name, v in unsupported.items():
         if name == "precision":
             if v is not None:
@@ -256,18 +264,23 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     if K_values is not None:
         K_values = torch.as_tensor(K_values)
         _check_matrix_values(K_values, problem[1].nnz if not from_file and isinstance(problem[1], CsrPair) else None)
-    _check_start_width(batch_size(*(torch.as_tensor(v) for v in (c, q, l, u, K_values) if v is not None)), x_init, y_init)
+    B_given = batch_size(*(torch.as_tensor(v) for v in (c, q, l, u, K_values) if v is not None))
+    _check_start_width(B_given, x_init, y_init)
+    streamed = check_slots(slots, B_given, group_width, dtype, K_values is not None, precondition)
     device = resolve_device(device)
     c0, K, q0, m_ineq, l0, u0 = load_problem(problem, device, dtype, verbose, compat)
     if from_file:
         check_lengths(K.n, K.m)
     _check_matrix_values(K_values, K.nnz)    # (a file or a dense / COO matrix says its pattern once it is CSR)
-    vec = lambda v, d: (torch.as_tensor(d).reshape(-1) if v is None else torch.as_tensor(v)).to(device=device, dtype=dtype)
+    # (a streamed family's 2-D arguments stay where they are: they are staged per admission)
+    stays = lambda v: streamed and v is not None and len(v.shape) == 2
+    vec = lambda v, d: (torch.as_tensor(v).to(dtype) if stays(v) else
+                        (torch.as_tensor(d).reshape(-1) if v is None else torch.as_tensor(v)).to(device=device, dtype=dtype))
     C_, Q, L, U = vec(c, c0), vec(q, q0), vec(l, l0), vec(u, u0)
     B = batch_size(C_, Q, L, U, K_values)
     time_used, data_precond, Ks, KsV, KsTV = 0.0, None, K, None, None
     if K_values is not None:
-        KsV = K_values.to(device=device, dtype=dtype)
+        KsV = K_values.to(dtype) if streamed else K_values.to(device=device, dtype=dtype)
     if precondition and K_values is not None:    # main.py:106-110 per LP: each matrix equilibrated on its own, each column scaled
         import time as _time
         from .precondition import ruiz_precondition_batch
@@ -285,7 +298,7 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
         Ks, _, _, _, _, data_precond, time_used = ruiz_precondition(ones_n, K, ones_m, ones_n, ones_n, device=device)
         t0 = _time.time()
         D_col, D_row = data_precond[0].to(dtype).view(-1, 1), data_precond[1].to(dtype).view(-1, 1)
-        sc = lambda v, D, op: (op(v.view(-1, 1), D).view(-1) if v.dim() == 1 else op(v, D))
+        sc = lambda v, D, op: (op(v.view(-1, 1), D).view(-1) if v.dim() == 1 else op(v, D.to(v.device)))
         C_, Q = sc(C_, D_col, torch.mul), sc(Q, D_row, torch.mul)
         L, U = sc(L, D_col, torch.div), sc(U, D_col, torch.div)
         time_used += _time.time() - t0
@@ -297,7 +310,7 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
         Ks, m_ineq, C_, Q, L, U, device, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period,
         precondition=precondition, primal_update=primal_weight_update, adaptive=adaptive_stepsize, data_precond=data_precond,
         time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init, seed=seed, traces=traces, group_width=group_width,
-        b0=b0, report=rep, K_values=KsV, KT_values=KsTV, setup_times=setup_times)
+        b0=b0, report=rep, K_values=KsV, KT_values=KsTV, setup_times=setup_times, slots=slots if streamed else None, schedule=schedule)
     if trace is not None:
         trace.extend(traces)
     if precondition:                         # x = D_col x_s, y = D_row y_s (pdhg.py:161-162), per LP with a matrix each

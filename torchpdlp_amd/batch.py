@@ -7,6 +7,9 @@ which is always taken at a check (pdhg.py:115-146), so every LP's checks fall on
 count ``k``: checking all live LPs together every ``restart_period`` iterations runs each through exactly the reference's control
 flow.  The step size, primal weight, restarts, KKT-pass count ``j`` and termination are per LP; a finished LP is frozen (its
 column is never written again).  The kernels: ``pdlp_batch_*`` (include/pdlp_hip.h).
+
+A family longer than the batch is wide is streamed (``slots``, ``_solve_stream``): a finished LP's column is retired and given to
+the next LP of the family at a check, which by the same argument runs the control flow -- and gets the bits -- of the plain batch.
 """
 from __future__ import annotations
 
@@ -19,8 +22,8 @@ import torch
 
 from . import _native as N
 from .engine import PdlpEngine
-from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, kkt_error, kkt_from_sums, np_type, primal_weight,
-                    restart_decision, start_eta, start_omega, terminated)
+from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, StreamQueue, kkt_error, kkt_from_sums, np_type,
+                    primal_weight, restart_decision, start_eta, start_omega, terminated)
 from .solver import estimate_sigma, precond_factors, resolve_device
 from .sparse import CsrPair
 
@@ -92,6 +95,7 @@ class BatchEngine:
                                 p(self.y), p(self.y_prev), p(self.y_sum), p(self.y_avg), p(self.y_last), p(self.dy),
                                 p(self.eta), p(self.omega), p(self.eta_sum), p(self.wpend), p(self.live), p(self.action),
                                 p(self.part), p(self.out))
+        self.k_start = None        # [Bp] int64 once the batch streams a family (enable_stream): the count at each column's admission
 
     def _col(self, v: torch.Tensor, ln: int) -> torch.Tensor:
         """a shared vector as it is, a per-LP one [len, B] padded to [len, Bp] (padding columns are dead)"""
@@ -139,7 +143,54 @@ class BatchEngine:
                 dst.copy_(torch.from_numpy(full).to(dst.dtype))
 
     def iterate(self, iters: int, adaptive: bool, k0: int):
+        if self.k_start is not None:
+            N.check(self.lib.pdlp_batch_iterate_from(self.eng.h, C.byref(self.desc), int(iters), int(adaptive), int(k0),
+                                                     self.k_start.data_ptr()), "pdlp_batch_iterate_from")
+            return
         N.check(self.lib.pdlp_batch_iterate(self.eng.h, C.byref(self.desc), int(iters), int(adaptive), int(k0)), "pdlp_batch_iterate")
+
+    def enable_stream(self):
+        """the state of a batch whose columns change hands (``admit`` / ``retire``): ``k_start``, and sums of its own for the
+        retirements (``retire_out`` [3][Bp][6]: the KKT passes of the next check must not overwrite what no host read has fetched)"""
+        self.k_start = torch.zeros(self.Bp, dtype=torch.int64, device=self.device)
+        self.retire_out = torch.zeros(3, self.Bp, 6, dtype=torch.float64, device=self.device)
+        self.retire_desc = N.PdlpBatch.from_buffer_copy(self.desc)
+        self.retire_desc.out = self.retire_out.data_ptr()
+
+    def _index(self, v) -> torch.Tensor:
+        return torch.from_numpy(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+
+    def admit(self, cols, ids, eta, omega, c=None, q=None, l=None, u=None, x0=None, y0=None, K_val=None, KT_val=None):
+        """``pdlp_batch_admit``: column ``cols[i]`` starts on column ``ids[i]`` of the feed -- ``[len, N]`` device tensors of the
+        working precision (None: the batch shares the vector / zeros / no matrices), ``eta`` and ``omega`` ``[N]`` host arrays"""
+        Nf = {int(v.shape[1]) for v in (c, q, l, u, x0, y0, K_val, KT_val) if v is not None} | {int(np.shape(eta)[0]), int(np.shape(omega)[0])}
+        if len(Nf) != 1:
+            raise ValueError(f"the arrays of a feed disagree on its width: {sorted(Nf)}")
+        for v in (c, q, l, u, x0, y0, K_val, KT_val):
+            if v is not None and (v.dtype != self.dtype or v.device != self.device or not v.is_contiguous()):
+                raise ValueError(f"a feed holds contiguous {self.dtype} tensors on {self.device}")
+        with torch.cuda.stream(self.stream):
+            sc = [torch.from_numpy(np.array(v)).to(device=self.device, dtype=self.dtype) for v in (eta, omega)]
+            ct, it = self._index(cols), self._index(ids)
+            p = lambda v: None if v is None else v.data_ptr()
+            feed = N.PdlpBatchFeed(Nf.pop(), p(c), p(q), p(l), p(u), p(x0), p(y0), p(K_val), p(KT_val), p(sc[0]), p(sc[1]))
+            N.check(self.lib.pdlp_batch_admit(self.eng.h, C.byref(self.desc), int(ct.numel()), ct.data_ptr(), it.data_ptr(), C.byref(feed)),
+                    "pdlp_batch_admit")
+
+    def retire(self, cols, ids, X_out, Y_out, rc_out=None, act_out=None, which: int = N.CUR, unscaled: bool = False, slot: int = 0):
+        """``pdlp_batch_retire``: the solution report of ``cols`` into column ``ids[i]`` of the ``[len, N]`` result tensors; the six
+        sums into ``retire_out[slot][cols[i]]`` (``out`` of a batch that does not stream).  No host read."""
+        Nr = int(X_out.shape[1])
+        for v, ln in ((X_out, self.n), (Y_out, self.m), (rc_out, self.n), (act_out, self.m)):
+            if v is not None and (tuple(v.shape) != (ln, Nr) or v.dtype != self.dtype or v.device != self.device or not v.is_contiguous()):
+                raise ValueError(f"a result array is a contiguous ({ln}, {Nr}) tensor of {self.dtype} on {self.device}")
+        desc = self.retire_desc if self.k_start is not None else self.desc
+        with torch.cuda.stream(self.stream):
+            ct, it = self._index(cols), self._index(ids)
+            p = lambda v: None if v is None else v.data_ptr()
+            N.check(self.lib.pdlp_batch_retire(self.eng.h, C.byref(desc), int(ct.numel()), ct.data_ptr(), it.data_ptr(), int(which),
+                                               int(bool(unscaled)), int(slot), p(X_out), p(Y_out), p(rc_out), p(act_out), Nr),
+                    "pdlp_batch_retire")
 
     def average(self, adaptive: bool):
         N.check(self.lib.pdlp_batch_average(self.eng.h, C.byref(self.desc), int(adaptive)), "pdlp_batch_average")
@@ -213,6 +264,7 @@ class BatchDriver:
         self.live = np.ones(B, bool)
         self.status = [STATUS_KKT_LIMIT] * B
         self.obj = np.full(B, np.nan)
+        self.lp = np.arange(B)               # column -> LP (the index into ``traces``); a streamed family changes it (occupy)
         self.k_global = 0
 
     def start(self, sigma, x_init=None, y_init=None):
@@ -220,6 +272,17 @@ class BatchDriver:
         self.omega = start_omega(self.q_norm, self.c_norm, t)                # pdhg.py:23
         eta = np.broadcast_to(np.asarray(start_eta(np.asarray(sigma, t), t), t), (self.be.B,))
         self.be.start(eta, self.omega, x_init, y_init)                       # pdhg.py:22 (sigma: one for the batch, or [B])
+
+    def occupy(self, cols, ids, q_norm, c_norm, omega):
+        """columns ``cols`` start on LPs ``ids`` (pdhg.py:19-23,45-54 for each): their counters, norms, primal weight and status"""
+        self.lp[cols] = ids
+        self.q_norm[cols], self.c_norm[cols], self.omega[cols] = q_norm, c_norm, omega
+        for a in (self.k, self.n, self.j, self.tt, self.kkt_first):
+            a[cols] = 0
+        self.obj[cols] = np.nan
+        self.live[cols] = True
+        for i in cols:
+            self.status[i] = STATUS_KKT_LIMIT
 
     def _finish(self, idx, status):
         for i in idx:
@@ -268,7 +331,7 @@ class BatchDriver:
         dec = restart_decision(r[0]["kkt"], r[1]["kkt"], r[2]["kkt"], self.kkt_first, self.tt, self.k, self.j, live, self.max_kkt, t)
         if self.traces is not None:
             for i in np.flatnonzero(live):
-                tr = self.traces[i]
+                tr = self.traces[self.lp[i]]
                 tr["kkt"] += [float(r[0]["kkt"][i]), float(r[1]["kkt"][i]), float(r[2]["kkt"][i])]
                 if dec["crit"][i] >= 0:
                     tr["restarts"].append((int(dec["crit"][i]), int(self.tt[i]), int(dec["use_avg"][i])))
@@ -294,7 +357,7 @@ class BatchDriver:
             be.set_scalars(omega=self.omega)
             if self.traces is not None:
                 for i in act:
-                    self.traces[i]["omega"].append(float(self.omega[i]))
+                    self.traces[self.lp[i]]["omega"].append(float(self.omega[i]))
         if capped.any():
             rc = kkt_from_sums(out[2], self.omega, t)
             chosen = rc if chosen is None else {key: np.where(capped, rc[key], chosen[key]) for key in rc}
@@ -303,7 +366,7 @@ class BatchDriver:
         self.j[act] += 2                                                     # pdhg.py:154,165
         if self.traces is not None:
             for i in act:
-                self.traces[i]["kkt"].append(float(kf[i]))
+                self.traces[self.lp[i]]["kkt"].append(float(kf[i]))
         res = kkt_from_sums(out[1], self.omega, t) if self.precondition else chosen
         self.obj[act] = res["p"][act].astype(np.float64)
         solved = terminated(res, self.q_norm, self.c_norm, self.tol, t)      # pdhg.py:173
@@ -332,10 +395,163 @@ def estimate_sigma_batch(be: BatchEngine, b0=None, power_iters=100, seed=None) -
     return be.power_iteration(b0.to(be.device), power_iters)
 
 
+def check_slots(slots, B: int, W, dtype, per_lp_matrices: bool, precondition: bool) -> bool:
+    """whether ``slots`` asks for a streamed solve of ``B`` LPs (None, or at least B: the plain batch); ValueError for a width the
+    launches cannot have or a combination that has no streamed form -- before any device work"""
+    if slots is None:
+        return False
+    if isinstance(slots, bool) or int(slots) != slots or slots < 1:
+        raise ValueError(f"slots must be a positive number of columns, got {slots!r}")
+    if slots >= B:
+        return False
+    W = int(W) if W is not None else group_width(int(slots), dtype)
+    if W not in (8, 16, 32) or slots % W != 0:
+        raise ValueError(f"slots must be a multiple of the group width {W} (8, 16 or 32: group_width), got {slots}")
+    if per_lp_matrices and precondition:
+        raise ValueError("K_values with precondition has no streamed form (a Ruiz equilibration per LP in chunks): solve it with "
+                         "slots=None, or equilibrate the matrices beforehand")
+    return True
+
+
+def _column_norms(v: torch.Tensor, B: int, t, device, chunk: int) -> np.ndarray:
+    """pdhg.py:19-20 per LP as the plain batch computes it (the float64 norm of every column, on the device); an array that stays on
+    the host goes there ``chunk`` columns at a time"""
+    v = v.reshape(v.shape[0], -1)
+    norm = lambda w: np.sqrt((w.double() ** 2).sum(0).cpu().numpy())
+    if v.device == device or v.shape[1] == 1:
+        return np.broadcast_to(norm(v), (B,)).astype(t)
+    return np.concatenate([norm(v[:, a:a + chunk].to(device)) for a in range(0, B, chunk)]).astype(t)
+
+
+def _solve_stream(Kp, m_ineq, C_, Q, L, U, B, slots, d_col, d_row, t0, *, max_kkt, tol, verbose, restart_period, precondition,
+                  primal_update, adaptive, time_limit, time_used, x_init, y_init, b0, sigma, seed, traces, W, report, K_values,
+                  setup_times, schedule):
+    """``pdlp_algorithm_batch`` for a family longer than the batch is wide: ``slots`` columns, the LPs queued in index order.
+
+    After every restart check of the batch (``k_global`` a multiple of the period) the columns whose LP has finished are retired
+    (``pdlp_batch_retire``: iterate and report into the LP's column of the results) and given to the next LPs
+    (``pdlp_batch_admit``).  ``StreamQueue`` (rules.py) says why an admitted LP runs the control flow of a batch that started with
+    it; the adaptive rule counts from its admission (``k_start``), and no kernel makes an LP's bits depend on its column: the
+    results are those of the plain batch at the same W.  Per check still one host read; the sums of the retirements are fetched
+    once, at the end.  Device memory: the state of ``slots`` LPs, the ``(n + m, B)`` results, and one admission's columns."""
+    dev, dt, t = Kp.val.device, Kp.val.dtype, np_type(Kp.dtype)
+    W = int(W) if W is not None else group_width(slots, dt)
+    per_lp = [v.dim() == 2 and v.shape[1] > 1 for v in (C_, Q, L, U)]
+    head = lambda v, per: (v[:, :slots] if per else v.reshape(-1)).to(device=dev, dtype=dt)
+    be = BatchEngine(Kp, m_ineq, *(head(v, per) for v, per in zip((C_, Q, L, U), per_lp)), slots, d_col=d_col, d_row=d_row, W=W,
+                     K_values=None if K_values is None else K_values[:, :slots])
+    be.enable_stream()
+    perm = Kp.transpose_perm() if K_values is not None else None
+    qn, cn = _column_norms(Q, B, t, dev, slots), _column_norms(C_, B, t, dev, slots)
+    if sigma is None:                                                        # pdhg.py:22 (once for a shared K; per LP, in chunks)
+        ts = time.time()
+        if K_values is None:
+            sigma = estimate_sigma(be.eng, b0, 100, seed)
+        else:
+            if b0 is None:
+                g = torch.Generator().manual_seed(int(seed) if seed is not None else int(time.time_ns() % (2 ** 31)))
+                b0 = torch.randn(be.n, generator=g, dtype=torch.float32)
+            parts = []
+            for a in range(0, B, slots):
+                cnt = min(slots, B - a)
+                with torch.cuda.stream(be.stream):
+                    be.K_valB[:, :cnt] = K_values[:, a:a + cnt].to(device=dev, dtype=dt)
+                    be.KT_valB.copy_(be.K_valB[perm])
+                parts.append(estimate_sigma_batch(be, b0, 100)[:cnt])
+            sigma = np.concatenate(parts)
+        if setup_times is not None:
+            setup_times["power_iteration_seconds"] = time.time() - ts
+    eta0 = np.broadcast_to(np.asarray(start_eta(np.asarray(sigma, t), t), t), (B,))      # pdhg.py:22
+    omega0 = np.broadcast_to(start_omega(qn, cn, t), (B,))                                # pdhg.py:23
+    drv = BatchDriver(be, qn[:slots].copy(), cn[:slots].copy(), restart_period, primal_update=primal_update, adaptive=adaptive,
+                      precondition=precondition, tol=tol, max_kkt=max_kkt, traces=traces)
+    drv.live[:] = False
+    queue = StreamQueue(B, slots, restart_period)
+    X = torch.zeros(be.n, B, dtype=dt, device=dev)
+    Y = torch.zeros(be.m, B, dtype=dt, device=dev)
+    rc = act = None
+    if report is not None:
+        rc, act = torch.zeros(be.n, B, dtype=dt, device=dev), torch.zeros(be.m, B, dtype=dt, device=dev)
+    sums = torch.zeros(B, 6, dtype=torch.float64, device=dev)
+    res = dict(k=np.zeros(B, np.int64), n=np.zeros(B, np.int64), j=np.zeros(B, np.int64), obj=np.full(B, np.nan),
+               omega=np.array(omega0, t), status=[STATUS_TIME_LIMIT] * B)
+
+    def stage(v, a, b, shared_ok=True):
+        """columns [a, b) of a source array as a feed array: [len, b - a] on the device (None: shared by the batch / zeros)"""
+        if v is None or (shared_ok and (v.dim() == 1 or v.shape[1] == 1)):
+            return None
+        if v.dim() == 1 or v.shape[1] == 1:                                  # one start point for every LP
+            return v.reshape(-1, 1).to(device=dev, dtype=dt).expand(-1, b - a).contiguous()
+        return v[:, a:b].to(device=dev, dtype=dt).contiguous()
+
+    def admit():
+        cols, ids = queue.admit(drv.k_global)
+        if not cols.size:
+            return
+        a, b = int(ids[0]), int(ids[-1]) + 1                                 # (the queue hands the LPs out in index order)
+        with torch.cuda.stream(be.stream):
+            Kv = stage(K_values, a, b, shared_ok=False)
+            be.admit(cols, np.arange(b - a), eta0[a:b], omega0[a:b], stage(C_, a, b), stage(Q, a, b), stage(L, a, b), stage(U, a, b),
+                     stage(x_init, a, b, shared_ok=False), stage(y_init, a, b, shared_ok=False), Kv, None if Kv is None else Kv[perm])
+        drv.occupy(cols, ids, qn[a:b], cn[a:b], omega0[a:b])
+        ks = np.zeros(slots, np.int64)
+        ks[queue.occupied()] = queue.admitted_at[queue.lp[queue.occupied()]]
+        be.set_scalars(k_start=ks, live=drv.live.astype(np.int32))
+
+    def retire(cols):
+        if not cols.size:
+            return
+        ids = queue.retire(cols, drv.k_global)
+        be.retire(cols, ids, X, Y, rc, act, N.CUR, unscaled=bool(precondition))
+        with torch.cuda.stream(be.stream):
+            sums[torch.from_numpy(ids).to(dev)] = be.retire_out[0][torch.from_numpy(cols).to(dev)]
+        for key, arr in (("k", drv.k), ("n", drv.n), ("j", drv.j), ("obj", drv.obj), ("omega", drv.omega)):
+            res[key][ids] = arr[cols]
+        for c_, i in zip(cols, ids):
+            res["status"][i] = drv.status[c_]
+
+    admit()
+    in_time = True
+    while queue.occupied().size:
+        if drv.live.any():
+            in_time = time.time() - t0 + time_used < time_limit
+            drv.step(in_time)
+        if not drv.live.any():               # nothing runs: the clock of the batch may move to its next check
+            drv.k_global = queue.next_boundary(drv.k_global)
+        if queue.may_admit(drv.k_global):
+            occ = queue.occupied()
+            retire(occ[~drv.live[occ]])
+            if in_time:
+                admit()
+        if verbose:
+            print(f"[batch] k={drv.k_global} live={int(drv.live.sum())}/{slots} waiting={queue.waiting()}")
+    late = queue.never_admitted()            # the clock ran out before their turn: k = 0, the start point, its report
+    sched = queue.schedule()
+    while queue.waiting():
+        cols, ids = queue.admit(queue.next_boundary(drv.k_global))
+        a, b = int(ids[0]), int(ids[-1]) + 1
+        with torch.cuda.stream(be.stream):
+            Kv = stage(K_values, a, b, shared_ok=False)
+            be.admit(cols, np.arange(b - a), eta0[a:b], omega0[a:b], stage(C_, a, b), stage(Q, a, b), stage(L, a, b), stage(U, a, b),
+                     stage(x_init, a, b, shared_ok=False), stage(y_init, a, b, shared_ok=False), Kv, None if Kv is None else Kv[perm])
+        queue.retire(cols, drv.k_global)
+        be.retire(cols, ids, X, Y, rc, act, N.CUR, unscaled=bool(precondition))
+        with torch.cuda.stream(be.stream):
+            sums[torch.from_numpy(ids).to(dev)] = be.retire_out[0][torch.from_numpy(cols).to(dev)]
+    if schedule is not None:
+        schedule.update(sched, slots=slots, group_width=W, never_admitted=late)
+    if report is not None:
+        Yr = Y * be.d_row if precondition else Y.clone()
+        report.update(y=Yr, reduced_costs=rc, row_activity=act, q_norm=qn, c_norm=cn,
+                      **kkt_from_sums(sums.cpu().numpy(), res["omega"], t))
+    be.synchronize()
+    return X, Y, res["obj"], res["k"], res["n"], res["j"], res["status"], time.time() - t0 + time_used
+
+
 def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, tol=1e-4, verbose=False, restart_period=40,
                          precondition=False, primal_update=False, adaptive=False, data_precond=None, time_limit=3600, time_used=0,
                          x_init=None, y_init=None, *, b0=None, sigma=None, seed=None, traces=None, group_width=None,
-                         report=None, K_values=None, KT_values=None, setup_times=None):
+                         report=None, K_values=None, KT_values=None, setup_times=None, slots=None, schedule=None):
     """``pdlp_algorithm`` on B LPs with the same ``K`` at once.  ``C_``, ``Q``, ``L``, ``U``: 1-D (shared) or [len, B] (one column
     per LP), of the scaled problem when ``precondition`` (then ``data_precond`` = ``ruiz_precondition``'s: ``D_col``, ``D_row``
     give the un-scaled residuals).  ``traces``: a list of B dicts (``kkt``, ``omega``, ``restarts``) that receive every LP's trace.
@@ -348,17 +564,28 @@ def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, t
     ``(D_col (n, B), D_row (m, B))``, every LP's own Ruiz factors (``ruiz_precondition_batch``), the step size comes from a power
     iteration per LP, and ``sigma`` may be one number or a [B] array.  ``setup_times``: a dict that receives
     ``power_iteration_seconds`` when sigma is estimated here.
+    ``slots`` < B: the family is streamed through ``slots`` columns (``_solve_stream``: the same results, bit for bit, from the
+    memory of ``slots`` LPs); ``c, q, l, u, x_init, y_init, K_values`` may then stay on the host.  ``schedule``: a dict that receives
+    ``column``, ``admitted_at``, ``retired_at`` ([B]) of such a run.
     Returns ``(X, Y, obj, k, n, j, status, total_time)`` with X [n, B], Y [m, B] (the scaled iterates when preconditioned, like
     ``pdlp_algorithm``'s x) and numpy arrays / a list of status strings per LP."""
     t0 = time.time()
-    Kp = CsrPair.from_any(K, device=resolve_device(device))
     B = batch_size(C_, Q, L, U, K_values)
+    streamed = check_slots(slots, B, group_width, K.val.dtype if isinstance(K, CsrPair) else C_.dtype, K_values is not None, precondition)
+    Kp = CsrPair.from_any(K, device=resolve_device(device))
     if K_values is not None and tuple(K_values.shape) != (Kp.nnz, B):
         raise ValueError(f"K_values must have shape ({Kp.nnz}, {B}), got {tuple(K_values.shape)}")
     for name, v, ln in (("x_init", x_init, Kp.n), ("y_init", y_init, Kp.m)):
         if v is not None and (v.dim() not in (1, 2) or v.shape[0] != ln or (v.dim() == 2 and v.shape[1] != B)):
             raise ValueError(f"{name} must have shape ({ln},) or ({ln}, {B}), got {tuple(v.shape)}")
     d_col, d_row = precond_factors(precondition, data_precond)
+    if streamed:
+        if KT_values is not None:
+            raise ValueError("a streamed family takes K_values only (the values of K' are permuted per admission)")
+        return _solve_stream(Kp, m_ineq, C_, Q, L, U, B, int(slots), d_col, d_row, t0, max_kkt=max_kkt, tol=tol, verbose=verbose,
+                             restart_period=restart_period, precondition=precondition, primal_update=primal_update, adaptive=adaptive,
+                             time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init, b0=b0, sigma=sigma, seed=seed,
+                             traces=traces, W=group_width, report=report, K_values=K_values, setup_times=setup_times, schedule=schedule)
     be = BatchEngine(Kp, m_ineq, C_, Q, L, U, B, d_col=d_col, d_row=d_row, W=group_width, K_values=K_values, KT_values=KT_values)
     t = np_type(Kp.dtype)
     # pdhg.py:19-20 per LP (as solver._global_norm: the float64 norm, rounded to the working precision)

@@ -82,7 +82,7 @@ int batch_finalize(pdlp_handle h, const pdlp_batch* b, const double* partials, i
         if (rc_ != PDLP_OK) return rc_;          \
     } while (0)
 
-template <typename T, int W> int batch_iterate_w(pdlp_handle h, const pdlp_batch* b, int iters, bool adaptive, int64_t k0)
+template <typename T, int W> int batch_iterate_w(pdlp_handle h, const pdlp_batch* b, int iters, bool adaptive, int64_t k0, const int64_t* k_start)
 {
     const int ineq_end = (int)h->p.m_ineq;
     T *eta = (T*)b->eta, *omega = (T*)b->omega, *eta_sum = (T*)b->eta_sum, *wpend = (T*)b->wpend;
@@ -96,7 +96,7 @@ template <typename T, int W> int batch_iterate_w(pdlp_handle h, const pdlp_batch
             BDen<T> en{(const T*)b->x, (const T*)b->x_prev};
             BATCH_TRY((batch_mv<T, W>(h, b, true, (const T*)b->dy, en, batch_part2(b))));
             hipLaunchKernelGGL(k_batch_adapt<T>, dim3(b->Bp), dim3(BLOCK), 0, h->stream, b->Bp, b->live, b->part,
-                               batch_grid(h->p.m, W), batch_part2(b), batch_grid(h->p.n, W), eta, omega, eta_sum, wpend, k0 + it + 1);
+                               batch_grid(h->p.m, W), batch_part2(b), batch_grid(h->p.n, W), eta, omega, eta_sum, wpend, k0 + it + 1, k_start);
             HIP_TRY(hipGetLastError());
         } else {
             BPrimal<T, false> ep{(T*)b->x, (T*)b->x_prev, (T*)b->xbar, (T*)b->x_sum, (const T*)b->c, (const T*)b->l, (const T*)b->u,
@@ -113,11 +113,11 @@ template <typename T, int W> int batch_iterate_w(pdlp_handle h, const pdlp_batch
     return PDLP_OK;
 }
 
-template <typename T> int batch_iterate_t(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0)
+template <typename T> int batch_iterate_t(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0, const int64_t* k_start)
 {
-    if (b->W == 8) return batch_iterate_w<T, 8>(h, b, iters, adaptive != 0, k0);
-    if (b->W == 16) return batch_iterate_w<T, 16>(h, b, iters, adaptive != 0, k0);
-    return batch_iterate_w<T, 32>(h, b, iters, adaptive != 0, k0);
+    if (b->W == 8) return batch_iterate_w<T, 8>(h, b, iters, adaptive != 0, k0, k_start);
+    if (b->W == 16) return batch_iterate_w<T, 16>(h, b, iters, adaptive != 0, k0, k_start);
+    return batch_iterate_w<T, 32>(h, b, iters, adaptive != 0, k0, k_start);
 }
 
 template <typename T> int batch_average_t(pdlp_handle h, const pdlp_batch* b, int adaptive)
@@ -193,6 +193,82 @@ template <typename T> int batch_report_t(pdlp_handle h, const pdlp_batch* b, int
     return batch_report_w<T, 32, false>(h, b, which, slot, rc, act);
 }
 
+// admission: one launch per side -- the n rows (c, l, u, x and the LP's scalars), the m rows (q, y), the nnz items (both value
+// populations, when matrices are attached)
+template <typename T> int batch_admit_t(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids,
+                                        const pdlp_batch_feed* f)
+{
+    const int64_t n = h->p.n, m = h->p.m;
+    T* const none = nullptr;
+    hipLaunchKernelGGL(k_batch_admit<T>, dim3(grid_for(n * count)), dim3(BLOCK), 0, h->stream, n, count, cols, ids, b->Bp, f->N,
+                       f->c ? (T*)b->c : none, (const T*)f->c, f->l ? (T*)b->l : none, (const T*)f->l, f->u ? (T*)b->u : none,
+                       (const T*)f->u, (T*)b->x, (T*)b->x_last, (T*)b->x_sum, (const T*)f->x0, (T*)b->eta, (T*)b->omega, (T*)b->eta_sum,
+                       (T*)b->wpend, (const T*)f->eta, (const T*)f->omega);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_batch_admit<T>, dim3(grid_for(m * count)), dim3(BLOCK), 0, h->stream, m, count, cols, ids, b->Bp, f->N,
+                       f->q ? (T*)b->q : none, (const T*)f->q, none, (const T*)nullptr, none, (const T*)nullptr, (T*)b->y, (T*)b->y_last,
+                       (T*)b->y_sum, (const T*)f->y0, none, none, none, none, (const T*)nullptr, (const T*)nullptr);
+    HIP_TRY(hipGetLastError());
+    if (f->K_val) {
+        const int64_t nnz = h->nnz;
+        hipLaunchKernelGGL(k_batch_admit<T>, dim3(grid_for(nnz * count)), dim3(BLOCK), 0, h->stream, nnz, count, cols, ids, b->Bp, f->N,
+                           (T*)h->bm.K_val, (const T*)f->K_val, (T*)h->bm.KT_val, (const T*)f->KT_val, none, (const T*)nullptr, none, none,
+                           none, (const T*)nullptr, none, none, none, none, (const T*)nullptr, (const T*)nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    return PDLP_OK;
+}
+
+// retirement: the report of the listed columns, stored into the caller's [len][N] arrays; the sums through the report's tree
+template <typename T, int W, bool U>
+int batch_retire_w(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids, int which, int slot,
+                   void* Xo, void* Yo, void* rc, void* act, int N)
+{
+    const T* X = (const T*)(which == PDLP_CUR ? b->x : which == PDLP_AVG ? b->x_avg : b->x_prev);
+    const T* Y = (const T*)(which == PDLP_CUR ? b->y : which == PDLP_AVG ? b->y_avg : b->y_prev);
+    const pdlp_problem& p = h->p;
+    double* out = b->out + (size_t)slot * b->Bp * 6;
+    const bool per = h->bm.K_val != nullptr;
+    for (int side = 0; side < 2; ++side) {      // 0: rows of K' (x, lam, four sums), 1: rows of K (y, K x, two sums)
+        const int rows = (int)(side == 0 ? p.n : p.m);
+        const int64_t* rp = side == 0 ? p.KT_rowptr : p.K_rowptr;
+        const int32_t* ci = side == 0 ? p.KT_colidx : p.K_colidx;
+        const T* va = (const T*)(per ? (side == 0 ? h->bm.KT_val : h->bm.K_val) : (side == 0 ? p.KT_val : p.K_val));
+        const dim3 grid(batch_grid(rows, W), b->Bp / W);
+        double* part = side == 0 ? b->part : batch_part2(b);
+        if (side == 0) {
+            BRetireDual<T, U> e{{X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp,
+                                 (const T*)batch_dcol(h), batch_dper(h)}, (T*)Xo, (T*)rc, N, -1};
+            if (per) hipLaunchKernelGGL((k_batch_mv_cols<T, W, true, BRetireDual<T, U>>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Y, b->Bp, count, cols, ids, N, e, part);
+            else hipLaunchKernelGGL((k_batch_mv_cols<T, W, false, BRetireDual<T, U>>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Y, b->Bp, count, cols, ids, N, e, part);
+        } else {
+            BRetirePrimal<T, U> e{{Y, (const T*)b->q, b->q_per_lp, (const T*)batch_drow(h), batch_dper(h), (int)p.m_ineq}, (T*)Yo, (T*)act, N, -1};
+            if (per) hipLaunchKernelGGL((k_batch_mv_cols<T, W, true, BRetirePrimal<T, U>>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, X, b->Bp, count, cols, ids, N, e, part);
+            else hipLaunchKernelGGL((k_batch_mv_cols<T, W, false, BRetirePrimal<T, U>>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, X, b->Bp, count, cols, ids, N, e, part);
+        }
+        HIP_TRY(hipGetLastError());
+        const int na = side == 0 ? 4 : 2;
+        hipLaunchKernelGGL(k_batch_finalize_cols, dim3(count * na), dim3(BLOCK), 0, h->stream, (const double*)part, batch_grid(rows, W), b->Bp,
+                           na, cols, out, 6, side == 0 ? 0 : 4);
+        HIP_TRY(hipGetLastError());
+    }
+    return PDLP_OK;
+}
+
+template <typename T>
+int batch_retire_t(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids, int which, int unscaled,
+                   int slot, void* Xo, void* Yo, void* rc, void* act, int N)
+{
+    if (unscaled) {
+        if (b->W == 8) return batch_retire_w<T, 8, true>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
+        if (b->W == 16) return batch_retire_w<T, 16, true>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
+        return batch_retire_w<T, 32, true>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
+    }
+    if (b->W == 8) return batch_retire_w<T, 8, false>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
+    if (b->W == 16) return batch_retire_w<T, 16, false>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
+    return batch_retire_w<T, 32, false>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
+}
+
 template <typename T> int batch_product_t(pdlp_handle h, const pdlp_batch* b, int transpose, const void* Vin, void* Vout)
 {
     BStore<T> es{(T*)Vout};
@@ -225,13 +301,44 @@ template <typename T> int batch_restart_t(pdlp_handle h, const pdlp_batch* b, in
 
 }  // namespace
 
-int pdlp_batch_iterate(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0)
+int pdlp_batch_iterate_from(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0, const int64_t* k_start)
 {
     if (iters < 0 || k0 < 0) return PDLP_ERR_INVALID;
     const int rc = batch_check(h, b);
     if (rc != PDLP_OK) return rc;
     Range range("pdlp: batch iterations", h->stream);
-    return DISPATCH(h, batch_iterate_t, h, b, iters, adaptive, k0);
+    return DISPATCH(h, batch_iterate_t, h, b, iters, adaptive, k0, k_start);
+}
+
+int pdlp_batch_iterate(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0)
+{
+    return pdlp_batch_iterate_from(h, b, iters, adaptive, k0, nullptr);
+}
+
+int pdlp_batch_admit(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids, const pdlp_batch_feed* f)
+{
+    const int rc = batch_check(h, b);
+    if (rc != PDLP_OK) return rc;
+    if (!f || !cols || !ids || count < 1 || count > b->Bp || f->N < 1 || !f->eta || !f->omega) return PDLP_ERR_INVALID;
+    // a vector is fed exactly where the batch holds a column of it per LP, the values exactly where matrices are attached
+    if ((f->c != nullptr) != (b->c_per_lp != 0) || (f->q != nullptr) != (b->q_per_lp != 0) || (f->l != nullptr) != (b->l_per_lp != 0) ||
+        (f->u != nullptr) != (b->u_per_lp != 0))
+        return PDLP_ERR_INVALID;
+    if ((f->K_val != nullptr) != (f->KT_val != nullptr) || (f->K_val != nullptr) != (h->bm.K_val != nullptr)) return PDLP_ERR_INVALID;
+    Range range("pdlp: batch admission", h->stream);
+    return DISPATCH(h, batch_admit_t, h, b, count, cols, ids, f);
+}
+
+int pdlp_batch_retire(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids, int which, int unscaled,
+                      int slot, void* X_out, void* Y_out, void* rc_out, void* act_out, int N)
+{
+    if ((which != PDLP_CUR && which != PDLP_AVG && which != PDLP_PREV) || slot < 0 || slot > 2) return PDLP_ERR_INVALID;
+    const int r = batch_check(h, b);
+    if (r != PDLP_OK) return r;
+    if (!cols || !ids || count < 1 || count > b->Bp || !X_out || !Y_out || N < 1) return PDLP_ERR_INVALID;
+    if (unscaled && (!batch_dcol(h) || !batch_drow(h))) return PDLP_ERR_STATE;
+    Range range("pdlp: batch retirement", h->stream);
+    return DISPATCH(h, batch_retire_t, h, b, count, cols, ids, which, unscaled, slot, X_out, Y_out, rc_out, act_out, N);
 }
 
 int pdlp_batch_average(pdlp_handle h, const pdlp_batch* b, int adaptive)

@@ -157,6 +157,7 @@ struct pdlp_solver {
     // batched solves with a matrix per LP (optional, attached by the caller: pdlp_batch_attach_matrices): the values of K and K'
     // as populations [nnz][Bp] over the handle's pattern, the Ruiz factors as [n][Bp] / [m][Bp]; used by every pdlp_batch_* call
     struct BatchMatrices { int Bp = 0; const void *K_val = nullptr, *KT_val = nullptr, *d_col = nullptr, *d_row = nullptr; } bm;
+    int64_t nnz = 0;           // stored entries of K (the rows of a value population: pdlp_batch_admit)
 };
 
 namespace {

@@ -220,6 +220,7 @@ int pdlp_create(pdlp_handle* out, const pdlp_problem* p, void* workspace, int64_
     h->mixed = p->dtype == PDLP_MIXED;
     h->nl = nl;
     h->ml = ml;
+    h->nnz = rpK[ml];
     int64_t ie = p->m_ineq - p->row0;
     h->ineq_end = (int)(ie < 0 ? 0 : (ie > ml ? ml : ie));
     bind_layout(h, (char*)workspace, L);

@@ -163,26 +163,28 @@ template <typename T, bool UNSCALE> struct BKktPrimal {
 
 // Solution report per column (pdlp_batch_report): the KKT sums of BKktDual / BKktPrimal with the reduced cost lam resp. the row
 // activity K x stored beside them (null: not stored) -- UNSCALE: lam_u = lam_s / D_col, act_u = (K_s x_s) / D_row
+// lam = project_lambda_box(c - K'y) of row j (helpers.py:3-39), un-scaled on request: what the report stores
+template <typename T, bool UNSCALE>
+__device__ __forceinline__ T batch_lam(const BKktDual<T, UNSCALE>& kkt, int j, size_t at, T kty)
+{
+    T lo = BCOL(kkt.l, kkt.ls, j, at), hi = BCOL(kkt.u, kkt.us, j, at);
+    T g = BCOL(kkt.c, kkt.cs, j, at) - kty;
+    if (UNSCALE) {
+        const T d = BCOL(kkt.dcol, kkt.dper, j, at);
+        g = g / d; lo = lo * d; hi = hi * d;
+    }
+    const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
+    if (ninf && pinf) return (T)0;
+    if (ninf) return g < (T)0 ? g : (T)0;
+    if (pinf) return g > (T)0 ? g : (T)0;
+    return g;
+}
 template <typename T, bool UNSCALE> struct BReportDual {
     static constexpr int NA = 4;
     BKktDual<T, UNSCALE> kkt; T* RC;
     __device__ void operator()(int j, size_t at, int b, T kty, double* acc) const
     {
-        if (RC) {
-            T lo = BCOL(kkt.l, kkt.ls, j, at), hi = BCOL(kkt.u, kkt.us, j, at);
-            T g = BCOL(kkt.c, kkt.cs, j, at) - kty;
-            if (UNSCALE) {
-                const T d = BCOL(kkt.dcol, kkt.dper, j, at);
-                g = g / d; lo = lo * d; hi = hi * d;
-            }
-            const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
-            T lam;
-            if (ninf && pinf) lam = (T)0;
-            else if (ninf) lam = g < (T)0 ? g : (T)0;
-            else if (pinf) lam = g > (T)0 ? g : (T)0;
-            else lam = g;
-            RC[at] = lam;
-        }
+        if (RC) RC[at] = batch_lam<T, UNSCALE>(kkt, j, at, kty);
         kkt(j, at, b, kty, acc);
     }
 };
@@ -280,14 +282,17 @@ __global__ __launch_bounds__(BLOCK) void k_batch_finalize(const double* __restri
 
 // adaptive_one_step_pdhg's step-size rule per LP (step.py:92-115, one trial: quirk Q1), then the bookkeeping of pdhg.py:107-112:
 // the step just taken gets weight eta_w (added to the sums by the next iteration, wpend), eta_sum += eta_w, eta = eta'.
-// One workgroup per LP: it reduces the LP's three partial sums, thread 0 applies the rule.
+// One workgroup per LP: it reduces the LP's three partial sums, thread 0 applies the rule.  k_global + 1 is the iteration count
+// of the batch after this step; an LP admitted later (k_start[b] > 0, pdlp_batch_iterate_from) counts from its admission.
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_batch_adapt(int Bp, const int32_t* __restrict__ live, const double* __restrict__ part_dy,
                                                        int gm, const double* __restrict__ part_den, int gn, T* eta,
-                                                       const T* __restrict__ omega, T* eta_sum, T* wpend, int64_t k)
+                                                       const T* __restrict__ omega, T* eta_sum, T* wpend, int64_t k_global,
+                                                       const int64_t* __restrict__ k_start)
 {
     const int b = blockIdx.x;
     if (!live[b]) return;                       // (uniform over the workgroup)
+    const int64_t k = k_start ? k_global - k_start[b] : k_global;      // the LP's own count: it entered its column at k_start[b]
     const double dyy = batch_block_sum(part_dy, gm, Bp, 1, b, 0);
     const double dkd = batch_block_sum(part_den, gn, Bp, 2, b, 0);
     const double dxx = batch_block_sum(part_den, gn, Bp, 2, b, 1);
@@ -382,5 +387,107 @@ __global__ __launch_bounds__(BLOCK) void k_batch_restart(int rows, int Bp, const
         }
     }
     batch_store_partials<W, 1>(acc, partials, Bp);
+}
+// ---- streaming a family through the columns (pdlp_batch_admit, pdlp_batch_retire) ----------------------------------------------
+// Both take a list: column cols[i] of the batch and column ids[i] of a [len][N] array of the caller (the feed, the results).
+// An entry with a column outside [0, Bp) or an id outside [0, N) is skipped.
+
+// admission, one side (the n rows, the m rows or the nnz items): element (row, i), i fastest, so columns listed next to each other
+// are stored next to each other.  d0..d2 <- s0..s2: the per-LP vectors (or value populations) of this side, null = none;
+// V = Vlast = V0 (null: zeros), Vsum = 0 when the side has an iterate; with eta given (the n rows) the LP's scalars as well.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_batch_admit(int64_t rows, int count, const int32_t* __restrict__ cols,
+                                                       const int32_t* __restrict__ ids, int Bp, int N, T* d0, const T* __restrict__ s0,
+                                                       T* d1, const T* __restrict__ s1, T* d2, const T* __restrict__ s2, T* V, T* Vlast,
+                                                       T* Vsum, const T* __restrict__ V0, T* eta, T* omega, T* eta_sum, T* wpend,
+                                                       const T* __restrict__ feta, const T* __restrict__ fomega)
+{
+    const int64_t total = rows * count;
+    for (int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x; e < total; e += (int64_t)gridDim.x * BLOCK) {
+        const int64_t r = e / count;
+        const int i = (int)(e - r * count);
+        const int col = cols[i], id = ids[i];
+        if (col < 0 || col >= Bp || id < 0 || id >= N) continue;
+        const size_t at = (size_t)r * Bp + col, from = (size_t)r * N + id;
+        if (d0) d0[at] = s0[from];
+        if (d1) d1[at] = s1[from];
+        if (d2) d2[at] = s2[from];
+        if (V) {
+            const T v = V0 ? V0[from] : (T)0;
+            V[at] = v;
+            Vlast[at] = v;
+            Vsum[at] = (T)0;
+        }
+        if (eta && r == 0) {
+            eta[col] = feta[id];
+            omega[col] = fomega[id];
+            eta_sum[col] = (T)0;
+            wpend[col] = (T)0;
+        }
+    }
+}
+
+// retirement: the report's epilogues with their stores redirected to column `id` of the result arrays ([len][N]); the iterate of
+// the side (x with K'y, y with K x) goes there as well.  The sums are BKktDual's / BKktPrimal's: the report's numbers.
+template <typename T, bool UNSCALE> struct BRetireDual {
+    static constexpr int NA = 4;
+    BKktDual<T, UNSCALE> kkt; T* Xout; T* RCout; int N; int id;
+    __device__ void operator()(int j, size_t at, int b, T kty, double* acc) const
+    {
+        const size_t to = (size_t)j * N + id;
+        Xout[to] = kkt.X[at];
+        if (RCout) RCout[to] = batch_lam<T, UNSCALE>(kkt, j, at, kty);
+        kkt(j, at, b, kty, acc);
+    }
+};
+template <typename T, bool UNSCALE> struct BRetirePrimal {
+    static constexpr int NA = 2;
+    BKktPrimal<T, UNSCALE> kkt; T* Yout; T* ACTout; int N; int id;
+    __device__ void operator()(int i, size_t at, int b, T kx, double* acc) const
+    {
+        const size_t to = (size_t)i * N + id;
+        Yout[to] = kkt.Y[at];
+        if (ACTout) ACTout[to] = UNSCALE ? kx / BCOL(kkt.drow, kkt.dper, i, at) : kx;
+        kkt(i, at, b, kx, acc);
+    }
+};
+
+// the row walk of k_batch_mv_all for the listed columns only; a group without a listed column leaves at once (its partials are
+// never read: k_batch_finalize_cols sums the listed columns)
+template <typename T, int W, bool PERLP, class Epi>
+__global__ __launch_bounds__(BLOCK) void k_batch_mv_cols(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                         const T* __restrict__ va, const T* __restrict__ Vin, int Bp, int count,
+                                                         const int32_t* __restrict__ cols, const int32_t* __restrict__ ids, int N,
+                                                         Epi epi, double* __restrict__ partials)
+{
+    const int b = blockIdx.y * W + (threadIdx.x & 63) % W;
+    int id = -1;
+    bool any = false;
+    for (int i = 0; i < count; ++i) {
+        const int c = cols[i], v = ids[i];
+        if (c < 0 || c >= Bp || v < 0 || v >= N) continue;
+        any = any || c / W == (int)blockIdx.y;
+        if (c == b) id = v;
+    }
+    if (!any) return;                           // (uniform over the workgroup)
+    double acc[Epi::NA > 0 ? Epi::NA : 1] = {0.0};
+    if (id >= 0) {
+        Epi e = epi;
+        e.id = id;
+        batch_rows<T, W, PERLP>(rows, rp, ci, va, Vin, Bp, b, e, acc);
+    }
+    if (Epi::NA > 0) batch_store_partials<W, Epi::NA>(acc, partials, Bp);
+}
+
+// k_batch_finalize for the listed columns: one workgroup per (i, a), the same tree, into out[cols[i]]
+__global__ __launch_bounds__(BLOCK) void k_batch_finalize_cols(const double* __restrict__ partials, int nblocks, int Bp, int na,
+                                                               const int32_t* __restrict__ cols, double* __restrict__ out, int stride,
+                                                               int off)
+{
+    const int i = blockIdx.x / na, a = blockIdx.x - i * na;
+    const int b = cols[i];
+    if (b < 0 || b >= Bp) return;               // (uniform over the workgroup)
+    const double s = batch_block_sum(partials, nblocks, Bp, na, b, a);
+    if (threadIdx.x == 0) out[(size_t)b * stride + off + a] = s;
 }
 #undef BCOL

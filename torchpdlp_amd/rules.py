@@ -1,6 +1,8 @@
 """The host-side rules of the reference's ``pdlp_algorithm`` (``/root/reference/PDLP/primal_dual_hybrid_gradient.py:7-181``,
 ``helpers.py:84-128``, ``enhancements.py:73-78``): when to restart, with which primal weight, and when to stop.
 
+``StreamQueue`` is the bookkeeping of a family streamed through the columns of a batch (``pdlp_algorithm_batch(slots=...)``).
+
 Pure numpy, no torch and no native library.  Every function takes scalars or arrays of any shape and returns the kind of thing it
 was given: ``PdhgDriver`` (solver.py) calls them with its scalars, ``BatchDriver`` (batch.py) with its ``[B]`` arrays.  Every
 intermediate is rounded to the working precision ``t`` (np.float32 / np.float64; ``t(v)`` of an array is an array of that type).
@@ -105,3 +107,68 @@ def primal_weight(dx2, dy2, omega, smooth_theta=0.5, t=np.float32):
         lw = t(np.log(np.float64(t(omega))))
         return t(np.exp(np.float64(t(t(smooth_theta) * lr) + t((t(1) - t(smooth_theta)) * lw))))
     return t(omega)
+
+
+class StreamQueue:
+    """Which LP of a family of ``B`` runs in which of ``slots`` columns, and when (``pdlp_algorithm_batch(slots=...)``).
+
+    The LPs wait in index order.  A column is free until ``admit`` gives it the next waiting LP and again once ``retire`` has taken
+    its LP out.  Admission is allowed only when the batch's iteration count ``k_global`` is a multiple of ``period``: every LP's
+    restart checks fall on multiples of the period of its OWN count (pdhg.py:115), so an LP that enters at a check of the batch
+    meets every later check of the batch at a check of its own -- the control flow of a batch that started with it.
+    ``column``, ``admitted_at``, ``retired_at`` (``[B]``; -1: never) are the schedule of the run."""
+
+    def __init__(self, B: int, slots: int, period: int):
+        if B < 1 or slots < 1 or period < 1:
+            raise ValueError("a family, the columns and the period are all at least 1")
+        self.B, self.slots, self.period = int(B), int(slots), int(period)
+        self.next = 0                                             # the first LP still waiting
+        self.lp = np.full(self.slots, -1, np.int64)               # column -> LP, -1 free
+        self.column = np.full(self.B, -1, np.int64)
+        self.admitted_at = np.full(self.B, -1, np.int64)
+        self.retired_at = np.full(self.B, -1, np.int64)
+
+    def waiting(self) -> int:
+        return self.B - self.next
+
+    def occupied(self) -> np.ndarray:
+        return np.flatnonzero(self.lp >= 0)
+
+    def free(self) -> np.ndarray:
+        return np.flatnonzero(self.lp < 0)
+
+    def may_admit(self, k_global: int) -> bool:
+        return int(k_global) % self.period == 0
+
+    def next_boundary(self, k_global: int) -> int:
+        """the first count >= ``k_global`` at which admission is allowed"""
+        return -(-int(k_global) // self.period) * self.period
+
+    def admit(self, k_global: int):
+        """the free columns, lowest first, take the next waiting LPs: ``(cols, ids)`` (empty when nothing waits or nothing is free)"""
+        if not self.may_admit(k_global):
+            raise ValueError(f"admission at k = {k_global}: not a multiple of the restart period {self.period}")
+        cols = self.free()[:self.waiting()]
+        ids = np.arange(self.next, self.next + cols.size, dtype=np.int64)
+        self.lp[cols] = ids
+        self.column[ids] = cols
+        self.admitted_at[ids] = int(k_global)
+        self.next += int(cols.size)
+        return cols, ids
+
+    def retire(self, cols, k_global: int) -> np.ndarray:
+        """the LPs of ``cols`` leave; their ids"""
+        cols = np.asarray(cols, np.int64).reshape(-1)
+        ids = self.lp[cols].copy()
+        if (ids < 0).any():
+            raise ValueError(f"columns {cols[ids < 0].tolist()} hold no LP")
+        self.retired_at[ids] = int(k_global)
+        self.lp[cols] = -1
+        return ids
+
+    def never_admitted(self) -> np.ndarray:
+        """the LPs still waiting (at a time-limit cut: they come back with k = 0)"""
+        return np.arange(self.next, self.B, dtype=np.int64)
+
+    def schedule(self) -> dict:
+        return dict(column=self.column.copy(), admitted_at=self.admitted_at.copy(), retired_at=self.retired_at.copy())
