@@ -194,32 +194,76 @@ def test_admit_writes_its_columns_and_nothing_else(attached):
     assert all(same_bits(v, after[k]) for k, v in state(be).items())
 
 
-def test_retire_is_the_report_of_the_listed_columns():
-    f = family(8, seed=64)
-    be = started_engine(f, adaptive_warm=11)
-    rc, act, sums = be.report(N.CUR, slot=1)
+def retire_engine(B, W, dtype=torch.float32, factors=None):
+    """a batch of B LPs 11 adaptive iterations in, averaged (x_avg and x_prev differ from x); ``factors``: "shared" -- the Ruiz
+    scaling of the family's one K --, "per_lp" -- a matrix per LP (matrix_noise) with every LP's own factors"""
+    f = family(B, seed=64, dtype=dtype, noise=0.2 if factors == "per_lp" else 0.0)
+    K, kw = csr(f), {}
+    if factors == "shared":
+        ones = lambda ln: torch.ones(ln, dtype=dtype, device=dev())
+        K, _, _, _, _, dp, _ = tp.ruiz_precondition(ones(f.n), K, ones(f.m), ones(f.n), ones(f.n), device=dev())
+        kw = dict(d_col=dp[0].view(-1), d_row=dp[1].view(-1))
+    elif factors == "per_lp":
+        sv, stv, dc, dr, _ = tp.ruiz_precondition_batch(K, f.vals.to(dev()))
+        kw = dict(K_values=sv, KT_values=stv, d_col=dc, d_row=dr)
+    d = lambda v: v.to(dev())
+    be = BatchEngine(K, f.m_ineq, d(f.C), d(f.Q), d(f.L), d(f.U), B, W=W, **kw)
+    t = np.float32 if dtype == torch.float32 else np.float64
+    eta = ((0.9 / norm2(f)) * np.linspace(0.7, 1.3, B)).astype(t)
+    be.start(eta, np.linspace(0.5, 2.0, B).astype(t), d(f.X_opt).to(dtype) * 0.5, d(f.Y_opt).to(dtype) * 0.5)
+    be.iterate(11, True, 0)
+    be.average(True)
+    return f, be
+
+
+RETIRE_CASES = {
+    # id: (B, W, dtype, which, factors, cols, ids); the result arrays have 6 columns.  Two groups: W = 16 with B = 32, W = 32 with 64
+    "f32_w8_cur": (8, 8, torch.float32, N.CUR, None, [6, 2], [1, 4]),
+    "w16_second_group_only": (32, 16, torch.float32, N.CUR, None, [20, 29], [1, 4]),        # group 0 leaves at once
+    "w16_both_groups": (32, 16, torch.float32, N.CUR, None, [3, 20, 15], [5, 0, 2]),
+    "w32_second_group_only": (64, 32, torch.float32, N.CUR, None, [40, 63], [4, 1]),
+    "w32_both_groups": (64, 32, torch.float32, N.CUR, None, [5, 33, 62], [0, 3, 2]),
+    "w8_avg": (8, 8, torch.float32, N.AVG, None, [6, 2], [1, 4]),
+    "w8_prev": (8, 8, torch.float32, N.PREV, None, [0, 7], [5, 3]),
+    "unscaled_shared_factors": (8, 8, torch.float32, N.CUR, "shared", [6, 2], [1, 4]),
+    "unscaled_per_lp_matrices": (8, 8, torch.float32, N.CUR, "per_lp", [1, 5, 4], [2, 0, 3]),
+    "f64_w16": (32, 16, torch.float64, N.CUR, None, [17, 4], [3, 1]),
+    # an entry with a column outside [0, Bp) or an id outside [0, 6) is skipped: (-1, 0), (8, 2) and (3, 6) serve nobody
+    "out_of_range_entries": (8, 8, torch.float32, N.CUR, None, [6, -1, 8, 2, 3], [1, 0, 2, 4, 6]),
+}
+
+
+@pytest.mark.parametrize("case", list(RETIRE_CASES), ids=list(RETIRE_CASES))
+def test_retire_is_the_report_of_the_listed_columns(case):
+    B, W, dtype, which, factors, cols, ids = RETIRE_CASES[case]
+    unscaled = factors is not None
+    f, be = retire_engine(B, W, dtype, factors)
+    src_x, src_y = {N.CUR: (be.x, be.y), N.AVG: (be.x_avg, be.y_avg), N.PREV: (be.x_prev, be.y_prev)}[which]
+    assert not torch.equal(be.x_avg[:, :B], be.x[:, :B]) and not torch.equal(be.x_prev[:, :B], be.x[:, :B])
+    rc, act, sums = be.report(which, unscaled=unscaled, slot=1)
     rc, act = rc.clone(), act.clone()
     Nr, poison = 6, 7.5
-    X, Y, RC, ACT = (torch.full((rows, Nr), poison, device=dev()) for rows in (f.n, f.m, f.n, f.m))
+    X, Y, RC, ACT = (torch.full((rows, Nr), poison, dtype=dtype, device=dev()) for rows in (f.n, f.m, f.n, f.m))
     be.out.fill_(poison)
-    cols, ids = [6, 2], [1, 4]
+    served = [(c, i) for c, i in zip(cols, ids) if 0 <= c < be.Bp and 0 <= i < Nr]
+    assert len(served) >= 2 and len({c // W for c, _ in served}) == (2 if "both_groups" in case or case == "f64_w16" else 1)
     before = state(be)
-    be.retire(cols, ids, X, Y, RC, ACT, N.CUR, slot=1)
+    be.retire(cols, ids, X, Y, RC, ACT, which, unscaled=unscaled, slot=1)
     out = be.out.cpu().numpy()
     assert all(same_bits(v, before[k]) for k, v in state(be).items())             # nothing of the batch is written
-    for col, i in zip(cols, ids):
-        assert torch.equal(X[:, i], be.x[:, col]) and torch.equal(Y[:, i], be.y[:, col])
+    for col, i in served:
+        assert torch.equal(X[:, i], src_x[:, col]) and torch.equal(Y[:, i], src_y[:, col])
         assert torch.equal(RC[:, i], rc[:, col]) and torch.equal(ACT[:, i], act[:, col])
         assert same_bits(out[1, col], sums[col])
-    others = [i for i in range(Nr) if i not in ids]
+    others = [i for i in range(Nr) if i not in [i for _, i in served]]
     for v in (X, Y, RC, ACT):
         assert (v[:, others] == poison).all()
     mask = np.ones(out.shape, bool)
-    mask[1, cols] = False
+    mask[1, [c for c, _ in served]] = False
     assert (out[mask] == poison).all()
     # without the optional arrays: the iterates and the sums only
     X2, Y2 = torch.full_like(X, poison), torch.full_like(Y, poison)
-    be.retire(cols, ids, X2, Y2, None, None, N.CUR, slot=1)
+    be.retire(cols, ids, X2, Y2, None, None, which, unscaled=unscaled, slot=1)
     assert torch.equal(X2, X) and torch.equal(Y2, Y) and same_bits(be.out.cpu().numpy(), out)
 
 

@@ -24,7 +24,7 @@ from . import _native as N
 from .engine import PdlpEngine
 from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, StreamQueue, kkt_error, kkt_from_sums, np_type,
                     primal_weight, restart_decision, start_eta, start_omega, terminated)
-from .solver import estimate_sigma, precond_factors, resolve_device
+from .solver import estimate_sigma, power_iteration_start, precond_factors, resolve_device
 from .sparse import CsrPair
 
 batch_decisions, kkt_finish, termination = restart_decision, kkt_from_sums, terminated      # (their earlier names)
@@ -97,27 +97,23 @@ class BatchEngine:
                                 p(self.part), p(self.out))
         self.k_start = None        # [Bp] int64 once the batch streams a family (enable_stream): the count at each column's admission
 
+    def _pad(self, v: Optional[torch.Tensor], ln: int) -> torch.Tensor:
+        """a fresh population [ln, Bp]: ``v`` [ln, B] in the columns of the LPs (1-D: the same in each; None: zeros), padding zero"""
+        out = torch.zeros(ln, self.Bp, dtype=self.dtype, device=self.device)
+        if v is not None:
+            v = v.to(device=self.device, dtype=self.dtype)
+            out[:, :self.B] = v.reshape(-1, 1) if v.dim() == 1 else v
+        return out
+
     def _col(self, v: torch.Tensor, ln: int) -> torch.Tensor:
         """a shared vector as it is, a per-LP one [len, B] padded to [len, Bp] (padding columns are dead)"""
-        v = v.to(device=self.device, dtype=self.dtype)
-        if v.dim() == 1:
-            return v.contiguous()
-        out = torch.zeros(ln, self.Bp, dtype=self.dtype, device=self.device)
-        out[:, :v.shape[1]] = v
-        return out
+        return v.to(device=self.device, dtype=self.dtype).contiguous() if v.dim() == 1 else self._pad(v, ln)
 
     def _population(self, v: torch.Tensor, ln: int) -> torch.Tensor:
         """[ln, B] values as a population [ln, Bp]: ``v`` itself when it already is one, else a padded copy"""
         if v.device == self.device and v.dtype == self.dtype and tuple(v.shape) == (ln, self.Bp) and v.is_contiguous():
             return v
         return self._pad(v, ln)
-
-    def _pad(self, v: Optional[torch.Tensor], ln: int) -> torch.Tensor:
-        out = torch.zeros(ln, self.Bp, dtype=self.dtype, device=self.device)
-        if v is not None:
-            v = v.to(device=self.device, dtype=self.dtype)
-            out[:, :self.B] = v.reshape(-1, 1) if v.dim() == 1 else v
-        return out
 
     def start(self, eta, omega, x_init=None, y_init=None):
         """pdhg.py:22-48 for every LP: the iterate (zeros or the given start), the restart point, empty sums, the step sizes"""
@@ -268,10 +264,8 @@ class BatchDriver:
         self.k_global = 0
 
     def start(self, sigma, x_init=None, y_init=None):
-        t = self.t
-        self.omega = start_omega(self.q_norm, self.c_norm, t)                # pdhg.py:23
-        eta = np.broadcast_to(np.asarray(start_eta(np.asarray(sigma, t), t), t), (self.be.B,))
-        self.be.start(eta, self.omega, x_init, y_init)                       # pdhg.py:22 (sigma: one for the batch, or [B])
+        eta, self.omega = start_scalars(sigma, self.q_norm, self.c_norm, self.t)
+        self.be.start(eta, self.omega, x_init, y_init)
 
     def occupy(self, cols, ids, q_norm, c_norm, omega):
         """columns ``cols`` start on LPs ``ids`` (pdhg.py:19-23,45-54 for each): their counters, norms, primal weight and status"""
@@ -386,12 +380,17 @@ def batch_size(*vecs) -> int:
     return bs.pop() if bs else 1
 
 
+def start_scalars(sigma, q_norm, c_norm, t):
+    """pdhg.py:22-23 per LP: the start ``(eta, omega)`` [B] from sigma (one for the batch, or [B]) and the norms [B]"""
+    omega = start_omega(q_norm, c_norm, t)
+    return np.broadcast_to(np.asarray(start_eta(np.asarray(sigma, t), t), t), np.shape(omega)), omega
+
+
 def estimate_sigma_batch(be: BatchEngine, b0=None, power_iters=100, seed=None) -> np.ndarray:
     """``estimate_sigma`` per LP of a batch with a matrix each: the reference's power iteration column by column on the population
     product, from the same start vector (``b0``, or drawn from ``seed`` as ``estimate_sigma`` draws it) for every LP"""
     if b0 is None:
-        g = torch.Generator().manual_seed(int(seed) if seed is not None else int(time.time_ns() % (2 ** 31)))
-        b0 = torch.randn(be.n, generator=g, dtype=torch.float32)
+        b0 = power_iteration_start(be.n, seed)
     return be.power_iteration(b0.to(be.device), power_iters)
 
 
@@ -413,65 +412,70 @@ def check_slots(slots, B: int, W, dtype, per_lp_matrices: bool, precondition: bo
     return True
 
 
-def _column_norms(v: torch.Tensor, B: int, t, device, chunk: int) -> np.ndarray:
-    """pdhg.py:19-20 per LP as the plain batch computes it (the float64 norm of every column, on the device); an array that stays on
-    the host goes there ``chunk`` columns at a time"""
+def _column_norms(v: torch.Tensor, B: int, t, device, chunk: Optional[int]) -> np.ndarray:
+    """pdhg.py:19-20 per LP (as solver._global_norm: the float64 norm of every column, rounded to the working precision), computed
+    where ``v`` is; with ``chunk``, an array that stays on the host goes to the device that many columns at a time"""
     v = v.reshape(v.shape[0], -1)
     norm = lambda w: np.sqrt((w.double() ** 2).sum(0).cpu().numpy())
-    if v.device == device or v.shape[1] == 1:
+    if chunk is None or v.device == device or v.shape[1] == 1:
         return np.broadcast_to(norm(v), (B,)).astype(t)
     return np.concatenate([norm(v[:, a:a + chunk].to(device)) for a in range(0, B, chunk)]).astype(t)
 
 
-def _solve_stream(Kp, m_ineq, C_, Q, L, U, B, slots, d_col, d_row, t0, *, max_kkt, tol, verbose, restart_period, precondition,
-                  primal_update, adaptive, time_limit, time_used, x_init, y_init, b0, sigma, seed, traces, W, report, K_values,
-                  setup_times, schedule):
-    """``pdlp_algorithm_batch`` for a family longer than the batch is wide: ``slots`` columns, the LPs queued in index order.
+def _setup(be: BatchEngine, B: int, Q, C_, K_values, perm, b0, sigma, seed, setup_times):
+    """pdhg.py:19-22 for the B LPs of a solve over ``be``: ``(q_norm, c_norm, sigma)``.  sigma when not given: once for a shared K,
+    per LP for a matrix each -- of a family longer than ``be`` is wide in chunks of its columns, each chunk's values through the
+    attached populations (the admissions overwrite them)."""
+    t, chunk = np_type(be.dtype), be.B if be.B < B else None
+    qn, cn = _column_norms(Q, B, t, be.device, chunk), _column_norms(C_, B, t, be.device, chunk)
+    if sigma is None:
+        ts = time.time()
+        if K_values is None:
+            sigma = estimate_sigma(be.eng, b0, 100, seed)
+        elif chunk is None:
+            sigma = estimate_sigma_batch(be, b0, 100, seed)
+        else:
+            b0, parts = power_iteration_start(be.n, seed) if b0 is None else b0, []
+            for a in range(0, B, chunk):
+                cnt = min(chunk, B - a)
+                with torch.cuda.stream(be.stream):
+                    be.K_valB[:, :cnt] = K_values[:, a:a + cnt].to(device=be.device, dtype=be.dtype)
+                    be.KT_valB.copy_(be.K_valB[perm])
+                parts.append(estimate_sigma_batch(be, b0, 100)[:cnt])
+            sigma = np.concatenate(parts)
+        if setup_times is not None:
+            setup_times["power_iteration_seconds"] = time.time() - ts
+    return qn, cn, sigma
+
+
+def _fill_report(report, be: BatchEngine, precondition, Y, rc, act, qn, cn, sums, omega):
+    """the solution report of the returned iterates (``Y`` scaled, as the batch holds it) into the caller's dict"""
+    if report is not None:
+        report.update(y=Y * be.d_row if precondition else Y.clone(), reduced_costs=rc, row_activity=act, q_norm=qn, c_norm=cn,
+                      **kkt_from_sums(sums, omega, np_type(be.dtype)))
+
+
+def _solve_stream(drv: BatchDriver, B, perm, C_, Q, L, U, x_init, y_init, K_values, qn, cn, sigma, time_left, verbose, want_report,
+                  schedule):
+    """``pdlp_algorithm_batch`` for a family longer than the batch is wide: the columns of ``drv.be``, the LPs queued in index order.
 
     After every restart check of the batch (``k_global`` a multiple of the period) the columns whose LP has finished are retired
     (``pdlp_batch_retire``: iterate and report into the LP's column of the results) and given to the next LPs
     (``pdlp_batch_admit``).  ``StreamQueue`` (rules.py) says why an admitted LP runs the control flow of a batch that started with
     it; the adaptive rule counts from its admission (``k_start``), and no kernel makes an LP's bits depend on its column: the
     results are those of the plain batch at the same W.  Per check still one host read; the sums of the retirements are fetched
-    once, at the end.  Device memory: the state of ``slots`` LPs, the ``(n + m, B)`` results, and one admission's columns."""
-    dev, dt, t = Kp.val.device, Kp.val.dtype, np_type(Kp.dtype)
-    W = int(W) if W is not None else group_width(slots, dt)
-    per_lp = [v.dim() == 2 and v.shape[1] > 1 for v in (C_, Q, L, U)]
-    head = lambda v, per: (v[:, :slots] if per else v.reshape(-1)).to(device=dev, dtype=dt)
-    be = BatchEngine(Kp, m_ineq, *(head(v, per) for v, per in zip((C_, Q, L, U), per_lp)), slots, d_col=d_col, d_row=d_row, W=W,
-                     K_values=None if K_values is None else K_values[:, :slots])
+    once, at the end.  Device memory: the state of ``slots`` LPs, the ``(n + m, B)`` results, and one admission's columns.
+    Returns ``(X, Y, rc, act, sums, res)``: the results [len, B] (rc, act None unless ``want_report``), the six sums [B, 6] and the
+    per-LP counters, objective, primal weight and status."""
+    be, t = drv.be, drv.t
+    dev, dt, slots = be.device, be.dtype, be.B
     be.enable_stream()
-    perm = Kp.transpose_perm() if K_values is not None else None
-    qn, cn = _column_norms(Q, B, t, dev, slots), _column_norms(C_, B, t, dev, slots)
-    if sigma is None:                                                        # pdhg.py:22 (once for a shared K; per LP, in chunks)
-        ts = time.time()
-        if K_values is None:
-            sigma = estimate_sigma(be.eng, b0, 100, seed)
-        else:
-            if b0 is None:
-                g = torch.Generator().manual_seed(int(seed) if seed is not None else int(time.time_ns() % (2 ** 31)))
-                b0 = torch.randn(be.n, generator=g, dtype=torch.float32)
-            parts = []
-            for a in range(0, B, slots):
-                cnt = min(slots, B - a)
-                with torch.cuda.stream(be.stream):
-                    be.K_valB[:, :cnt] = K_values[:, a:a + cnt].to(device=dev, dtype=dt)
-                    be.KT_valB.copy_(be.K_valB[perm])
-                parts.append(estimate_sigma_batch(be, b0, 100)[:cnt])
-            sigma = np.concatenate(parts)
-        if setup_times is not None:
-            setup_times["power_iteration_seconds"] = time.time() - ts
-    eta0 = np.broadcast_to(np.asarray(start_eta(np.asarray(sigma, t), t), t), (B,))      # pdhg.py:22
-    omega0 = np.broadcast_to(start_omega(qn, cn, t), (B,))                                # pdhg.py:23
-    drv = BatchDriver(be, qn[:slots].copy(), cn[:slots].copy(), restart_period, primal_update=primal_update, adaptive=adaptive,
-                      precondition=precondition, tol=tol, max_kkt=max_kkt, traces=traces)
+    eta0, omega0 = start_scalars(sigma, qn, cn, t)
     drv.live[:] = False
-    queue = StreamQueue(B, slots, restart_period)
+    queue = StreamQueue(B, slots, drv.period)
     X = torch.zeros(be.n, B, dtype=dt, device=dev)
     Y = torch.zeros(be.m, B, dtype=dt, device=dev)
-    rc = act = None
-    if report is not None:
-        rc, act = torch.zeros(be.n, B, dtype=dt, device=dev), torch.zeros(be.m, B, dtype=dt, device=dev)
+    rc, act = (torch.zeros(be.n, B, dtype=dt, device=dev), torch.zeros(be.m, B, dtype=dt, device=dev)) if want_report else (None, None)
     sums = torch.zeros(B, 6, dtype=torch.float64, device=dev)
     res = dict(k=np.zeros(B, np.int64), n=np.zeros(B, np.int64), j=np.zeros(B, np.int64), obj=np.full(B, np.nan),
                omega=np.array(omega0, t), status=[STATUS_TIME_LIMIT] * B)
@@ -484,16 +488,25 @@ def _solve_stream(Kp, m_ineq, C_, Q, L, U, B, slots, d_col, d_row, t0, *, max_kk
             return v.reshape(-1, 1).to(device=dev, dtype=dt).expand(-1, b - a).contiguous()
         return v[:, a:b].to(device=dev, dtype=dt).contiguous()
 
-    def admit():
-        cols, ids = queue.admit(drv.k_global)
-        if not cols.size:
-            return
+    def admit_cols(cols, ids):
         a, b = int(ids[0]), int(ids[-1]) + 1                                 # (the queue hands the LPs out in index order)
         with torch.cuda.stream(be.stream):
             Kv = stage(K_values, a, b, shared_ok=False)
             be.admit(cols, np.arange(b - a), eta0[a:b], omega0[a:b], stage(C_, a, b), stage(Q, a, b), stage(L, a, b), stage(U, a, b),
                      stage(x_init, a, b, shared_ok=False), stage(y_init, a, b, shared_ok=False), Kv, None if Kv is None else Kv[perm])
-        drv.occupy(cols, ids, qn[a:b], cn[a:b], omega0[a:b])
+        return slice(a, b)
+
+    def retire_cols(cols, ids):
+        be.retire(cols, ids, X, Y, rc, act, N.CUR, unscaled=drv.precondition)
+        with torch.cuda.stream(be.stream):
+            sums[torch.from_numpy(ids).to(dev)] = be.retire_out[0][torch.from_numpy(cols).to(dev)]
+
+    def admit():
+        cols, ids = queue.admit(drv.k_global)
+        if not cols.size:
+            return
+        lps = admit_cols(cols, ids)
+        drv.occupy(cols, ids, qn[lps], cn[lps], omega0[lps])
         ks = np.zeros(slots, np.int64)
         ks[queue.occupied()] = queue.admitted_at[queue.lp[queue.occupied()]]
         be.set_scalars(k_start=ks, live=drv.live.astype(np.int32))
@@ -502,9 +515,7 @@ def _solve_stream(Kp, m_ineq, C_, Q, L, U, B, slots, d_col, d_row, t0, *, max_kk
         if not cols.size:
             return
         ids = queue.retire(cols, drv.k_global)
-        be.retire(cols, ids, X, Y, rc, act, N.CUR, unscaled=bool(precondition))
-        with torch.cuda.stream(be.stream):
-            sums[torch.from_numpy(ids).to(dev)] = be.retire_out[0][torch.from_numpy(cols).to(dev)]
+        retire_cols(cols, ids)
         for key, arr in (("k", drv.k), ("n", drv.n), ("j", drv.j), ("obj", drv.obj), ("omega", drv.omega)):
             res[key][ids] = arr[cols]
         for c_, i in zip(cols, ids):
@@ -514,7 +525,7 @@ def _solve_stream(Kp, m_ineq, C_, Q, L, U, B, slots, d_col, d_row, t0, *, max_kk
     in_time = True
     while queue.occupied().size:
         if drv.live.any():
-            in_time = time.time() - t0 + time_used < time_limit
+            in_time = time_left()
             drv.step(in_time)
         if not drv.live.any():               # nothing runs: the clock of the batch may move to its next check
             drv.k_global = queue.next_boundary(drv.k_global)
@@ -529,23 +540,12 @@ def _solve_stream(Kp, m_ineq, C_, Q, L, U, B, slots, d_col, d_row, t0, *, max_kk
     sched = queue.schedule()
     while queue.waiting():
         cols, ids = queue.admit(queue.next_boundary(drv.k_global))
-        a, b = int(ids[0]), int(ids[-1]) + 1
-        with torch.cuda.stream(be.stream):
-            Kv = stage(K_values, a, b, shared_ok=False)
-            be.admit(cols, np.arange(b - a), eta0[a:b], omega0[a:b], stage(C_, a, b), stage(Q, a, b), stage(L, a, b), stage(U, a, b),
-                     stage(x_init, a, b, shared_ok=False), stage(y_init, a, b, shared_ok=False), Kv, None if Kv is None else Kv[perm])
+        admit_cols(cols, ids)
         queue.retire(cols, drv.k_global)
-        be.retire(cols, ids, X, Y, rc, act, N.CUR, unscaled=bool(precondition))
-        with torch.cuda.stream(be.stream):
-            sums[torch.from_numpy(ids).to(dev)] = be.retire_out[0][torch.from_numpy(cols).to(dev)]
+        retire_cols(cols, ids)
     if schedule is not None:
-        schedule.update(sched, slots=slots, group_width=W, never_admitted=late)
-    if report is not None:
-        Yr = Y * be.d_row if precondition else Y.clone()
-        report.update(y=Yr, reduced_costs=rc, row_activity=act, q_norm=qn, c_norm=cn,
-                      **kkt_from_sums(sums.cpu().numpy(), res["omega"], t))
-    be.synchronize()
-    return X, Y, res["obj"], res["k"], res["n"], res["j"], res["status"], time.time() - t0 + time_used
+        schedule.update(sched, slots=slots, group_width=be.W, never_admitted=late)
+    return X, Y, rc, act, sums, res
 
 
 def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, tol=1e-4, verbose=False, restart_period=40,
@@ -579,33 +579,31 @@ def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, t
         if v is not None and (v.dim() not in (1, 2) or v.shape[0] != ln or (v.dim() == 2 and v.shape[1] != B)):
             raise ValueError(f"{name} must have shape ({ln},) or ({ln}, {B}), got {tuple(v.shape)}")
     d_col, d_row = precond_factors(precondition, data_precond)
+    if streamed and KT_values is not None:
+        raise ValueError("a streamed family takes K_values only (the values of K' are permuted per admission)")
+    dev, dt = Kp.val.device, Kp.val.dtype
+    width = int(slots) if streamed else B            # the columns of the batch; a streamed family's first LPs start in them
+    head = lambda v: v if not streamed else (v[:, :width] if v.dim() == 2 and v.shape[1] > 1 else v.reshape(-1)).to(device=dev, dtype=dt)
+    be = BatchEngine(Kp, m_ineq, head(C_), head(Q), head(L), head(U), width, d_col=d_col, d_row=d_row, W=group_width,
+                     K_values=None if K_values is None else K_values[:, :width], KT_values=KT_values)
+    perm = Kp.transpose_perm() if streamed and K_values is not None else None
+    qn, cn, sigma = _setup(be, B, Q, C_, K_values, perm, b0, sigma, seed, setup_times)
+    drv = BatchDriver(be, qn[:width].copy(), cn[:width].copy(), restart_period, primal_update=primal_update, adaptive=adaptive,
+                      precondition=precondition, tol=tol, max_kkt=max_kkt, traces=traces)
+    time_left = lambda: time.time() - t0 + time_used < time_limit
     if streamed:
-        if KT_values is not None:
-            raise ValueError("a streamed family takes K_values only (the values of K' are permuted per admission)")
-        return _solve_stream(Kp, m_ineq, C_, Q, L, U, B, int(slots), d_col, d_row, t0, max_kkt=max_kkt, tol=tol, verbose=verbose,
-                             restart_period=restart_period, precondition=precondition, primal_update=primal_update, adaptive=adaptive,
-                             time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init, b0=b0, sigma=sigma, seed=seed,
-                             traces=traces, W=group_width, report=report, K_values=K_values, setup_times=setup_times, schedule=schedule)
-    be = BatchEngine(Kp, m_ineq, C_, Q, L, U, B, d_col=d_col, d_row=d_row, W=group_width, K_values=K_values, KT_values=KT_values)
-    t = np_type(Kp.dtype)
-    # pdhg.py:19-20 per LP (as solver._global_norm: the float64 norm, rounded to the working precision)
-    colnorm = lambda v: np.broadcast_to(np.sqrt((v.double().reshape(v.shape[0], -1) ** 2).sum(0).cpu().numpy()), (B,)).astype(t)
-    qn, cn = colnorm(Q), colnorm(C_)
-    if sigma is None:                                                        # pdhg.py:22: K only, once for the batch ...
-        ts = time.time()
-        sigma = estimate_sigma_batch(be, b0, 100, seed) if K_values is not None else estimate_sigma(be.eng, b0, 100, seed)
-        if setup_times is not None:                                          # ... or once per LP's own matrix
-            setup_times["power_iteration_seconds"] = time.time() - ts
-    drv = BatchDriver(be, qn, cn, restart_period, primal_update=primal_update, adaptive=adaptive, precondition=precondition, tol=tol,
-                      max_kkt=max_kkt, traces=traces)
+        X, Y, rc, act, sums, res = _solve_stream(drv, B, perm, C_, Q, L, U, x_init, y_init, K_values, qn, cn, sigma, time_left, verbose,
+                                                 report is not None, schedule)
+        _fill_report(report, be, precondition, Y, rc, act, qn, cn, sums.cpu().numpy(), res["omega"])
+        be.synchronize()
+        return X, Y, res["obj"], res["k"], res["n"], res["j"], res["status"], time.time() - t0 + time_used
     drv.start(sigma, x_init, y_init)
     while drv.live.any():
-        drv.step(time.time() - t0 + time_used < time_limit)
+        drv.step(time_left())
         if verbose:
             print(f"[batch] k={drv.k_global} live={int(drv.live.sum())}/{B}")
     if report is not None:
         rc, act, sums = be.report(N.CUR, unscaled=bool(precondition))
-        Yr = be.y[:, :B] * be.d_row if precondition else be.y[:, :B].clone()
-        report.update(y=Yr, reduced_costs=rc.clone(), row_activity=act.clone(), q_norm=qn, c_norm=cn, **kkt_from_sums(sums, drv.omega, t))
+        _fill_report(report, be, precondition, be.y[:, :B], rc.clone(), act.clone(), qn, cn, sums, drv.omega)
     be.synchronize()
     return (be.x[:, :B].clone(), be.y[:, :B].clone(), drv.obj, drv.k, drv.n, drv.j, list(drv.status), time.time() - t0 + time_used)

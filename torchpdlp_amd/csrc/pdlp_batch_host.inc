@@ -1,8 +1,10 @@
 // pdlp_batch_host.inc -- host side of the batched solves (pdlp_batch_*, include/pdlp_hip.h): launch shapes and the C entry points.
 // Part of pdlp_hip.hip (included at file scope after the other entry points; not a translation unit of its own).
-// Kernels: pdlp_kernel_batch.inc.  Instantiated per (dtype, W, shared or per-LP matrix values, epilogue); every other flag (shared
-// or per-LP vectors, the iteration count) is a launch argument.  With matrices attached (pdlp_batch_attach_matrices) every product
-// here reads the per-LP values and the un-scaling epilogues the per-LP Ruiz factors.
+// Kernels: pdlp_kernel_batch.inc.  Every population product is one batch_launch of k_batch_mv, instantiated per (dtype, W, shared
+// or per-LP matrix values, column selector, epilogue) -- batch_dispatch turns the batch's dtype and W into those constants; every
+// other flag (shared or per-LP vectors, the iteration count) is a launch argument.  With matrices attached
+// (pdlp_batch_attach_matrices) every product reads the per-LP values and the un-scaling epilogues the per-LP Ruiz factors.  The
+// report and retirement are one body (batch_report_w) under two selectors.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -29,8 +31,28 @@ inline int batch_dper(pdlp_handle h) { return h->bm.d_col ? 1 : 0; }
 // the second set of partials (the adaptive rule needs two at once)
 inline double* batch_part2(const pdlp_batch* b) { return b->part + (size_t)4 * BATCH_MAXG * b->Bp; }
 
-template <typename T, int W, class Epi>
-int batch_mv(pdlp_handle h, const pdlp_batch* b, bool transpose, const T* Vin, const Epi& epi, double* partials)
+// The element type and W of a batch as compile-time constants, f(T(), integral_constant<int, W>()), and a flag beside them,
+// f(T(), integral_constant<int, W>(), bool_constant<flag>()): what DISPATCH is for the element type alone.  Use: TYPE(t), VAL(w)
+template <class F> int batch_dispatch(pdlp_handle h, const pdlp_batch* b, F f)
+{
+    auto width = [&](auto t) {
+        if (b->W == 8) return f(t, std::integral_constant<int, 8>());
+        if (b->W == 16) return f(t, std::integral_constant<int, 16>());
+        return f(t, std::integral_constant<int, 32>());
+    };
+    return h->p.dtype == PDLP_F32 ? width(float()) : width(double());
+}
+template <class F> int batch_dispatch(pdlp_handle h, const pdlp_batch* b, int flag, F f)
+{
+    return batch_dispatch(h, b, [&](auto t, auto w) { return flag ? f(t, w, std::true_type()) : f(t, w, std::false_type()); });
+}
+#define TYPE(t) decltype(t)
+#define VAL(c) decltype(c)::value
+
+// one product launch: K (or K' with `transpose`) times the population Vin over the columns `sel` picks, with every LP's own
+// values when matrices are attached
+template <typename T, int W, class Sel, class Epi>
+int batch_launch(pdlp_handle h, const pdlp_batch* b, bool transpose, const T* Vin, const Sel& sel, const Epi& epi, double* partials)
 {
     const int rows = (int)(transpose ? h->p.n : h->p.m);
     const pdlp_problem& p = h->p;
@@ -39,41 +61,43 @@ int batch_mv(pdlp_handle h, const pdlp_batch* b, bool transpose, const T* Vin, c
     const dim3 grid(batch_grid(rows, W), b->Bp / W);
     if (h->bm.K_val) {
         const T* va = (const T*)(transpose ? h->bm.KT_val : h->bm.K_val);
-        hipLaunchKernelGGL((k_batch_mv<T, W, true, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, b->live, epi, partials);
+        hipLaunchKernelGGL((k_batch_mv<T, W, true, Sel, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, sel, epi, partials);
     } else {
         const T* va = (const T*)(transpose ? p.KT_val : p.K_val);
-        hipLaunchKernelGGL((k_batch_mv<T, W, false, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, b->live, epi, partials);
+        hipLaunchKernelGGL((k_batch_mv<T, W, false, Sel, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, sel, epi, partials);
     }
     HIP_TRY(hipGetLastError());
     return PDLP_OK;
 }
 
-// the same over every column b < B, frozen or not (the report, the plain product)
-template <typename T, int W, class Epi>
-int batch_mv_all(pdlp_handle h, const pdlp_batch* b, bool transpose, const T* Vin, const Epi& epi, double* partials)
+// the sums of `count` columns into out[slot]: every column of the population, or the listed ones
+int batch_finalize(pdlp_handle h, const pdlp_batch* b, const double* partials, int64_t rows, int na, int slot, int off, int count,
+                   const int32_t* cols = nullptr, const int32_t* ids = nullptr, int N = 0)
 {
-    const int rows = (int)(transpose ? h->p.n : h->p.m);
-    const pdlp_problem& p = h->p;
-    const int64_t* rp = transpose ? p.KT_rowptr : p.K_rowptr;
-    const int32_t* ci = transpose ? p.KT_colidx : p.K_colidx;
-    const dim3 grid(batch_grid(rows, W), b->Bp / W);
-    if (h->bm.K_val) {
-        const T* va = (const T*)(transpose ? h->bm.KT_val : h->bm.K_val);
-        hipLaunchKernelGGL((k_batch_mv_all<T, W, true, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, b->B, epi, partials);
-    } else {
-        const T* va = (const T*)(transpose ? p.KT_val : p.K_val);
-        hipLaunchKernelGGL((k_batch_mv_all<T, W, false, Epi>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Vin, b->Bp, b->B, epi, partials);
-    }
+    hipLaunchKernelGGL(k_batch_finalize, dim3(count * na), dim3(BLOCK), 0, h->stream, partials, batch_grid(rows, b->W), b->Bp, na,
+                       cols, ids, N, b->out + (size_t)slot * b->Bp * 6, 6, off);
     HIP_TRY(hipGetLastError());
     return PDLP_OK;
 }
 
-int batch_finalize(pdlp_handle h, const pdlp_batch* b, const double* partials, int64_t rows, int na, int slot, int off)
+// the arguments of a pass over an iterate: `which` and the slot of its sums; the Ruiz factors an un-scaled pass divides by
+int batch_check_pass(pdlp_handle h, const pdlp_batch* b, int which, int slot)
 {
-    hipLaunchKernelGGL(k_batch_finalize, dim3(b->Bp * na), dim3(BLOCK), 0, h->stream, partials,
-                       batch_grid(rows, b->W), b->Bp, na, b->out + (size_t)slot * b->Bp * 6, 6, off);
-    HIP_TRY(hipGetLastError());
-    return PDLP_OK;
+    if ((which != PDLP_CUR && which != PDLP_AVG && which != PDLP_PREV) || slot < 0 || slot > 2) return PDLP_ERR_INVALID;
+    return batch_check(h, b);
+}
+int batch_check_unscaled(pdlp_handle h, int unscaled) { return unscaled && (!batch_dcol(h) || !batch_drow(h)) ? PDLP_ERR_STATE : PDLP_OK; }
+
+// the iterate `which` of the batch behind the KKT epilogues of its two sides
+template <typename T, bool U> BKktDual<T, U> batch_kkt_dual(pdlp_handle h, const pdlp_batch* b, int which)
+{
+    const void* X = which == PDLP_CUR ? b->x : which == PDLP_AVG ? b->x_avg : b->x_prev;
+    return {(const T*)X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp, (const T*)batch_dcol(h), batch_dper(h)};
+}
+template <typename T, bool U> BKktPrimal<T, U> batch_kkt_primal(pdlp_handle h, const pdlp_batch* b, int which)
+{
+    const void* Y = which == PDLP_CUR ? b->y : which == PDLP_AVG ? b->y_avg : b->y_prev;
+    return {(const T*)Y, (const T*)b->q, b->q_per_lp, (const T*)batch_drow(h), batch_dper(h), (int)h->p.m_ineq};
 }
 
 #define BATCH_TRY(expr)                          \
@@ -82,42 +106,29 @@ int batch_finalize(pdlp_handle h, const pdlp_batch* b, const double* partials, i
         if (rc_ != PDLP_OK) return rc_;          \
     } while (0)
 
-template <typename T, int W> int batch_iterate_w(pdlp_handle h, const pdlp_batch* b, int iters, bool adaptive, int64_t k0, const int64_t* k_start)
+template <typename T, int W, bool ADAPT> int batch_iterate_w(pdlp_handle h, const pdlp_batch* b, int iters, int64_t k0, const int64_t* k_start)
 {
-    const int ineq_end = (int)h->p.m_ineq;
+    const BSelLive live{b->live};
     T *eta = (T*)b->eta, *omega = (T*)b->omega, *eta_sum = (T*)b->eta_sum, *wpend = (T*)b->wpend;
+    const BPrimal<T, ADAPT> ep{(T*)b->x, (T*)b->x_prev, (T*)b->xbar, (T*)b->x_sum, (const T*)b->c, (const T*)b->l, (const T*)b->u,
+                               b->c_per_lp, b->l_per_lp, b->u_per_lp, eta, omega, wpend};
+    const BDual<T, ADAPT> ed{(T*)b->y, (T*)b->y_prev, (T*)b->y_sum, (T*)b->dy, (const T*)b->q, b->q_per_lp, eta, omega, wpend, (int)h->p.m_ineq};
+    const BDen<T> en{(const T*)b->x, (const T*)b->x_prev};
     for (int it = 0; it < iters; ++it) {
-        if (adaptive) {
-            BPrimal<T, true> ep{(T*)b->x, (T*)b->x_prev, (T*)b->xbar, (T*)b->x_sum, (const T*)b->c, (const T*)b->l, (const T*)b->u,
-                                b->c_per_lp, b->l_per_lp, b->u_per_lp, eta, omega, wpend};
-            BATCH_TRY((batch_mv<T, W>(h, b, true, (const T*)b->y, ep, nullptr)));
-            BDual<T, true> ed{(T*)b->y, (T*)b->y_prev, (T*)b->y_sum, (T*)b->dy, (const T*)b->q, b->q_per_lp, eta, omega, wpend, ineq_end};
-            BATCH_TRY((batch_mv<T, W>(h, b, false, (const T*)b->xbar, ed, b->part)));
-            BDen<T> en{(const T*)b->x, (const T*)b->x_prev};
-            BATCH_TRY((batch_mv<T, W>(h, b, true, (const T*)b->dy, en, batch_part2(b))));
+        BATCH_TRY((batch_launch<T, W>(h, b, true, (const T*)b->y, live, ep, nullptr)));
+        BATCH_TRY((batch_launch<T, W>(h, b, false, (const T*)b->xbar, live, ed, ADAPT ? b->part : nullptr)));
+        if (ADAPT) {
+            BATCH_TRY((batch_launch<T, W>(h, b, true, (const T*)b->dy, live, en, batch_part2(b))));
             hipLaunchKernelGGL(k_batch_adapt<T>, dim3(b->Bp), dim3(BLOCK), 0, h->stream, b->Bp, b->live, b->part,
                                batch_grid(h->p.m, W), batch_part2(b), batch_grid(h->p.n, W), eta, omega, eta_sum, wpend, k0 + it + 1, k_start);
             HIP_TRY(hipGetLastError());
-        } else {
-            BPrimal<T, false> ep{(T*)b->x, (T*)b->x_prev, (T*)b->xbar, (T*)b->x_sum, (const T*)b->c, (const T*)b->l, (const T*)b->u,
-                                 b->c_per_lp, b->l_per_lp, b->u_per_lp, eta, omega, wpend};
-            BATCH_TRY((batch_mv<T, W>(h, b, true, (const T*)b->y, ep, nullptr)));
-            BDual<T, false> ed{(T*)b->y, (T*)b->y_prev, (T*)b->y_sum, (T*)b->dy, (const T*)b->q, b->q_per_lp, eta, omega, wpend, ineq_end};
-            BATCH_TRY((batch_mv<T, W>(h, b, false, (const T*)b->xbar, ed, nullptr)));
         }
     }
-    if (!adaptive && iters > 0) {
+    if (!ADAPT && iters > 0) {
         hipLaunchKernelGGL(k_batch_etasum<T>, dim3(grid_for(b->Bp)), dim3(BLOCK), 0, h->stream, b->Bp, b->live, (const T*)eta, eta_sum, iters);
         HIP_TRY(hipGetLastError());
     }
     return PDLP_OK;
-}
-
-template <typename T> int batch_iterate_t(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0, const int64_t* k_start)
-{
-    if (b->W == 8) return batch_iterate_w<T, 8>(h, b, iters, adaptive != 0, k0, k_start);
-    if (b->W == 16) return batch_iterate_w<T, 16>(h, b, iters, adaptive != 0, k0, k_start);
-    return batch_iterate_w<T, 32>(h, b, iters, adaptive != 0, k0, k_start);
 }
 
 template <typename T> int batch_average_t(pdlp_handle h, const pdlp_batch* b, int adaptive)
@@ -139,58 +150,29 @@ template <typename T> int batch_average_t(pdlp_handle h, const pdlp_batch* b, in
 
 template <typename T, int W, bool U> int batch_kkt_w(pdlp_handle h, const pdlp_batch* b, int which, int slot)
 {
-    const T* X = (const T*)(which == PDLP_CUR ? b->x : which == PDLP_AVG ? b->x_avg : b->x_prev);
-    const T* Y = (const T*)(which == PDLP_CUR ? b->y : which == PDLP_AVG ? b->y_avg : b->y_prev);
-    BKktDual<T, U> ed{X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp, (const T*)batch_dcol(h),
-                       batch_dper(h)};
-    BATCH_TRY((batch_mv<T, W>(h, b, true, Y, ed, b->part)));
-    BATCH_TRY(batch_finalize(h, b, b->part, h->p.n, 4, slot, 0));
-    BKktPrimal<T, U> ep{Y, (const T*)b->q, b->q_per_lp, (const T*)batch_drow(h), batch_dper(h), (int)h->p.m_ineq};
-    BATCH_TRY((batch_mv<T, W>(h, b, false, X, ep, batch_part2(b))));
-    return batch_finalize(h, b, batch_part2(b), h->p.m, 2, slot, 4);
+    const BSelLive live{b->live};
+    const BKktDual<T, U> ed = batch_kkt_dual<T, U>(h, b, which);
+    const BKktPrimal<T, U> ep = batch_kkt_primal<T, U>(h, b, which);
+    BATCH_TRY((batch_launch<T, W>(h, b, true, ep.Y, live, ed, b->part)));
+    BATCH_TRY(batch_finalize(h, b, b->part, h->p.n, 4, slot, 0, b->Bp));
+    BATCH_TRY((batch_launch<T, W>(h, b, false, ed.X, live, ep, batch_part2(b))));
+    return batch_finalize(h, b, batch_part2(b), h->p.m, 2, slot, 4, b->Bp);
 }
 
-template <typename T> int batch_kkt_t(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot)
+// The solution report of the columns `sel` picks: the two products of a KKT pass with lam and K x stored (and the iterate, where
+// Xo / Yo are given) at column `id` of the [len][N] arrays, the six sums of the `count` columns into out[slot].  pdlp_batch_report:
+// every LP b < B into [len][Bp] arrays, column b (padding columns of rc, act and out are never written: the finalize launch ends
+// at column B); pdlp_batch_retire: the listed columns into the caller's results.
+template <typename T, int W, bool U, class Sel>
+int batch_report_w(pdlp_handle h, const pdlp_batch* b, int which, int slot, const Sel& sel, int count, const int32_t* cols,
+                   const int32_t* ids, void* Xo, void* Yo, void* rc, void* act, int N)
 {
-    if (unscaled) {
-        if (b->W == 8) return batch_kkt_w<T, 8, true>(h, b, which, slot);
-        if (b->W == 16) return batch_kkt_w<T, 16, true>(h, b, which, slot);
-        return batch_kkt_w<T, 32, true>(h, b, which, slot);
-    }
-    if (b->W == 8) return batch_kkt_w<T, 8, false>(h, b, which, slot);
-    if (b->W == 16) return batch_kkt_w<T, 16, false>(h, b, which, slot);
-    return batch_kkt_w<T, 32, false>(h, b, which, slot);
-}
-
-// the report of every LP b < B: the two products of a KKT pass over all columns, lam and K x stored, the sums of columns b < B
-// into out[slot] (padding columns of rc, act and out are never written: the finalize launch ends at column B)
-template <typename T, int W, bool U> int batch_report_w(pdlp_handle h, const pdlp_batch* b, int which, int slot, void* rc, void* act)
-{
-    const T* X = (const T*)(which == PDLP_CUR ? b->x : which == PDLP_AVG ? b->x_avg : b->x_prev);
-    const T* Y = (const T*)(which == PDLP_CUR ? b->y : which == PDLP_AVG ? b->y_avg : b->y_prev);
-    const pdlp_problem& p = h->p;
-    double* out = b->out + (size_t)slot * b->Bp * 6;
-    BReportDual<T, U> ed{{X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp,
-                          (const T*)batch_dcol(h), batch_dper(h)}, (T*)rc};
-    BATCH_TRY((batch_mv_all<T, W>(h, b, true, Y, ed, b->part)));
-    hipLaunchKernelGGL(k_batch_finalize, dim3(b->B * 4), dim3(BLOCK), 0, h->stream, (const double*)b->part, batch_grid(p.n, W), b->Bp, 4, out, 6, 0);
-    BReportPrimal<T, U> ep{{Y, (const T*)b->q, b->q_per_lp, (const T*)batch_drow(h), batch_dper(h), (int)p.m_ineq}, (T*)act};
-    BATCH_TRY((batch_mv_all<T, W>(h, b, false, X, ep, batch_part2(b))));
-    hipLaunchKernelGGL(k_batch_finalize, dim3(b->B * 2), dim3(BLOCK), 0, h->stream, (const double*)batch_part2(b), batch_grid(p.m, W), b->Bp, 2, out, 6, 4);
-    HIP_TRY(hipGetLastError());
-    return PDLP_OK;
-}
-
-template <typename T> int batch_report_t(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot, void* rc, void* act)
-{
-    if (unscaled) {
-        if (b->W == 8) return batch_report_w<T, 8, true>(h, b, which, slot, rc, act);
-        if (b->W == 16) return batch_report_w<T, 16, true>(h, b, which, slot, rc, act);
-        return batch_report_w<T, 32, true>(h, b, which, slot, rc, act);
-    }
-    if (b->W == 8) return batch_report_w<T, 8, false>(h, b, which, slot, rc, act);
-    if (b->W == 16) return batch_report_w<T, 16, false>(h, b, which, slot, rc, act);
-    return batch_report_w<T, 32, false>(h, b, which, slot, rc, act);
+    const BReportDual<T, U> ed{batch_kkt_dual<T, U>(h, b, which), (T*)Xo, (T*)rc, N};
+    const BReportPrimal<T, U> ep{batch_kkt_primal<T, U>(h, b, which), (T*)Yo, (T*)act, N};
+    BATCH_TRY((batch_launch<T, W>(h, b, true, ep.kkt.Y, sel, ed, b->part)));
+    BATCH_TRY(batch_finalize(h, b, b->part, h->p.n, 4, slot, 0, count, cols, ids, N));
+    BATCH_TRY((batch_launch<T, W>(h, b, false, ed.kkt.X, sel, ep, batch_part2(b))));
+    return batch_finalize(h, b, batch_part2(b), h->p.m, 2, slot, 4, count, cols, ids, N);
 }
 
 // admission: one launch per side -- the n rows (c, l, u, x and the LP's scalars), the m rows (q, y), the nnz items (both value
@@ -219,64 +201,6 @@ template <typename T> int batch_admit_t(pdlp_handle h, const pdlp_batch* b, int 
     return PDLP_OK;
 }
 
-// retirement: the report of the listed columns, stored into the caller's [len][N] arrays; the sums through the report's tree
-template <typename T, int W, bool U>
-int batch_retire_w(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids, int which, int slot,
-                   void* Xo, void* Yo, void* rc, void* act, int N)
-{
-    const T* X = (const T*)(which == PDLP_CUR ? b->x : which == PDLP_AVG ? b->x_avg : b->x_prev);
-    const T* Y = (const T*)(which == PDLP_CUR ? b->y : which == PDLP_AVG ? b->y_avg : b->y_prev);
-    const pdlp_problem& p = h->p;
-    double* out = b->out + (size_t)slot * b->Bp * 6;
-    const bool per = h->bm.K_val != nullptr;
-    for (int side = 0; side < 2; ++side) {      // 0: rows of K' (x, lam, four sums), 1: rows of K (y, K x, two sums)
-        const int rows = (int)(side == 0 ? p.n : p.m);
-        const int64_t* rp = side == 0 ? p.KT_rowptr : p.K_rowptr;
-        const int32_t* ci = side == 0 ? p.KT_colidx : p.K_colidx;
-        const T* va = (const T*)(per ? (side == 0 ? h->bm.KT_val : h->bm.K_val) : (side == 0 ? p.KT_val : p.K_val));
-        const dim3 grid(batch_grid(rows, W), b->Bp / W);
-        double* part = side == 0 ? b->part : batch_part2(b);
-        if (side == 0) {
-            BRetireDual<T, U> e{{X, (const T*)b->c, (const T*)b->l, (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp,
-                                 (const T*)batch_dcol(h), batch_dper(h)}, (T*)Xo, (T*)rc, N, -1};
-            if (per) hipLaunchKernelGGL((k_batch_mv_cols<T, W, true, BRetireDual<T, U>>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Y, b->Bp, count, cols, ids, N, e, part);
-            else hipLaunchKernelGGL((k_batch_mv_cols<T, W, false, BRetireDual<T, U>>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, Y, b->Bp, count, cols, ids, N, e, part);
-        } else {
-            BRetirePrimal<T, U> e{{Y, (const T*)b->q, b->q_per_lp, (const T*)batch_drow(h), batch_dper(h), (int)p.m_ineq}, (T*)Yo, (T*)act, N, -1};
-            if (per) hipLaunchKernelGGL((k_batch_mv_cols<T, W, true, BRetirePrimal<T, U>>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, X, b->Bp, count, cols, ids, N, e, part);
-            else hipLaunchKernelGGL((k_batch_mv_cols<T, W, false, BRetirePrimal<T, U>>), grid, dim3(BLOCK), 0, h->stream, rows, rp, ci, va, X, b->Bp, count, cols, ids, N, e, part);
-        }
-        HIP_TRY(hipGetLastError());
-        const int na = side == 0 ? 4 : 2;
-        hipLaunchKernelGGL(k_batch_finalize_cols, dim3(count * na), dim3(BLOCK), 0, h->stream, (const double*)part, batch_grid(rows, W), b->Bp,
-                           na, cols, out, 6, side == 0 ? 0 : 4);
-        HIP_TRY(hipGetLastError());
-    }
-    return PDLP_OK;
-}
-
-template <typename T>
-int batch_retire_t(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids, int which, int unscaled,
-                   int slot, void* Xo, void* Yo, void* rc, void* act, int N)
-{
-    if (unscaled) {
-        if (b->W == 8) return batch_retire_w<T, 8, true>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
-        if (b->W == 16) return batch_retire_w<T, 16, true>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
-        return batch_retire_w<T, 32, true>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
-    }
-    if (b->W == 8) return batch_retire_w<T, 8, false>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
-    if (b->W == 16) return batch_retire_w<T, 16, false>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
-    return batch_retire_w<T, 32, false>(h, b, count, cols, ids, which, slot, Xo, Yo, rc, act, N);
-}
-
-template <typename T> int batch_product_t(pdlp_handle h, const pdlp_batch* b, int transpose, const void* Vin, void* Vout)
-{
-    BStore<T> es{(T*)Vout};
-    if (b->W == 8) return batch_mv_all<T, 8>(h, b, transpose != 0, (const T*)Vin, es, nullptr);
-    if (b->W == 16) return batch_mv_all<T, 16>(h, b, transpose != 0, (const T*)Vin, es, nullptr);
-    return batch_mv_all<T, 32>(h, b, transpose != 0, (const T*)Vin, es, nullptr);
-}
-
 template <typename T, int W> int batch_restart_w(pdlp_handle h, const pdlp_batch* b, int slot)
 {
     const dim3 gn(batch_grid(h->p.n, W), b->Bp / W), gm(batch_grid(h->p.m, W), b->Bp / W);
@@ -286,15 +210,8 @@ template <typename T, int W> int batch_restart_w(pdlp_handle h, const pdlp_batch
     hipLaunchKernelGGL((k_batch_restart<T, W>), gm, dim3(BLOCK), 0, h->stream, (int)h->p.m, b->Bp, b->action, (T*)b->y,
                        (const T*)b->y_avg, (T*)b->y_sum, (T*)b->y_last, (T*)nullptr, (T*)nullptr, batch_part2(b));
     HIP_TRY(hipGetLastError());
-    BATCH_TRY(batch_finalize(h, b, b->part, h->p.n, 1, slot, 0));
-    return batch_finalize(h, b, batch_part2(b), h->p.m, 1, slot, 1);
-}
-
-template <typename T> int batch_restart_t(pdlp_handle h, const pdlp_batch* b, int slot)
-{
-    if (b->W == 8) return batch_restart_w<T, 8>(h, b, slot);
-    if (b->W == 16) return batch_restart_w<T, 16>(h, b, slot);
-    return batch_restart_w<T, 32>(h, b, slot);
+    BATCH_TRY(batch_finalize(h, b, b->part, h->p.n, 1, slot, 0, b->Bp));
+    return batch_finalize(h, b, batch_part2(b), h->p.m, 1, slot, 1, b->Bp);
 }
 
 #undef BATCH_TRY
@@ -307,7 +224,7 @@ int pdlp_batch_iterate_from(pdlp_handle h, const pdlp_batch* b, int iters, int a
     const int rc = batch_check(h, b);
     if (rc != PDLP_OK) return rc;
     Range range("pdlp: batch iterations", h->stream);
-    return DISPATCH(h, batch_iterate_t, h, b, iters, adaptive, k0, k_start);
+    return batch_dispatch(h, b, adaptive, [&](auto t, auto w, auto a) { return batch_iterate_w<TYPE(t), VAL(w), VAL(a)>(h, b, iters, k0, k_start); });
 }
 
 int pdlp_batch_iterate(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0)
@@ -332,13 +249,15 @@ int pdlp_batch_admit(pdlp_handle h, const pdlp_batch* b, int count, const int32_
 int pdlp_batch_retire(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids, int which, int unscaled,
                       int slot, void* X_out, void* Y_out, void* rc_out, void* act_out, int N)
 {
-    if ((which != PDLP_CUR && which != PDLP_AVG && which != PDLP_PREV) || slot < 0 || slot > 2) return PDLP_ERR_INVALID;
-    const int r = batch_check(h, b);
+    int r = batch_check_pass(h, b, which, slot);
     if (r != PDLP_OK) return r;
     if (!cols || !ids || count < 1 || count > b->Bp || !X_out || !Y_out || N < 1) return PDLP_ERR_INVALID;
-    if (unscaled && (!batch_dcol(h) || !batch_drow(h))) return PDLP_ERR_STATE;
+    if ((r = batch_check_unscaled(h, unscaled)) != PDLP_OK) return r;
     Range range("pdlp: batch retirement", h->stream);
-    return DISPATCH(h, batch_retire_t, h, b, count, cols, ids, which, unscaled, slot, X_out, Y_out, rc_out, act_out, N);
+    const BSelList sel{count, cols, ids, b->Bp, N};
+    return batch_dispatch(h, b, unscaled, [&](auto t, auto w, auto u) {
+        return batch_report_w<TYPE(t), VAL(w), VAL(u)>(h, b, which, slot, sel, count, cols, ids, X_out, Y_out, rc_out, act_out, N);
+    });
 }
 
 int pdlp_batch_average(pdlp_handle h, const pdlp_batch* b, int adaptive)
@@ -350,22 +269,21 @@ int pdlp_batch_average(pdlp_handle h, const pdlp_batch* b, int adaptive)
 
 int pdlp_batch_kkt(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot)
 {
-    if ((which != PDLP_CUR && which != PDLP_AVG && which != PDLP_PREV) || slot < 0 || slot > 2) return PDLP_ERR_INVALID;
-    const int rc = batch_check(h, b);
-    if (rc != PDLP_OK) return rc;
-    if (unscaled && (!batch_dcol(h) || !batch_drow(h))) return PDLP_ERR_STATE;
+    int rc = batch_check_pass(h, b, which, slot);
+    if (rc != PDLP_OK || (rc = batch_check_unscaled(h, unscaled)) != PDLP_OK) return rc;
     Range range("pdlp: batch KKT pass", h->stream);
-    return DISPATCH(h, batch_kkt_t, h, b, which, unscaled, slot);
+    return batch_dispatch(h, b, unscaled, [&](auto t, auto w, auto u) { return batch_kkt_w<TYPE(t), VAL(w), VAL(u)>(h, b, which, slot); });
 }
 
 int pdlp_batch_report(pdlp_handle h, const pdlp_batch* b, int which, int unscaled, int slot, void* rc, void* act)
 {
-    if ((which != PDLP_CUR && which != PDLP_AVG && which != PDLP_PREV) || slot < 0 || slot > 2) return PDLP_ERR_INVALID;
-    const int r = batch_check(h, b);
-    if (r != PDLP_OK) return r;
-    if (unscaled && (!batch_dcol(h) || !batch_drow(h))) return PDLP_ERR_STATE;
+    int r = batch_check_pass(h, b, which, slot);
+    if (r != PDLP_OK || (r = batch_check_unscaled(h, unscaled)) != PDLP_OK) return r;
     Range range("pdlp: batch solution report", h->stream);
-    return DISPATCH(h, batch_report_t, h, b, which, unscaled, slot, rc, act);
+    const BSelAll sel{b->B};
+    return batch_dispatch(h, b, unscaled, [&](auto t, auto w, auto u) {
+        return batch_report_w<TYPE(t), VAL(w), VAL(u)>(h, b, which, slot, sel, b->B, nullptr, nullptr, nullptr, nullptr, rc, act, b->Bp);
+    });
 }
 
 int pdlp_batch_restart(pdlp_handle h, const pdlp_batch* b, int slot)
@@ -373,7 +291,7 @@ int pdlp_batch_restart(pdlp_handle h, const pdlp_batch* b, int slot)
     if (slot < 0 || slot > 2) return PDLP_ERR_INVALID;
     const int rc = batch_check(h, b);
     if (rc != PDLP_OK) return rc;
-    return DISPATCH(h, batch_restart_t, h, b, slot);
+    return batch_dispatch(h, b, [&](auto t, auto w) { return batch_restart_w<TYPE(t), VAL(w)>(h, b, slot); });
 }
 
 int pdlp_batch_attach_matrices(pdlp_handle h, int Bp, const void* K_valB, const void* KT_valB, const void* d_colB, const void* d_rowB)
@@ -398,5 +316,10 @@ int pdlp_batch_product(pdlp_handle h, const pdlp_batch* b, int transpose, const 
     const int rc = batch_check(h, b);
     if (rc != PDLP_OK) return rc;
     Range range("pdlp: batch product", h->stream);
-    return DISPATCH(h, batch_product_t, h, b, transpose, Vin, Vout);
+    return batch_dispatch(h, b, [&](auto t, auto w) {
+        using T = TYPE(t);
+        return batch_launch<T, VAL(w)>(h, b, transpose != 0, (const T*)Vin, BSelAll{b->B}, BStore<T>{(T*)Vout}, nullptr);
+    });
 }
+#undef TYPE
+#undef VAL

@@ -3,7 +3,8 @@
 // Part of pdlp_hip.hip (included inside its anonymous namespace; not a translation unit of its own).
 //
 // Populations are row-major V[row][Bp]: column b is LP b, Bp is B rounded up to a multiple of the group width W (8, 16, 32).
-// A launch has gridDim.y = Bp / W; group g serves columns [g W, (g + 1) W).  Inside a wave, W lanes work on a row
+// A launch has gridDim.y = Bp / W; group g serves columns [g W, (g + 1) W).  One product kernel, k_batch_mv<T, W, PERLP, Sel, Epi>:
+// a selector (BSelLive, BSelAll, BSelList) says which columns take part, an epilogue what happens to a row's sum.  Inside a wave, W lanes work on a row
 // (lane % W = the LP of the group), 64 / W rows at a time, each lane walking the row's items in CSR order -- the row walk of
 // k_csr_mv: an item reads one coalesced segment of W values of the gathered population.
 //
@@ -63,7 +64,7 @@ template <typename T, bool ADAPT> struct BPrimal {
     static constexpr int NA = 0;
     T* X; T* Xprev; T* Xbar; T* Xsum; const T* c; const T* l; const T* u; int cs, ls, us;
     const T* eta; const T* omega; const T* wpend;
-    __device__ void operator()(int j, size_t at, int b, T kty, double*) const
+    __device__ void operator()(int j, size_t at, int b, int, T kty, double*) const
     {
         const T xo = X[at];
         if (ADAPT) Xsum[at] = Xsum[at] + wpend[b] * xo;
@@ -84,7 +85,7 @@ template <typename T, bool ADAPT> struct BPrimal {
 template <typename T, bool ADAPT> struct BDual {
     static constexpr int NA = ADAPT ? 1 : 0;
     T* Y; T* Yprev; T* Ysum; T* DY; const T* q; int qs; const T* eta; const T* omega; const T* wpend; int ineq_end;
-    __device__ void operator()(int i, size_t at, int b, T kx, double* acc) const
+    __device__ void operator()(int i, size_t at, int b, int, T kx, double* acc) const
     {
         const T yo = Y[at];
         if (ADAPT) Ysum[at] = Ysum[at] + wpend[b] * yo;
@@ -107,7 +108,7 @@ template <typename T, bool ADAPT> struct BDual {
 template <typename T> struct BDen {
     static constexpr int NA = 2;
     const T* X; const T* Xprev;
-    __device__ void operator()(int j, size_t at, int, T kdy, double* acc) const
+    __device__ void operator()(int j, size_t at, int, int, T kdy, double* acc) const
     {
         const T dx = X[at] - Xprev[at];
         acc[0] += (double)kdy * (double)dx;
@@ -116,17 +117,19 @@ template <typename T> struct BDen {
 };
 
 // KKT, variable side (helpers.py:21-37,75-82,93-95): ||c - K'y - lam||^2, l_dual'max(lam,0), u_dual'min(lam,0), c'x -- the
-// arithmetic of KktDualEpi per column
+// arithmetic of KktDualEpi per column.  box(): g = c - K'y of row j and lam = project_lambda_box(g) (helpers.py:3-39) with the
+// bounds as the dual objective takes them (an infinite one counts 0), un-scaled on request -- the sums and the report's store
+template <typename T> struct BBox { T g, lam, ld, ud; };
 template <typename T, bool UNSCALE> struct BKktDual {
     static constexpr int NA = 4;
     const T* X; const T* c; const T* l; const T* u; int cs, ls, us; const T* dcol; int dper;
-    __device__ void operator()(int j, size_t at, int, T kty, double* acc) const
+    __device__ BBox<T> box(int j, size_t at, T kty) const
     {
-        T cj = BCOL(c, cs, j, at), lo = BCOL(l, ls, j, at), hi = BCOL(u, us, j, at), xj = X[at];
-        T g = cj - kty;
-        if (UNSCALE) {            // K_u'(D_row y) = (K_s'y)/D_col, c_u = c_s/D_col, l_u = l_s D_col, x_u = D_col x
+        T lo = BCOL(l, ls, j, at), hi = BCOL(u, us, j, at);
+        T g = BCOL(c, cs, j, at) - kty;
+        if (UNSCALE) {            // K_u'(D_row y) = (K_s'y)/D_col, l_u = l_s D_col
             const T d = BCOL(dcol, dper, j, at);
-            g = g / d; cj = cj / d; lo = lo * d; hi = hi * d; xj = xj * d;
+            g = g / d; lo = lo * d; hi = hi * d;
         }
         const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
         T lam;
@@ -134,11 +137,20 @@ template <typename T, bool UNSCALE> struct BKktDual {
         else if (ninf) lam = g < (T)0 ? g : (T)0;
         else if (pinf) lam = g > (T)0 ? g : (T)0;
         else lam = g;
-        const T ld = ninf ? (T)0 : lo, ud = pinf ? (T)0 : hi;
-        const T r = g - lam;
+        return {g, lam, ninf ? (T)0 : lo, pinf ? (T)0 : hi};
+    }
+    __device__ void operator()(int j, size_t at, int, int, T kty, double* acc) const
+    {
+        const BBox<T> v = box(j, at, kty);
+        T cj = BCOL(c, cs, j, at), xj = X[at];
+        if (UNSCALE) {            // c_u = c_s/D_col, x_u = D_col x
+            const T d = BCOL(dcol, dper, j, at);
+            cj = cj / d; xj = xj * d;
+        }
+        const T r = v.g - v.lam;
         acc[0] += (double)r * (double)r;
-        acc[1] += (double)ld * (double)(lam > (T)0 ? lam : (T)0);
-        acc[2] += (double)ud * (double)(lam < (T)0 ? lam : (T)0);
+        acc[1] += (double)v.ld * (double)(v.lam > (T)0 ? v.lam : (T)0);
+        acc[2] += (double)v.ud * (double)(v.lam < (T)0 ? v.lam : (T)0);
         acc[3] += (double)cj * (double)xj;
     }
 };
@@ -147,7 +159,7 @@ template <typename T, bool UNSCALE> struct BKktDual {
 template <typename T, bool UNSCALE> struct BKktPrimal {
     static constexpr int NA = 2;
     const T* Y; const T* q; int qs; const T* drow; int dper; int ineq_end;
-    __device__ void operator()(int i, size_t at, int, T kx, double* acc) const
+    __device__ void operator()(int i, size_t at, int, int, T kx, double* acc) const
     {
         T qi = BCOL(q, qs, i, at), yi = Y[at];
         T r = kx - qi;
@@ -161,40 +173,29 @@ template <typename T, bool UNSCALE> struct BKktPrimal {
     }
 };
 
-// Solution report per column (pdlp_batch_report): the KKT sums of BKktDual / BKktPrimal with the reduced cost lam resp. the row
-// activity K x stored beside them (null: not stored) -- UNSCALE: lam_u = lam_s / D_col, act_u = (K_s x_s) / D_row
-// lam = project_lambda_box(c - K'y) of row j (helpers.py:3-39), un-scaled on request: what the report stores
-template <typename T, bool UNSCALE>
-__device__ __forceinline__ T batch_lam(const BKktDual<T, UNSCALE>& kkt, int j, size_t at, T kty)
-{
-    T lo = BCOL(kkt.l, kkt.ls, j, at), hi = BCOL(kkt.u, kkt.us, j, at);
-    T g = BCOL(kkt.c, kkt.cs, j, at) - kty;
-    if (UNSCALE) {
-        const T d = BCOL(kkt.dcol, kkt.dper, j, at);
-        g = g / d; lo = lo * d; hi = hi * d;
-    }
-    const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
-    if (ninf && pinf) return (T)0;
-    if (ninf) return g < (T)0 ? g : (T)0;
-    if (pinf) return g > (T)0 ? g : (T)0;
-    return g;
-}
+// Solution report per column (pdlp_batch_report, pdlp_batch_retire): the KKT sums of BKktDual / BKktPrimal with the iterate of
+// the side, the reduced cost lam resp. the row activity K x stored beside them at [row][id] of the caller's [len][N] arrays (null:
+// not stored) -- UNSCALE: lam_u = lam_s / D_col, act_u = (K_s x_s) / D_row.  The report is N = Bp, id = b, no iterate.
 template <typename T, bool UNSCALE> struct BReportDual {
     static constexpr int NA = 4;
-    BKktDual<T, UNSCALE> kkt; T* RC;
-    __device__ void operator()(int j, size_t at, int b, T kty, double* acc) const
+    BKktDual<T, UNSCALE> kkt; T* Xout; T* RC; int N;
+    __device__ void operator()(int j, size_t at, int b, int id, T kty, double* acc) const
     {
-        if (RC) RC[at] = batch_lam<T, UNSCALE>(kkt, j, at, kty);
-        kkt(j, at, b, kty, acc);
+        const size_t to = (size_t)j * N + id;
+        if (Xout) Xout[to] = kkt.X[at];
+        if (RC) RC[to] = kkt.box(j, at, kty).lam;
+        kkt(j, at, b, id, kty, acc);
     }
 };
 template <typename T, bool UNSCALE> struct BReportPrimal {
     static constexpr int NA = 2;
-    BKktPrimal<T, UNSCALE> kkt; T* ACT;
-    __device__ void operator()(int i, size_t at, int b, T kx, double* acc) const
+    BKktPrimal<T, UNSCALE> kkt; T* Yout; T* ACT; int N;
+    __device__ void operator()(int i, size_t at, int b, int id, T kx, double* acc) const
     {
-        if (ACT) ACT[at] = UNSCALE ? kx / BCOL(kkt.drow, kkt.dper, i, at) : kx;
-        kkt(i, at, b, kx, acc);
+        const size_t to = (size_t)i * N + id;
+        if (Yout) Yout[to] = kkt.Y[at];
+        if (ACT) ACT[to] = UNSCALE ? kx / BCOL(kkt.drow, kkt.dper, i, at) : kx;
+        kkt(i, at, b, id, kx, acc);
     }
 };
 
@@ -202,14 +203,42 @@ template <typename T, bool UNSCALE> struct BReportPrimal {
 template <typename T> struct BStore {
     static constexpr int NA = 0;
     T* Vout;
-    __device__ void operator()(int, size_t at, int, T s, double*) const { Vout[at] = s; }
+    __device__ void operator()(int, size_t at, int, int, T s, double*) const { Vout[at] = s; }
+};
+
+// Which columns a launch serves.  pick(b, W, id) for the lane's column b: id >= 0 when b takes part -- the column of the
+// destination under which an epilogue files its stores (b itself unless listed) --, else -1; false when no column of b's group
+// takes part and the workgroup leaves at once (uniform over the workgroup).
+struct BSelLive {               // the live columns (every iteration, the KKT passes)
+    const int32_t* live;
+    __device__ bool pick(int b, int, int& id) const { id = live[b] ? b : -1; return true; }
+};
+struct BSelAll {                // every LP of the batch, b < B, frozen or not (the report is wanted when all are frozen; the plain
+    int B;                      // product); padding columns are neither read nor written
+    __device__ bool pick(int b, int, int& id) const { id = b < B ? b : -1; return true; }
+};
+struct BSelList {               // column cols[i] of the batch under column ids[i] of [len][N] arrays (retirement); an entry with a
+    int count; const int32_t* cols; const int32_t* ids; int Bp, N;       // column outside [0, Bp) or an id outside [0, N) is skipped
+    __device__ bool pick(int b, int W, int& id) const
+    {
+        bool any = false;
+        id = -1;
+        for (int i = 0; i < count; ++i) {
+            const int c = cols[i], v = ids[i];
+            if (c < 0 || c >= Bp || v < 0 || v >= N) continue;
+            any = any || c / W == (int)blockIdx.y;
+            if (c == b) id = v;
+        }
+        return any;             // a group without a listed column: its partials are never read (k_batch_finalize sums the listed)
+    }
 };
 
 // the row walk of a launch for column b of its group: the matrix (rows x cols, CSR) times column b of Vin[cols][Bp], the epilogue
 // per row.  PERLP: va is the population of values [nnz][Bp] and item p of this column is va[p * Bp + b]; else va[p] serves all
 template <typename T, int W, bool PERLP, class Epi>
 __device__ __forceinline__ void batch_rows(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                                           const T* __restrict__ va, const T* __restrict__ Vin, int Bp, int b, const Epi& epi, double* acc)
+                                           const T* __restrict__ va, const T* __restrict__ Vin, int Bp, int b, int id, const Epi& epi,
+                                           double* acc)
 {
     constexpr int RPW = 64 / W;
     const int sub = (threadIdx.x & 63) / W;
@@ -224,33 +253,22 @@ __device__ __forceinline__ void batch_rows(int rows, const int64_t* __restrict__
             } else {
                 for (int64_t p = rp[r]; p < e; ++p) s += va[p] * Vin[(size_t)ci[p] * Bp + b];
             }
-            epi(r, (size_t)r * Bp + b, b, s, acc);
+            epi(r, (size_t)r * Bp + b, b, id, s, acc);
         }
     }
 }
 
-// one product of the matrix (rows x cols, CSR) with a population Vin[cols][Bp], the epilogue per (row, live column)
-template <typename T, int W, bool PERLP, class Epi>
+// one product of the matrix (rows x cols, CSR) with a population Vin[cols][Bp], the epilogue per (row, column the selector picks)
+template <typename T, int W, bool PERLP, class Sel, class Epi>
 __global__ __launch_bounds__(BLOCK) void k_batch_mv(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                                                    const T* __restrict__ va, const T* __restrict__ Vin, int Bp,
-                                                    const int32_t* __restrict__ live, Epi epi, double* __restrict__ partials)
+                                                    const T* __restrict__ va, const T* __restrict__ Vin, int Bp, Sel sel, Epi epi,
+                                                    double* __restrict__ partials)
 {
     const int b = blockIdx.y * W + (threadIdx.x & 63) % W;
+    int id;
+    if (!sel.pick(b, W, id)) return;
     double acc[Epi::NA > 0 ? Epi::NA : 1] = {0.0};
-    if (live[b]) batch_rows<T, W, PERLP>(rows, rp, ci, va, Vin, Bp, b, epi, acc);
-    if (Epi::NA > 0) batch_store_partials<W, Epi::NA>(acc, partials, Bp);
-}
-
-// the same over every LP of the batch, b < B, frozen or not (the report is wanted when all are frozen); padding columns are
-// neither read nor written
-template <typename T, int W, bool PERLP, class Epi>
-__global__ __launch_bounds__(BLOCK) void k_batch_mv_all(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                                                        const T* __restrict__ va, const T* __restrict__ Vin, int Bp, int B, Epi epi,
-                                                        double* __restrict__ partials)
-{
-    const int b = blockIdx.y * W + (threadIdx.x & 63) % W;
-    double acc[Epi::NA > 0 ? Epi::NA : 1] = {0.0};
-    if (b < B) batch_rows<T, W, PERLP>(rows, rp, ci, va, Vin, Bp, b, epi, acc);
+    if (id >= 0) batch_rows<T, W, PERLP>(rows, rp, ci, va, Vin, Bp, b, id, epi, acc);
     if (Epi::NA > 0) batch_store_partials<W, Epi::NA>(acc, partials, Bp);
 }
 
@@ -271,11 +289,15 @@ __device__ __forceinline__ double batch_block_sum(const double* __restrict__ par
     return t;
 }
 
-// out[b * stride + off + a] = sum over blocks of partials[block][b][a], a < na: one workgroup per (b, a)
+// out[b * stride + off + a] = sum over blocks of partials[block][b][a], a < na: one workgroup per (i, a); b = i, or with a list
+// b = cols[i] (an entry that BSelList skips is skipped here)
 __global__ __launch_bounds__(BLOCK) void k_batch_finalize(const double* __restrict__ partials, int nblocks, int Bp, int na,
+                                                          const int32_t* __restrict__ cols, const int32_t* __restrict__ ids, int N,
                                                           double* __restrict__ out, int stride, int off)
 {
-    const int b = blockIdx.x / na, a = blockIdx.x - b * na;
+    const int i = blockIdx.x / na, a = blockIdx.x - i * na;
+    const int b = cols ? cols[i] : i;
+    if (cols && (b < 0 || b >= Bp || ids[i] < 0 || ids[i] >= N)) return;      // (uniform over the workgroup)
     const double s = batch_block_sum(partials, nblocks, Bp, na, b, a);
     if (threadIdx.x == 0) out[(size_t)b * stride + off + a] = s;
 }
@@ -390,7 +412,8 @@ __global__ __launch_bounds__(BLOCK) void k_batch_restart(int rows, int Bp, const
 }
 // ---- streaming a family through the columns (pdlp_batch_admit, pdlp_batch_retire) ----------------------------------------------
 // Both take a list: column cols[i] of the batch and column ids[i] of a [len][N] array of the caller (the feed, the results).
-// An entry with a column outside [0, Bp) or an id outside [0, N) is skipped.
+// An entry with a column outside [0, Bp) or an id outside [0, N) is skipped.  Retirement is the report (BReportDual / BReportPrimal)
+// under BSelList.
 
 // admission, one side (the n rows, the m rows or the nnz items): element (row, i), i fastest, so columns listed next to each other
 // are stored next to each other.  d0..d2 <- s0..s2: the per-LP vectors (or value populations) of this side, null = none;
@@ -425,69 +448,5 @@ __global__ __launch_bounds__(BLOCK) void k_batch_admit(int64_t rows, int count, 
             wpend[col] = (T)0;
         }
     }
-}
-
-// retirement: the report's epilogues with their stores redirected to column `id` of the result arrays ([len][N]); the iterate of
-// the side (x with K'y, y with K x) goes there as well.  The sums are BKktDual's / BKktPrimal's: the report's numbers.
-template <typename T, bool UNSCALE> struct BRetireDual {
-    static constexpr int NA = 4;
-    BKktDual<T, UNSCALE> kkt; T* Xout; T* RCout; int N; int id;
-    __device__ void operator()(int j, size_t at, int b, T kty, double* acc) const
-    {
-        const size_t to = (size_t)j * N + id;
-        Xout[to] = kkt.X[at];
-        if (RCout) RCout[to] = batch_lam<T, UNSCALE>(kkt, j, at, kty);
-        kkt(j, at, b, kty, acc);
-    }
-};
-template <typename T, bool UNSCALE> struct BRetirePrimal {
-    static constexpr int NA = 2;
-    BKktPrimal<T, UNSCALE> kkt; T* Yout; T* ACTout; int N; int id;
-    __device__ void operator()(int i, size_t at, int b, T kx, double* acc) const
-    {
-        const size_t to = (size_t)i * N + id;
-        Yout[to] = kkt.Y[at];
-        if (ACTout) ACTout[to] = UNSCALE ? kx / BCOL(kkt.drow, kkt.dper, i, at) : kx;
-        kkt(i, at, b, kx, acc);
-    }
-};
-
-// the row walk of k_batch_mv_all for the listed columns only; a group without a listed column leaves at once (its partials are
-// never read: k_batch_finalize_cols sums the listed columns)
-template <typename T, int W, bool PERLP, class Epi>
-__global__ __launch_bounds__(BLOCK) void k_batch_mv_cols(int rows, const int64_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                                                         const T* __restrict__ va, const T* __restrict__ Vin, int Bp, int count,
-                                                         const int32_t* __restrict__ cols, const int32_t* __restrict__ ids, int N,
-                                                         Epi epi, double* __restrict__ partials)
-{
-    const int b = blockIdx.y * W + (threadIdx.x & 63) % W;
-    int id = -1;
-    bool any = false;
-    for (int i = 0; i < count; ++i) {
-        const int c = cols[i], v = ids[i];
-        if (c < 0 || c >= Bp || v < 0 || v >= N) continue;
-        any = any || c / W == (int)blockIdx.y;
-        if (c == b) id = v;
-    }
-    if (!any) return;                           // (uniform over the workgroup)
-    double acc[Epi::NA > 0 ? Epi::NA : 1] = {0.0};
-    if (id >= 0) {
-        Epi e = epi;
-        e.id = id;
-        batch_rows<T, W, PERLP>(rows, rp, ci, va, Vin, Bp, b, e, acc);
-    }
-    if (Epi::NA > 0) batch_store_partials<W, Epi::NA>(acc, partials, Bp);
-}
-
-// k_batch_finalize for the listed columns: one workgroup per (i, a), the same tree, into out[cols[i]]
-__global__ __launch_bounds__(BLOCK) void k_batch_finalize_cols(const double* __restrict__ partials, int nblocks, int Bp, int na,
-                                                               const int32_t* __restrict__ cols, double* __restrict__ out, int stride,
-                                                               int off)
-{
-    const int i = blockIdx.x / na, a = blockIdx.x - i * na;
-    const int b = cols[i];
-    if (b < 0 || b >= Bp) return;               // (uniform over the workgroup)
-    const double s = batch_block_sum(partials, nblocks, Bp, na, b, a);
-    if (threadIdx.x == 0) out[(size_t)b * stride + off + a] = s;
 }
 #undef BCOL

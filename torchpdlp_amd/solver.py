@@ -236,12 +236,17 @@ class PdhgDriver:
         self.solved = bool(terminated(res, self.q_norm, self.c_norm, self.tol, t))
 
 
+def power_iteration_start(n: int, seed=None) -> torch.Tensor:
+    """the start vector of the power iteration, drawn on the host from ``seed`` (None: from the clock, as unpinned as the reference's)"""
+    g = torch.Generator().manual_seed(int(seed) if seed is not None else int(time.time_ns() % (2 ** 31)))
+    return torch.randn(n, generator=g, dtype=torch.float32)
+
+
 def estimate_sigma(eng: PdlpEngine, b0=None, power_iters=100, seed=None) -> float:
     """spectral_norm_estimate_torch (helpers.py:41-51); the reference's start vector is an unseeded
     torch.randn (quirk Q6) -- here ``b0`` or ``seed`` pins it, and every rank uses the same vector."""
     if b0 is None:
-        g = torch.Generator().manual_seed(int(seed) if seed is not None else int(time.time_ns() % (2 ** 31)))
-        b0 = torch.randn(eng.n, generator=g, dtype=torch.float32).to(eng.device)
+        b0 = power_iteration_start(eng.n, seed).to(eng.device)
         if eng.comm is not None:
             eng.comm.dist.broadcast(b0, 0, group=eng.comm.group)
             part = getattr(eng, "part", None)
