@@ -133,6 +133,63 @@ def test_sharded_step_equals_unsharded_cpu_gloo(world, balance):
         assert dict(ret) == {r: "ok" for r in range(world)}
 
 
+def _comm_cpu_worker(rank, world, port, ret):
+    from torchpdlp_amd.engine import Comm
+    _init(rank, world, port)
+    try:
+        comm = Comm()
+        assert (comm.rank, comm.world, comm.backend) == (rank, world, "gloo") and comm.coll_device(None) == "cpu"
+        # agree: the minimum of the ranks' flags, whatever truthy thing a rank hands in
+        assert comm.agree(1) == 1 and comm.agree(True) == 1 and comm.agree(0) == 0
+        assert comm.agree(rank == 0) == 0 and comm.agree(rank != 0) == 0 and comm.agree(rank + 1) == 1
+        # the three reductions and their one spelling
+        v = lambda: torch.tensor([rank + 1.0, -(rank + 1.0), 0.5], dtype=torch.float64)
+        t = v(); comm.all_reduce_sum(t); assert t.tolist() == [3.0, -3.0, 1.0]
+        t = v(); comm.all_reduce_max(t); assert t.tolist() == [2.0, -1.0, 0.5]
+        t = v(); comm.all_reduce_min(t); assert t.tolist() == [1.0, -2.0, 0.5]
+        t = v(); comm.all_reduce(t, dist.ReduceOp.MAX); assert t.tolist() == [2.0, -1.0, 0.5]
+        t = v(); comm.all_reduce_sum(t, dist.ReduceOp.MIN); assert t.tolist() == [1.0, -2.0, 0.5]     # (subclasses pass `op` on)
+        t = v(); w = comm.all_reduce_sum_async(t)
+        if w is not None:
+            w.wait()
+        assert t.tolist() == [3.0, -3.0, 1.0]
+        # gathers: whole blocks, then a piece of every rank's block; nothing outside the piece moves
+        B = 100
+        mine = lambda: torch.arange(B, dtype=torch.float32) + 1000 * (rank + 1)
+        want = torch.cat([torch.arange(B, dtype=torch.float32) + 1000 * (q + 1) for q in range(world)])
+        for gather in (comm.all_gather, comm.all_gather_async):
+            full = torch.zeros(world * B)
+            full[rank * B:(rank + 1) * B] = mine()
+            w = gather(full)
+            if w is not None:
+                w.wait()
+            assert torch.equal(full, want)
+        full = torch.full((world * B,), -1.0)
+        full[rank * B:(rank + 1) * B] = mine()
+        w = comm.all_gather_piece(full, 37, 64)
+        if w is not None:
+            w.wait()
+        for q in range(world):
+            blk = full[q * B:(q + 1) * B]
+            assert torch.equal(blk[37:64], want[q * B + 37:q * B + 64])
+            if q != rank:
+                assert bool((blk[:37] == -1).all()) and bool((blk[64:] == -1).all())
+        assert torch.equal(full[rank * B:(rank + 1) * B], mine())
+        assert comm.all_gather_piece(full, 64, 64) is None and comm.all_gather_piece(full, 70, 64) is None
+        ret[rank] = "ok"
+    finally:
+        dist.destroy_process_group()
+
+
+def test_comm_collectives_cpu_gloo():
+    """Comm on host tensors under gloo: agree is the minimum, the three reductions reduce, a piece fills every rank's [lo, hi)"""
+    port = _free_port()
+    with mp.Manager() as man:
+        ret = man.dict()
+        mp.spawn(_comm_cpu_worker, args=(2, port, ret), nprocs=2, join=True)
+        assert dict(ret) == {0: "ok", 1: "ok"}
+
+
 def _shard_gen_worker(rank, world, port, ret):
     from torchpdlp_amd.distributed import gen_lp_shard_arrays
     from torchpdlp_amd.engine import Comm

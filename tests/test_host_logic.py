@@ -2,6 +2,8 @@
 without a GPU: a stand-in engine with the PdlpEngine interface whose arithmetic is the CPU ORACLE, driven by the
 product's own ``run_pdlp`` / ``PdhgDriver``, against the reference's recorded runs (tests/golden/solve_trace.npz).
 This checks the control flow the HIP engine plugs into; the kernels themselves are checked on the GPU."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -350,3 +352,70 @@ def test_exportable_workspace_sizes():
     for n in (123, 2 ** 31 - 1, 2 ** 31, 3 * 2 ** 31 + 5, 7 * 2 ** 31):
         s = exportable_bytes(n)
         assert s >= n and s % (2 * MB) == 0 and not (s & 0x80000000)
+
+
+def test_shape_rule_of_the_tiled_kernel():
+    """which matrices are candidates for the tiled kernel, by PDLP_TILED: "0" never; "1" whenever there are rows; "auto" from
+    2^20 non-zeros, a gathered vector of 2^16 entries and 10 non-zeros per row on; "time" from the two sizes on"""
+    from torchpdlp_amd.engine_kernels import TILED_MIN_COLS, TILED_MIN_NNZ, TILED_MIN_PER_ROW, wants_tiles
+    assert (TILED_MIN_NNZ, TILED_MIN_COLS, TILED_MIN_PER_ROW) == (1 << 20, 1 << 16, 10)
+    NZ, CO = 1 << 20, 1 << 16
+    rows = NZ // 10                                   # (104857 rows: 10 * rows = 2^20 - 6 <= nnz)
+    table = [  # rows, cols, nnz                       "0"    "1"    "auto" "time"
+        ((rows, CO, NZ),                              (False, True,  True,  True)),
+        ((rows, CO, NZ - 1),                          (False, True,  False, False)),       # one non-zero short
+        ((rows, CO - 1, NZ),                          (False, True,  False, False)),       # one column short
+        ((rows, CO, 10 * rows),                       (False, True,  False, False)),       # (10 * rows < 2^20)
+        ((200_000, CO, 2_000_000),                    (False, True,  True,  True)),        # exactly 10 per row
+        ((200_000, CO, 1_999_999),                    (False, True,  False, True)),        # just under 10 per row: only "auto" minds
+        ((0, CO, NZ),                                 (False, False, False, False)),       # no rows: nobody tiles
+        ((0, 10, 0),                                  (False, False, False, False)),
+        ((5, 10, 7),                                  (False, True,  False, False)),       # "1" ignores the sizes
+    ]
+    for shape, want in table:
+        got = tuple(wants_tiles(mode, *shape) for mode in ("0", "1", "auto", "time"))
+        assert got == want, (shape, got, want)
+        # the conditions as the engine spelled them out before they had a name
+        for mode in ("0", "1", "auto", "time"):
+            r, c, z = shape
+            skip = mode == "0" or r == 0 or (mode != "1" and (c < (1 << 16) or z < (1 << 20))) or (mode == "auto" and z < 10 * r)
+            assert wants_tiles(mode, r, c, z) == (not skip)
+
+
+def test_knobs_from_env():
+    """the engine's PDLP_* switches: defaults, and every variable flips exactly its own field"""
+    from torchpdlp_amd.engine import knobs_from_env
+    d = knobs_from_env({})
+    assert d._asdict() == dict(running_kkt=True, kty_reuse=True, begin_inline=True, producer_pieces=True, graph=False, exchange_chunks=1,
+                               delta=True, lib_comm=False, tiled="auto", sorted="auto", tile_lw=None, tile_rpt=None, tile_groups=None,
+                               peer_trace=False)
+    cases = [
+        ({"PDLP_RUNNING_KKT": "0"}, dict(running_kkt=False)), ({"PDLP_RUNNING_KKT": "00"}, dict(running_kkt=False)),
+        ({"PDLP_RUNNING_KKT": "1"}, {}), ({"PDLP_RUNNING_KKT": ""}, {}),
+        ({"PDLP_NO_KTY_REUSE": ""}, dict(kty_reuse=False)), ({"PDLP_NO_KTY_REUSE": "0"}, dict(kty_reuse=False)),
+        ({"PDLP_BEGIN_INLINE": "0"}, dict(begin_inline=False)), ({"PDLP_BEGIN_INLINE": "1"}, {}),
+        ({"PDLP_PRODUCER_PIECES": "0"}, dict(producer_pieces=False)), ({"PDLP_PRODUCER_PIECES": "yes"}, {}),
+        ({"PDLP_GRAPH": "0"}, dict(graph=True)), ({"PDLP_GRAPH": ""}, dict(graph=True)),
+        ({"PDLP_EXCHANGE_CHUNKS": "3"}, dict(exchange_chunks=3)),
+        ({"PDLP_DELTA": "0"}, dict(delta=False)), ({"PDLP_DELTA": "00"}, {}), ({"PDLP_DELTA": "1"}, {}),
+        ({"PDLP_LIB_COMM": "1"}, dict(lib_comm=True)), ({"PDLP_LIB_COMM": "true"}, {}),
+        ({"PDLP_TILED": "time"}, dict(tiled="time")), ({"PDLP_SORTED": "0"}, dict(sorted="0")),
+        ({"PDLP_TILE_LW": "13"}, dict(tile_lw=13)), ({"PDLP_TILE_RPT": ""}, {}), ({"PDLP_TILE_RPT": "8"}, dict(tile_rpt=8)),
+        ({"PDLP_TILE_GROUPS": "2"}, dict(tile_groups=2)),
+        ({"PDLP_PEER_TRACE": "1"}, dict(peer_trace=True)), ({"PDLP_PEER_TRACE": ""}, {}),
+    ]
+    for env, flipped in cases:
+        assert knobs_from_env(env) == d._replace(**flipped), env
+    with pytest.raises(AttributeError):
+        d.delta = False                                # read once, then fixed
+
+
+def test_knobs_are_read_from_the_process_environment(monkeypatch):
+    from torchpdlp_amd.engine import knobs_from_env
+    for name in list(os.environ):
+        if name.startswith("PDLP_"):
+            monkeypatch.delenv(name)
+    assert knobs_from_env() == knobs_from_env({})
+    monkeypatch.setenv("PDLP_TILED", "0")
+    monkeypatch.setenv("PDLP_EXCHANGE_CHUNKS", "2")
+    assert knobs_from_env() == knobs_from_env({})._replace(tiled="0", exchange_chunks=2)

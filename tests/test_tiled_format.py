@@ -179,3 +179,70 @@ def test_abi_tile_ptr_is_relative_to_64_bit_row_block_bases():
     t2 = T.Tiles(6, 1, 16384, 2, 4, 10, 10, torch.zeros(1, dtype=torch.int32), torch.zeros(1), big, torch.zeros(1, dtype=torch.int32))
     rel2, base2 = t2.abi_tile_ptr()
     assert torch.equal(rel2, rel) and base2.tolist() == [1 << 33, (1 << 33) + 1024]
+
+
+# ---- column-sorted row blocks (the CSR kernel's format for clustered matrices) ----------------------------------------------------
+def _blocks(cols_per_block, seed=0):
+    """(first, colidx, val) of row blocks given as lists of column arrays, in CSR order"""
+    lens = [len(c) for c in cols_per_block]
+    first = torch.tensor(np.concatenate([[0], np.cumsum(lens)]), dtype=torch.int64)
+    ci = torch.from_numpy(np.concatenate([np.asarray(c, np.int64) for c in cols_per_block]).astype(np.int32))
+    va = torch.from_numpy(np.random.default_rng(seed).standard_normal(int(first[-1])))
+    return first, ci, va
+
+
+def test_sorted_row_blocks_format():
+    from torchpdlp_amd.tiled import SORTED_COL_BITS, SORTED_MAX_ITEMS, sorted_row_blocks
+    assert (SORTED_COL_BITS, SORTED_MAX_ITEMS) == (21, 2048)
+    rng = np.random.default_rng(7)
+    ncols, W = 3_000_000, 1 << 21
+    rows_of = lambda base, width, nrows, per: [np.sort(base + rng.choice(width, per, replace=False)) for _ in range(nrows)]
+    blocks = [
+        np.concatenate(rows_of(1_000_000, 50_000, 250, 6)),        # 1500 items: slots from 1024 on set bit 31 of the word
+        np.array([ncols - 1]),                                     # one item
+        np.zeros(0, np.int64),                                     # empty
+        np.concatenate([[0, W], 5 + rng.choice(1000, 8, replace=False)]),      # columns span 2^21: too wide
+        np.concatenate(rows_of(2_000_000, 100_000, 683, 3)),       # 2049 items: too long
+        500_000 + rng.permutation(4000)[:300],                     # one row whose columns are not in order
+    ]
+    assert [len(b) for b in blocks] == [1500, 1, 0, 10, 2049, 300]
+    first, ci, va = _blocks(blocks)
+    sidx, sval, cbase, n_sorted = sorted_row_blocks(first, ci, va, force=True)
+    assert sidx.dtype == torch.int32 and cbase.dtype == torch.int32 and sval.dtype == va.dtype
+    assert sidx.numel() == sval.numel() == va.numel() and cbase.numel() == 6
+    assert n_sorted == 3 and (cbase >= 0).tolist() == [True, True, False, False, False, True]
+    assert int(sidx.min()) < 0                                     # the int32 wrap did happen
+    word = sidx.long() & 0xFFFFFFFF                                # as the kernel reads it: unsigned
+    slot, low = word >> 21, word & (W - 1)
+    x = torch.from_numpy(rng.standard_normal(ncols))
+    prod = torch.full((va.numel(),), float("nan"), dtype=torch.float64)
+    for b in range(6):
+        f, e = int(first[b]), int(first[b + 1])
+        if int(cbase[b]) < 0:                                      # read in CSR order: the sorted arrays are not looked at
+            prod[f:e] = va[f:e] * x[ci[f:e].long()]
+            continue
+        s, col = slot[f:e], int(cbase[b]) + low[f:e]
+        assert sorted(s.tolist()) == list(range(e - f))            # a permutation of the block's CSR positions
+        assert torch.equal(col, ci[f:e].long()[s]) and torch.equal(sval[f:e], va[f:e][s])
+        assert bool((col[1:] >= col[:-1]).all())                   # non-decreasing in stored order
+        prod[f + s] = sval[f:e] * x[col]                           # the kernel's scatter to the row-order slot
+    assert torch.equal(prod, va * x[ci.long()])                    # so the rows are summed from the CSR kernel's own products
+    rowptr = np.concatenate([np.arange(0, 1500, 6), [1500], 1501 + np.arange(0, 10, 5), 1511 + np.arange(0, 2049, 3), [3560, 3860]])
+    sums = lambda p: np.add.reduceat(np.concatenate([p.numpy(), [0.0]]), rowptr[:-1])
+    assert np.array_equal(sums(prod), sums(va * x[ci.long()]))
+
+
+def test_sorted_row_blocks_only_when_the_columns_cluster():
+    """without ``force``: None unless at least half of all items sit in sortable blocks whose sorted neighbours are < 32 columns
+    apart on average (the rule returns None for a share < 0.5: exactly half still sorts)"""
+    from torchpdlp_amd.tiled import sorted_row_blocks
+    thin = lambda base, k: base + 32 * np.arange(k)                # mean gap exactly 32: not dense
+    dense = lambda base, k: base + 31 * np.arange(k)               # mean gap 31
+    assert sorted_row_blocks(*_blocks([thin(0, 10), thin(5000, 20), thin(90_000, 2)]), force=False) is None
+    assert sorted_row_blocks(*_blocks([thin(0, 10), thin(5000, 20)]), force=True) is not None
+    out = sorted_row_blocks(*_blocks([dense(0, 11), thin(5000, 10)]), force=False)                    # 11 of 21 items
+    assert out is not None and out[3] == 2 and out[2].tolist() == [0, 5000]
+    assert sorted_row_blocks(*_blocks([dense(0, 10), thin(5000, 10)]), force=False) is not None       # exactly half
+    assert sorted_row_blocks(*_blocks([dense(0, 10), thin(5000, 11)]), force=False) is None           # 10 of 21
+    # a block that cannot be sorted (too long) does not count as dense, however close its columns are
+    assert sorted_row_blocks(*_blocks([np.arange(2049), thin(5000, 10)]), force=False) is None

@@ -455,3 +455,48 @@ def emulate_spmv(t: Tiles, x: torch.Tensor) -> torch.Tensor:
         for i, r in enumerate(t.rem_rows.tolist()):
             y[r] += seg[rptr[i]:rptr[i + 1]].sum()
     return y[:t.nrows]
+
+
+# ---- column-sorted row blocks: the CSR kernel's format for matrices whose entries cluster ---------------------------------------
+# (``pdlp_attach_sorted``, include/pdlp_hip.h)  A clustered matrix (banded, block structured) has nearly empty tiles and stays with
+# the CSR kernel; a copy of its items, sorted by column inside every row block of that kernel's schedule, makes a wave's gathers
+# cover consecutive sorted items -- a few cache lines instead of one per lane.  Item = value + 4-byte
+# ``(slot << SORTED_COL_BITS) | (column - cbase[block])``, ``slot`` = the item's position in CSR order inside its block: the product
+# goes to ``lds[slot]`` and the rows are summed in CSR order, so the sums are the CSR kernel's bit for bit.  The word is stored as
+# int32: from slot 1024 on it has bit 31 set and wraps to a negative number (the kernel reads it unsigned).  A block that is empty,
+# longer than SORTED_MAX_ITEMS or wider than 2^SORTED_COL_BITS columns gets ``cbase = -1`` and is read in CSR order.
+SORTED_MAX_ITEMS = 2048      # items of one row block of the CSR schedule (pdlp_create); only a single longer row exceeds it
+SORTED_COL_BITS = 21         # bits of the word that hold column - cbase; the slot takes the upper 11
+SORTED_DENSE_GAP = 32.0      # mean distance of sorted neighbours below which they share 128-byte lines (32 float32 entries)
+SORTED_MIN_SHARE = 0.5       # without ``force``: the share of all items that must sit in such blocks
+
+
+def sorted_row_blocks(first: torch.Tensor, colidx: torch.Tensor, val: torch.Tensor, force: bool = True):
+    """The column-sorted copy of a CSR matrix's items for the row blocks that start at the item offsets ``first`` (nb + 1 of them,
+    the last one = the number of items).  Returns ``(sidx int32, sval, cbase int32 [nb], n_sorted)`` or, without ``force``, None
+    when sorting would not pay.  Pure torch, on the device of the arrays."""
+    nb, nnz = int(first.numel()) - 1, int(val.numel())
+    first = first.long()
+    lens = first[1:] - first[:-1]
+    dev = colidx.device
+    bid = torch.repeat_interleave(torch.arange(nb, device=dev), lens)
+    cl = colidx.long()
+    big = torch.iinfo(torch.int64).max
+    cmin = torch.full((nb,), big, dtype=torch.int64, device=dev).scatter_reduce_(0, bid, cl, "amin")
+    cmax = torch.full((nb,), -1, dtype=torch.int64, device=dev).scatter_reduce_(0, bid, cl, "amax")
+    ok = (lens > 0) & (lens <= SORTED_MAX_ITEMS) & (cmax - cmin < (1 << SORTED_COL_BITS))
+    if not force:
+        # Sorting pays when neighbouring sorted items share 128-byte lines.  A block whose columns are spread so thinly that sorted
+        # neighbours are >= 32 columns apart on average touches one line per item either way, and the sorted form then only costs:
+        # the extra dependent load of the block's base column and scattered LDS stores (neos3-shaped K': 24.5k -> 24.9k it/s
+        # in plain CSR order, profiles/r05_small_lp/).  Keep CSR order unless most items sit in blocks that do cluster.
+        gap = (cmax - cmin).double() / (lens - 1).clamp(min=1).double()
+        dense = ok & (gap < SORTED_DENSE_GAP)
+        if float(lens[dense].sum()) < SORTED_MIN_SHARE * nnz:
+            return None
+    order = torch.argsort((bid << 32) | cl, stable=True)        # by (block, column); blocks stay in place
+    slot = (torch.arange(nnz, device=dev) - first[bid])[order]
+    sidx = (slot << SORTED_COL_BITS) | (cl[order] - cmin[bid]).clamp_(0, (1 << SORTED_COL_BITS) - 1)
+    sidx = torch.where(sidx >= 2 ** 31, sidx - 2 ** 32, sidx).to(torch.int32)
+    cbase = torch.where(ok, cmin, torch.full_like(cmin, -1)).to(torch.int32)
+    return sidx, val[order].contiguous(), cbase, int(ok.sum())
