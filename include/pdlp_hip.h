@@ -550,6 +550,11 @@ int pdlp_probe_gather(void* scratch, int64_t scratch_bytes, int64_t table_entrie
 /* norm[i] = sqrt(max_p |val[p]|) over row i, replaced by 1 when < eps (:49-50 / :54-55) */
 int pdlp_csr_row_scale_factors(int dtype, int64_t rows, const int64_t* rowptr, const void* val, double eps,
                                void* norm, void* stream);
+/* Pock-Chambolle factors with alpha = 1 (no counterpart in the reference: PDLP's second scaling pass, run once after the Ruiz
+ * sweeps): norm[i] = sqrt(sum_p |val[p]|) over row i, 1 where the sum is 0 (an empty row, stored zeros only).  The sum is
+ * accumulated in double in an order that depends on the row alone (no atomics, not on the launch), then one sqrt and one rounding
+ * to `dtype`.  Column factors: the same call on the K' copy.  The divisions are pdlp_csr_div_rows / _div_cols. */
+int pdlp_csr_row_l1_factors(int dtype, int64_t rows, const int64_t* rowptr, const void* val, void* norm, void* stream);
 /* val[p] /= norm[row(p)]                      (:52 / :57 on the copy whose rows are being scaled) */
 int pdlp_csr_div_rows(int dtype, int64_t rows, const int64_t* rowptr, void* val, const void* norm, void* stream);
 /* val[p] /= norm_full[colidx[p]]              (the same scaling applied to the transposed copy)   */

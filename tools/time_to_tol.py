@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time-to-tolerance on the bench LP (BASELINE.json metric, second half): full restarted solve, prints the
-restart log every check.  python tools/time_to_tol.py [n] [nnz_per_row] [tol] [ruiz 0/1] [max_kkt] [f32|f64|mixed]
+restart log every check.  python tools/time_to_tol.py [n] [nnz_per_row] [tol] [ruiz 0/1] [max_kkt] [f32|f64|mixed] [--pock-chambolle]
+(--pock-chambolle, with ruiz 1: the Pock-Chambolle pass after the sweeps, solve_lp's pock_chambolle=True)
 (mixed: the generator's matrix entries are float32 numbers, so holding K in float32 under float64 vectors is the same LP
 as the f64 run; PDLP_DELTA=0 switches its delta mode off)"""
 import os, sys, time
@@ -9,10 +10,14 @@ import torch
 import torchpdlp_amd as tp
 from torchpdlp_amd.solver import run_pdlp
 
+pock = "--pock-chambolle" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--pock-chambolle"]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 tol = float(sys.argv[3]) if len(sys.argv) > 3 else 1e-4
 ruiz = len(sys.argv) > 4 and sys.argv[4] == "1"
+if pock and not ruiz:
+    sys.exit("--pock-chambolle needs ruiz = 1")
 max_kkt = int(sys.argv[5]) if len(sys.argv) > 5 else 40000
 prec = sys.argv[6] if len(sys.argv) > 6 else "f32"        # f32 | f64 | mixed (float32 matrix, float64 vectors, delta mode)
 dt = torch.float32 if prec == "f32" else torch.float64
@@ -40,7 +45,7 @@ c, q, l, u = lp.c, lp.q, lp.l, lp.u
 dcol = drow = None
 t_ruiz = 0.0
 if ruiz:
-    K, c, q, l, u, dp, t_ruiz = tp.ruiz_precondition(c, K, q, l, u, device=dev)
+    K, c, q, l, u, dp, t_ruiz = tp.ruiz_precondition(c, K, q, l, u, device=dev, pock_chambolle=pock)
     dcol, drow = dp[0], dp[1]
 if prec == "mixed" and ruiz:      # the scaled matrix is not float32-valued: iterate on its rounding, anchors from the float64 one
     Kh = K.to(dtype=torch.float32)
@@ -48,11 +53,11 @@ if prec == "mixed" and ruiz:      # the scaled matrix is not float32-valued: ite
 else:
     eng = tp.PdlpEngine.from_full(K, c, q, l, u, lp.m_ineq, d_col=dcol, d_row=drow, vec_dtype=torch.float64 if prec == "mixed" else None)
 torch.cuda.synchronize()
-print(f"setup {time.time()-t0:.1f}s (ruiz {t_ruiz:.2f}s) kernels={eng.kernels} precision={prec} delta={eng.delta}", flush=True)
+print(f"setup {time.time()-t0:.1f}s (ruiz{' + Pock-Chambolle' if pock else ''} {t_ruiz:.2f}s) kernels={eng.kernels} precision={prec} delta={eng.delta}", flush=True)
 trace = dict(kkt=[], omega=[], restarts=[])
 x, obj, it, nr, j, status, secs = run_pdlp(eng, max_kkt=max_kkt, tol=tol, verbose=True, precondition=ruiz, primal_update=True,
                                            adaptive=True, time_limit=time_limit, seed=0, power_iters=100, trace=trace)
-print(f"RESULT n={n} k={k} tol={tol} ruiz={ruiz} precision={prec}: status={status} obj={obj:.6f} iterations={it} restarts={nr} kkt_passes={j} "
+print(f"RESULT n={n} k={k} tol={tol} ruiz={ruiz} pock_chambolle={pock} precision={prec}: status={status} obj={obj:.6f} iterations={it} restarts={nr} kkt_passes={j} "
       f"solve_time={secs:.2f}s  ({it/secs:.1f} it/s incl. power iteration and checks)", flush=True)
 
 # ---- independent float64 check of the exit point (at 10M the only evaluator of the 1e-8 claim was the library's own

@@ -1,6 +1,6 @@
 """Batch driver with the reference's command line and CSV schema (``/root/reference/PDLP/main.py:11-174``):
 
-    python -m torchpdlp_amd --instance_path DIR [--tolerance 1e-4] [--output_path output] [--precondition]
+    python -m torchpdlp_amd --instance_path DIR [--tolerance 1e-4] [--output_path output] [--precondition [--pock_chambolle]]
         [--primal_weight_update] [--adaptive_stepsize] [--verbose] [--max_kkt N] [--time_limit S] [--solution_dir DIR]
 
 Solves every ``*.mps`` in the folder (sorted), continues past failures and writes ``solver_results.csv`` with the
@@ -29,6 +29,9 @@ def parse_args(argv=None):
     p.add_argument("--tolerance", type=float, default=1e-4)
     p.add_argument("--output_path", type=str, default="output")
     p.add_argument("--precondition", action="store_true")
+    p.add_argument("--pock_chambolle", action="store_true",
+                   help="with --precondition (not in the reference's CLI): one Pock-Chambolle pass (alpha = 1) after the Ruiz sweeps, "
+                        "PDLP's default pair of scalings")
     p.add_argument("--primal_weight_update", action="store_true")
     p.add_argument("--adaptive_stepsize", action="store_true")
     p.add_argument("--adaptive_retry", action="store_true",
@@ -135,7 +138,7 @@ def main(argv=None) -> int:
             results.append(row)
             continue
         try:
-            r = solve_lp(problem, tol=args.tolerance, precondition=args.precondition, primal_weight_update=args.primal_weight_update,
+            r = solve_lp(problem, tol=args.tolerance, precondition=args.precondition, pock_chambolle=args.pock_chambolle, primal_weight_update=args.primal_weight_update,
                          adaptive_stepsize=args.adaptive_stepsize, adaptive_retry=args.adaptive_retry, max_kkt=args.max_kkt, time_limit=args.time_limit,
                          verbose=args.verbose, dtype=dtype, seed=args.seed, fishnet=args.fishnet, comm=comm,
                          infeasibility_detect=args.infeasibility_detect, precision="mixed" if args.dtype == "mixed" else None,

@@ -148,6 +148,7 @@ SIGNATURES = {
     "pdlp_range_pop": (_I, [_P]),
     "pdlp_probe_gather": (_I, [_P, _I64, _I64, _I, _P, C.POINTER(_D)]),
     "pdlp_csr_row_scale_factors": (_I, [_I, _I64, _P, _P, _D, _P, _P]),
+    "pdlp_csr_row_l1_factors": (_I, [_I, _I64, _P, _P, _P, _P]),
     "pdlp_csr_div_rows": (_I, [_I, _I64, _P, _P, _P, _P]),
     "pdlp_csr_div_cols": (_I, [_I, _I64, _P, _P, _P, _P]),
     "pdlp_vec_muldiv": (_I, [_I, _I64, _P, _P, _I, _P]),

@@ -67,7 +67,7 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
              seed: Optional[int] = None, compat: bool = True, x_init=None, y_init=None, trace=None,
              fishnet: bool = False, comm=None, infeasibility_detect: bool = False, infeas_tol: float = 1e-4,
              precision: Optional[str] = None, adaptive_retry: bool = False, direct_exchange: bool = False,
-             report: bool = True) -> LPResult:
+             report: bool = True, pock_chambolle: bool = False) -> LPResult:
     """Solve ``min c'x, K[:m_ineq]x >= q[:m_ineq], K[m_ineq:]x = q[m_ineq:], l <= x <= u`` on the current HIP device.
 
     ``problem`` is an MPS path or ``(c, K, q, m_ineq, l, u)`` with ``K`` dense / COO / scipy-sparse / ``CsrPair``.
@@ -84,7 +84,12 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     ``direct_exchange`` (sharded solves, the ranks of ONE node, at most 8): the iterations run without collectives -- every half-step
     stores its block straight into the other ranks' memory over HIP IPC / xGMI (``PdlpEngine.enable_peer_exchange``, DESIGN.md
     section 5); connected and cross-checked against the collective-driven loop first, which stays in charge if anything differs.
+    ``pock_chambolle`` (only with ``precondition``; not in the reference): PDLP's second scaling step, one Pock-Chambolle pass with
+    alpha = 1 after the Ruiz sweeps -- rows and columns divided by the square roots of their 1-norms
+    (``precondition.pock_chambolle_pass``).  It composes into the same ``D_col``, ``D_row``, so the solution and
+    the report are un-scaled as with Ruiz alone.  Sharded solves do not have it yet and raise ``ValueError``.
     """
+    _check_pock_chambolle(pock_chambolle, precondition)
     device = resolve_device(device)
     if is_mixed(precision):
         dtype = torch.float64
@@ -96,13 +101,16 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
         from .engine import Comm
         cm = Comm() if comm is True else comm
         if cm.world > 1:
+            if pock_chambolle:
+                raise ValueError("pock_chambolle has no sharded form yet (the pass needs the sweeps' gather of the full factor "
+                                 "vectors): solve on one GPU, or with precondition alone")
             return _solve_lp_sharded(problem, cm, device, run, dtype=dtype, verbose=verbose, seed=seed, compat=compat, x_init=x_init,
                                      y_init=y_init, precision=precision, direct_exchange=direct_exchange, report=report)
     c, K, q, m_ineq, l, u = load_problem(problem, device, dtype, verbose, compat)
     time_used, data_precond = 0.0, None
     Ks, cs, qs, ls, us = K, c, q, l, u
     if precondition:                                                    # main.py:106-110
-        Ks, cs, qs, ls, us, data_precond, time_used = ruiz_precondition(c, K, q, l, u, device=device)
+        Ks, cs, qs, ls, us, data_precond, time_used = ruiz_precondition(c, K, q, l, u, device=device, pock_chambolle=pock_chambolle)
     if fishnet:                                                         # main.py:114-125 (k=32 points rounds, 2^5 points)
         import time as _time
         from .spectral_casting import spectral_cast
@@ -117,6 +125,12 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     if precondition:        # the reference returns the scaled iterate (quirk Q4); solve_lp un-scales: x = D_col x_s (pdhg.py:161)
         x = data_precond[0].view(-1, 1).to(x.dtype) * x
     return LPResult(x, obj, k, n, j, status, total, **report_fields(rep))
+
+
+def _check_pock_chambolle(pock_chambolle, precondition):
+    """the Pock-Chambolle pass is a second step of the preconditioner: asked for without it, it is an error (before any device work)"""
+    if pock_chambolle and not precondition:
+        raise ValueError("pock_chambolle=True needs precondition=True (the pass runs after the Ruiz sweeps)")
 
 
 def load_problem(problem, device, dtype, verbose=False, compat=True):
@@ -212,7 +226,8 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
                    max_kkt: int = 100_000, time_limit: float = 3600, restart_period: int = 40, dtype=torch.float32,
                    seed: Optional[int] = None, compat: bool = True, x_init=None, y_init=None, trace=None, verbose: bool = False,
                    group_width: Optional[int] = None, b0=None, report: bool = True, K_values=None, setup_times: Optional[dict] = None,
-                   slots: Optional[int] = None, schedule: Optional[dict] = None, **unsupported) -> BatchResult:
+                   slots: Optional[int] = None, schedule: Optional[dict] = None, pock_chambolle: bool = False,
+                   **unsupported) -> BatchResult:
     """Solve B LPs that share ``K`` (and ``m_ineq``) of ``problem`` and differ in ``c``, ``q``, ``l``, ``u`` in one batch.
 
     ``K_values`` ``(nnz, B)``: a constraint matrix per LP.  The LPs then share only the sparsity pattern of ``problem``'s K (its row
@@ -234,12 +249,14 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     omitted, 1-D (shared) or 2-D ``(len, B)`` (one column per LP; the 2-D arguments must agree on B).  Every LP runs through the
     reference's ``pdlp_algorithm`` with the same flags, its own step sizes, primal weight, restarts and KKT-pass count; ``max_kkt``
     applies per LP, ``time_limit`` to the whole batch.  With ``precondition`` one Ruiz equilibration of K serves every LP and each
-    column of c, q, l, u is scaled.  ``report`` (default on): the reduced costs, row activities, residuals and gaps of every LP
+    column of c, q, l, u is scaled; ``pock_chambolle`` (only with ``precondition``) adds ``solve_lp``'s Pock-Chambolle pass to it, once for
+    a shared K and per LP with ``K_values``.  ``report`` (default on): the reduced costs, row activities, residuals and gaps of every LP
     (``BatchResult``'s fields; ``res[i]`` passes them on).  ``trace``: a list that receives B dicts (``kkt``, ``omega``, ``restarts``).  Flags of
     ``solve_lp`` that have no batched form (sharding, fishnet, infeasibility detection, ``adaptive_retry``, the direct exchange,
     ``precision="mixed"``) raise ``ValueError``."""
     import numpy as np
     from .batch import batch_size, check_slots, pdlp_algorithm_batch
+    _check_pock_chambolle(pock_chambolle, precondition)
     for name, v in unsupported.items():
         if name == "precision":
             if v is not None:
@@ -284,7 +301,7 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     if precondition and K_values is not None:    # main.py:106-110 per LP: each matrix equilibrated on its own, each column scaled
         import time as _time
         from .precondition import ruiz_precondition_batch
-        KsV, KsTV, D_col, D_row, time_used = ruiz_precondition_batch(K, KsV, device=device)
+        KsV, KsTV, D_col, D_row, time_used = ruiz_precondition_batch(K, KsV, device=device, pock_chambolle=pock_chambolle)
         if setup_times is not None:
             setup_times["ruiz_seconds"] = time_used
         t0 = _time.time()
@@ -295,7 +312,7 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     elif precondition:                       # main.py:106-110: one equilibration of K, every column of c, q, l, u scaled
         import time as _time
         ones_n, ones_m = torch.ones(K.n, dtype=dtype, device=device), torch.ones(K.m, dtype=dtype, device=device)
-        Ks, _, _, _, _, data_precond, time_used = ruiz_precondition(ones_n, K, ones_m, ones_n, ones_n, device=device)
+        Ks, _, _, _, _, data_precond, time_used = ruiz_precondition(ones_n, K, ones_m, ones_n, ones_n, device=device, pock_chambolle=pock_chambolle)
         t0 = _time.time()
         D_col, D_row = data_precond[0].to(dtype).view(-1, 1), data_precond[1].to(dtype).view(-1, 1)
         sc = lambda v, D, op: (op(v.view(-1, 1), D).view(-1) if v.dim() == 1 else op(v, D.to(v.device)))

@@ -393,6 +393,26 @@ __global__ __launch_bounds__(BLOCK) void k_row_scale_factors(int64_t rows, const
     }
 }
 
+// Pock-Chambolle factors (alpha = 1): norm[i] = sqrt(sum_p |va[p]|) over row i, 1 where the sum is 0 (an empty row, or stored zeros
+// only).  k_row_scale_factors' lane layout; every lane adds its items p = rp[i] + lt, + 8, ... in double in that order, the eight
+// partial sums meet in a 3-step butterfly (a + b == b + a: all eight lanes hold the same bits), one sqrt, one rounding to T.
+// The order depends on the row alone, not on the grid.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_row_l1_factors(int64_t rows, const int64_t* __restrict__ rp, const T* __restrict__ va,
+                                                          T* __restrict__ norm)
+{
+    const int64_t g = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 3;
+    const int lt = threadIdx.x & 7;
+    const int64_t stride = ((int64_t)gridDim.x * BLOCK) >> 3;
+    for (int64_t i = g; i < ((rows + stride - 1) / stride) * stride; i += stride) {      // (uniform trip count: the shuffles need every lane)
+        double s = 0.0;
+        if (i < rows)
+            for (int64_t p = rp[i] + lt; p < rp[i + 1]; p += 8) s += fabs((double)va[p]);
+        for (int off = 4; off > 0; off >>= 1) s += shfl_xor_t(s, off);
+        if (i < rows && lt == 0) norm[i] = s > 0.0 ? (T)sqrt(s) : (T)1;
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_div_rows(int64_t rows, const int64_t* __restrict__ rp, T* __restrict__ va,
                                                     const T* __restrict__ norm)

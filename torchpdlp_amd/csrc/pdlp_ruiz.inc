@@ -17,6 +17,16 @@ int pdlp_csr_row_scale_factors(int dtype, int64_t rows, const int64_t* rowptr, c
     return PDLP_OK;
 }
 
+int pdlp_csr_row_l1_factors(int dtype, int64_t rows, const int64_t* rowptr, const void* val, void* norm, void* stream)
+{
+    if (rows < 0 || (dtype != PDLP_F32 && dtype != PDLP_F64) || (rows > 0 && (!rowptr || !norm))) return PDLP_ERR_INVALID;
+    if (rows == 0) return PDLP_OK;
+    const int g = grid_for(rows * 8);
+    WITH_T(dtype, hipLaunchKernelGGL(k_row_l1_factors<T>, dim3(g), dim3(BLOCK), 0, (hipStream_t)stream, rows, rowptr, (const T*)val, (T*)norm));
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
 int pdlp_csr_div_rows(int dtype, int64_t rows, const int64_t* rowptr, void* val, const void* norm, void* stream)
 {
     if (rows < 0 || (dtype != PDLP_F32 && dtype != PDLP_F64)) return PDLP_ERR_INVALID;

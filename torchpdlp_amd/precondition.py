@@ -1,10 +1,11 @@
-"""Ruiz equilibration on the two CSR copies of K, on the device.
+"""Ruiz equilibration, and PDLP's Pock-Chambolle pass after it, on the two CSR copies of K, on the device.
 
 Drop-in for ``ruiz_precondition`` (``/root/reference/PDLP/enhancements.py:4-71``), which is
 dense-only (``torch.linalg.norm(K, ord=inf, dim=...)`` does not take sparse input) and therefore
 cannot run at the benchmark sizes.  Each sweep is: row factors of K (sqrt of the row's max |.|,
 1 when < eps), divide K's rows and K''s columns by them; row factors of K' (= K's columns),
-divide K''s rows and K's columns by them.  The kernels are the ``pdlp_csr_*`` / ``pdlp_vec_*``
+divide K''s rows and K's columns by them.  ``pock_chambolle=True`` adds one pass by the square roots of the row and column
+1-norms (``pock_chambolle_pass``); the reference has none.  The kernels are the ``pdlp_csr_*`` / ``pdlp_vec_*``
 entry points of the C ABI.
 """
 from __future__ import annotations
@@ -64,6 +65,30 @@ def _sweeps(lib, code, stream, rows_K, rows_KT, K_blk, KT_blk, D_row, D_col, max
     return sweeps
 
 
+def pock_chambolle_pass(lib, code, stream, rows_K, rows_KT, K_blk, KT_blk, D_row, D_col):
+    """One Pock-Chambolle pass with alpha = 1 (PDLP's second scaling step) on the two CSR copies that ``_sweeps`` has equilibrated, in
+    place: ``r_i = sqrt(sum_j |Ks_ij|)``, ``c_j = sqrt(sum_i |Ks_ij|)`` (1 where the sum is 0), both of the SAME matrix -- before either
+    division, unlike a Ruiz sweep, whose column factors see the rows already divided -- then ``Ks <- diag(1/r) Ks diag(1/c)``,
+    ``D_row /= r``, ``D_col /= c``.  The column factors are the row factors of the K' copy.  One process only: ``K_blk`` / ``KT_blk``
+    are the whole copies (the sharded pass would need the sweeps' gather of the full factor vectors).  Returns ``(r, c)``."""
+    (rp, ci, va), (t_rp, t_ci, t_va) = K_blk, KT_blk
+    dev, dt = va.device, va.dtype
+    p = lambda t: t.data_ptr()
+    rn = torch.empty(rows_K, dtype=dt, device=dev)
+    cn = torch.empty(rows_KT, dtype=dt, device=dev)
+    nnz_K, nnz_KT = int(va.numel()), int(t_va.numel())
+    with N.trace_range("pdlp: Pock-Chambolle pass", torch.cuda.current_stream(dev)):
+        N.check(lib.pdlp_csr_row_l1_factors(code, rows_K, p(rp), p(va), p(rn), stream), "row 1-norm factors")
+        N.check(lib.pdlp_csr_row_l1_factors(code, rows_KT, p(t_rp), p(t_va), p(cn), stream), "col 1-norm factors")
+        N.check(lib.pdlp_vec_muldiv(code, rows_K, p(D_row), p(rn), 1, stream), "D_row /= r")
+        N.check(lib.pdlp_csr_div_rows(code, rows_K, p(rp), p(va), p(rn), stream), "K rows /= r")
+        N.check(lib.pdlp_csr_div_cols(code, nnz_KT, p(t_ci), p(t_va), p(rn), stream), "K' cols /= r")
+        N.check(lib.pdlp_vec_muldiv(code, rows_KT, p(D_col), p(cn), 1, stream), "D_col /= c")
+        N.check(lib.pdlp_csr_div_rows(code, rows_KT, p(t_rp), p(t_va), p(cn), stream), "K' rows /= c")
+        N.check(lib.pdlp_csr_div_cols(code, nnz_K, p(ci), p(va), p(cn), stream), "K cols /= c")
+    return rn, cn
+
+
 def ruiz_precondition_shard(shard: dict, comm, max_iter=20, eps=1e-6) -> dict:
     """Ruiz on a problem that only exists as shards: ``shard`` = this rank's keyword arguments of ``PdlpEngine`` as
     ``distributed.shard_arrays`` / ``gen_lp_shard_arrays`` build them (row block of K and of K' in the padded layout, local
@@ -104,11 +129,12 @@ def ruiz_precondition_shard(shard: dict, comm, max_iter=20, eps=1e-6) -> dict:
     return out
 
 
-def ruiz_precondition(c, K, q, l, u, device=None, max_iter=20, eps=1e-6):
+def ruiz_precondition(c, K, q, l, u, device=None, max_iter=20, eps=1e-6, pock_chambolle=False):
     """Returns ``(K_s, c_s, q_s, l_s, u_s, (D_col, D_row, K, c, q, l, u), time_used)`` like the reference.
 
     ``K_s`` is a ``CsrPair`` (both copies scaled consistently).  Reproduces the reference's early-exit
-    test, which looks at the ROW factors twice (quirk Q3, enhancements.py:60-61).
+    test, which looks at the ROW factors twice (quirk Q3, enhancements.py:60-61).  ``pock_chambolle`` (not in the reference): one
+    ``pock_chambolle_pass`` after the sweeps, composed into the same ``D_col``, ``D_row``.
     """
     t0 = time.time()
     lib = N.load()
@@ -128,6 +154,8 @@ def ruiz_precondition(c, K, q, l, u, device=None, max_iter=20, eps=1e-6):
     D_col = torch.ones(n, dtype=dt, device=dev)
     p = lambda t: t.data_ptr()
     _sweeps(lib, code, stream, m, n, (Ks.rowptr, Ks.colidx, Ks.val), (Ks.t_rowptr, Ks.t_colidx, Ks.t_val), D_row, D_col, max_iter, eps)
+    if pock_chambolle:
+        pock_chambolle_pass(lib, code, stream, m, n, (Ks.rowptr, Ks.colidx, Ks.val), (Ks.t_rowptr, Ks.t_colidx, Ks.t_val), D_row, D_col)
     N.check(lib.pdlp_vec_muldiv(code, n, p(c_s), p(D_col), 0, stream), "c *= D_col")      # :64
     N.check(lib.pdlp_vec_muldiv(code, m, p(q_s), p(D_row), 0, stream), "q *= D_row")      # :65
     N.check(lib.pdlp_vec_muldiv(code, n, p(l_s), p(D_col), 1, stream), "l /= D_col")      # :66
@@ -137,8 +165,8 @@ def ruiz_precondition(c, K, q, l, u, device=None, max_iter=20, eps=1e-6):
     return (Ks, col(c_s), col(q_s), col(l_s), col(u_s), (col(D_col), col(D_row), K, c, q, l, u), time.time() - t0)
 
 
-def ruiz_precondition_batch(K, K_values, device=None, max_iter=20, eps=1e-6):
-    """``ruiz_precondition`` of every LP's matrix of a batch over one pattern: ``K`` (a ``CsrPair``) gives the pattern, column b of
+def ruiz_precondition_batch(K, K_values, device=None, max_iter=20, eps=1e-6, pock_chambolle=False):
+    """``ruiz_precondition`` (with its ``pock_chambolle``) of every LP's matrix of a batch over one pattern: ``K`` (a ``CsrPair``) gives the pattern, column b of
     ``K_values`` ``(nnz, B)`` the values of LP b in its CSR order.  A host loop over the LPs (set-up, once per solve).  Returns
     ``(Ks_values (nnz, B), KsT_values (nnz, B) in the order of K', D_col (n, B), D_row (m, B), seconds)``."""
     t0 = time.time()
@@ -149,7 +177,7 @@ def ruiz_precondition_batch(K, K_values, device=None, max_iter=20, eps=1e-6):
     sv, stv, dc, dr = [], [], [], []
     for b in range(vals.shape[1]):
         Ks, _, _, _, _, dp, _ = ruiz_precondition(ones_n, Kp.with_values(vals[:, b].contiguous(), perm), ones_m, ones_n, ones_n,
-                                                  device=Kp.device, max_iter=max_iter, eps=eps)
+                                                  device=Kp.device, max_iter=max_iter, eps=eps, pock_chambolle=pock_chambolle)
         sv.append(Ks.val); stv.append(Ks.t_val); dc.append(dp[0].view(-1)); dr.append(dp[1].view(-1))
     st = lambda cols: torch.stack(cols, dim=1).contiguous()
     return st(sv), st(stv), st(dc), st(dr), time.time() - t0

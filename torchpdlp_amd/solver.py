@@ -327,7 +327,8 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
 
     ``K`` may be a dense / COO torch tensor (as the reference takes), a scipy sparse matrix or a
     ``CsrPair``.  With ``precondition=True`` pass the scaled problem and ``data_precond`` as returned by
-    ``ruiz_precondition`` (its first two entries ``D_col, D_row`` are what is used).  ``b0`` / ``sigma`` /
+    ``ruiz_precondition`` (its first two entries ``D_col, D_row`` are what is used; with ``pock_chambolle=True`` there
+    they hold the Pock-Chambolle pass as well, and nothing here changes).  ``b0`` / ``sigma`` /
     ``seed`` pin the power-iteration start the reference leaves to an unseeded RNG.
     Returns ``(x, prim_obj, k, n, j, status, total_time)``; ``x`` is an (n,1) tensor and, like the
     reference's (quirk Q4), the SCALED iterate when preconditioned.
