@@ -214,10 +214,8 @@ def test_ruiz_matches_solve_lp():
         assert np.linalg.norm(x - xo) <= 2e-2 * (1 + np.linalg.norm(xo)), b
         assert (y[:f.m_ineq] >= 0).all(), b
     # y = D_row y_s: the scaled dual of the same batch, multiplied out on the host
-    from torchpdlp_amd.precondition import ruiz_precondition
-    Kd = csr(f)
-    ones = lambda ln: torch.ones(ln, device=dev())
-    Ks, _, _, _, _, dp, _ = ruiz_precondition(ones(f.n), Kd, ones(f.m), ones(f.n), ones(f.n), device=dev())
+    Ks, scaling = tp.equilibrate_matrix(csr(f), device=dev())
+    dp = (scaling.d_col, scaling.d_row)
     Dc, Dr = dp[0].view(-1, 1), dp[1].view(-1, 1)
     Xs, Ys, *_ = pdlp_algorithm_batch(Ks, f.m_ineq, f.C.to(dev()) * Dc, f.Q.to(dev()) * Dr, f.L.to(dev()) / Dc, f.U.to(dev()) / Dc,
                                       dev(), precondition=True, data_precond=dp, seed=0)

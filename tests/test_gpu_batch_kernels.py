@@ -631,8 +631,7 @@ def test_golden_adaptive_step_columns(group):
 # ---------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def ruiz_lp(T, B):
-    """the golden ruiz.npz LP equilibrated by the library's ruiz_precondition in T: K_s, D_col, D_row and per-LP scaled vectors"""
-    from torchpdlp_amd.precondition import ruiz_precondition
+    """the golden ruiz.npz LP equilibrated by the library's equilibrate_matrix in T: K_s, D_col, D_row and per-LP scaled vectors"""
     z = np.load(os.path.join(GOLDEN, "ruiz.npz"))
     Kd = z["mixed_400x300/plain/it20/K"].astype(np.float64)
     m, n = Kd.shape
@@ -640,11 +639,10 @@ def ruiz_lp(T, B):
     Kc.sort_indices()
     t = lambda a, dt=TORCH[T]: torch.from_numpy(np.ascontiguousarray(a)).to(dtype=dt)
     Kp = tp.CsrPair(m, n, t(Kc.indptr, torch.int64), t(Kc.indices, torch.int32), t(Kc.data)).to(dev())
-    ones = lambda ln: torch.ones(ln, dtype=TORCH[T], device=dev())
-    Ks, _, _, _, _, dp, _ = ruiz_precondition(ones(n), Kp, ones(m), ones(n), ones(n), device=dev())
+    Ks, scaling = tp.equilibrate_matrix(Kp, device=dev())
     torch.cuda.synchronize()
     rp, ci, va = (v.cpu().numpy() for v in (Ks.rowptr, Ks.colidx, Ks.val))
-    dc, dr = dp[0].double().cpu().numpy().reshape(-1), dp[1].double().cpu().numpy().reshape(-1)
+    dc, dr = scaling.d_col.double().cpu().numpy(), scaling.d_row.double().cpu().numpy()
     assert not np.allclose(dc, 1) and not np.allclose(dr, 1)
     rng = np.random.default_rng(5)
     L, U = bounds_mix(n, rng, np.float64, B)

@@ -18,7 +18,7 @@ import torch
 import torchpdlp_amd as tp
 from torchpdlp_amd import _native as N
 from torchpdlp_amd.batch import BatchEngine, estimate_sigma_batch, pdlp_algorithm_batch
-from torchpdlp_amd.precondition import ruiz_precondition, ruiz_precondition_batch
+from torchpdlp_amd.precondition import equilibrate_matrix, ruiz_precondition_batch
 from tests import test_gpu_batch_kernels as bk
 from tests import test_gpu_report as rp_
 
@@ -100,8 +100,8 @@ def test_equal_columns_give_the_bits_of_the_shared_matrix_ruiz(dtype):
     B = 5
     f = family(B, seed=71, noise=0.0, dtype=dtype)
     K = csr(f)
-    ones = lambda ln: torch.ones(ln, dtype=dtype, device=dev())
-    Ks, _, _, _, _, dp, _ = ruiz_precondition(ones(f.n), K, ones(f.m), ones(f.n), ones(f.n), device=dev())
+    Ks, scaling = equilibrate_matrix(K, device=dev())
+    dp = (scaling.d_col, scaling.d_row)
     Dc, Dr = dp[0].view(-1, 1), dp[1].view(-1, 1)
     sc = (f.C.to(dev()) * Dc, f.Q.to(dev()) * Dr, f.L.to(dev()) / Dc, f.U.to(dev()) / Dc)
     kw = dict(sigma=norm2(f, Ks.val.cpu()), precondition=True, adaptive=True, primal_update=True, max_kkt=3000)
@@ -482,11 +482,10 @@ def test_ruiz_per_lp_equals_ruiz_of_each_matrix_and_solves_like_solve_lp():
     f = family(B, seed=40)
     K = csr(f)
     sv, stv, dc, dr, secs = ruiz_precondition_batch(K, f.vals.to(dev()))
-    ones = lambda ln: torch.ones(ln, device=dev())
     for b in range(B):
-        Ks, _, _, _, _, dp, _ = ruiz_precondition(ones(f.n), csr(f, f.vals[:, b]), ones(f.m), ones(f.n), ones(f.n), device=dev())
+        Ks, scaling = equilibrate_matrix(csr(f, f.vals[:, b]), device=dev())
         assert torch.equal(sv[:, b], Ks.val) and torch.equal(stv[:, b], Ks.t_val), b
-        assert torch.equal(dc[:, b], dp[0].view(-1)) and torch.equal(dr[:, b], dp[1].view(-1)), b
+        assert torch.equal(dc[:, b], scaling.d_col) and torch.equal(dr[:, b], scaling.d_row), b
     assert not torch.equal(dc[:, 0], dc[:, 1])
     prob = (f.C[:, 0], K, f.Q[:, 0], f.m_ineq, f.L[:, 0], f.U[:, 0])
     times = {}

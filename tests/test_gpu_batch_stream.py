@@ -200,9 +200,8 @@ def retire_engine(B, W, dtype=torch.float32, factors=None):
     f = family(B, seed=64, dtype=dtype, noise=0.2 if factors == "per_lp" else 0.0)
     K, kw = csr(f), {}
     if factors == "shared":
-        ones = lambda ln: torch.ones(ln, dtype=dtype, device=dev())
-        K, _, _, _, _, dp, _ = tp.ruiz_precondition(ones(f.n), K, ones(f.m), ones(f.n), ones(f.n), device=dev())
-        kw = dict(d_col=dp[0].view(-1), d_row=dp[1].view(-1))
+        K, scaling = tp.equilibrate_matrix(K, device=dev())
+        kw = dict(d_col=scaling.d_col, d_row=scaling.d_row)
     elif factors == "per_lp":
         sv, stv, dc, dr, _ = tp.ruiz_precondition_batch(K, f.vals.to(dev()))
         kw = dict(K_values=sv, KT_values=stv, d_col=dc, d_row=dr)

@@ -275,8 +275,7 @@ def test_batch_over_a_shared_matrix_equals_equal_columns_of_values(monkeypatch):
     last digits with or without the pass (3.0928428 against 3.0928426 on this matrix with Ruiz alone).  Everything else of the two
     calls is compared as it runs: the pass once against the pass per LP, the scaling of every column, the solve, the report."""
     f = bad_family(8, torch.float32)
-    ones = lambda ln: torch.ones(ln, device=dev())
-    Ks = tp.ruiz_precondition(ones(f.n), csr(f), ones(f.m), ones(f.n), ones(f.n), device=dev(), pock_chambolle=True)[0]
+    Ks = tp.equilibrate_matrix(csr(f), device=dev(), pock_chambolle=True)[0]
     dense = np.zeros((f.m, f.n))
     np.add.at(dense, (np.repeat(np.arange(f.m), 5), h64(Ks.colidx).astype(np.int64)), h64(Ks.val))
     sigma = float(np.linalg.norm(dense, 2))

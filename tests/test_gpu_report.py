@@ -359,13 +359,12 @@ def original_problem(problem, dtype):
 def termination_norms(P, precondition):
     """||q||, ||c|| as the solver's check_termination is given them (pdhg.py:19-20,173), in float64 numpy: of the original q and c,
     or -- with preconditioning, as in the reference -- of q * D_row and c * D_col (enhancements.py:64-65) with the Ruiz factors of
-    the original K.  The factors are a function of the original problem alone (K in fact); they come from ruiz_precondition, the
+    the original K.  The factors are a function of the original problem alone (K in fact); they come from equilibrate_matrix, the
     one place that defines them (its own tests: test_gpu_parity.py against tests/golden/ruiz.npz)."""
     if not precondition:
         return np.linalg.norm(P.q), np.linalg.norm(P.c)
-    c, K, q, _, l, u = P.orig
-    D_col, D_row = tp.ruiz_precondition(c, K, q, l, u, device=dev())[5][:2]
-    return np.linalg.norm(P.q * h64(D_row)), np.linalg.norm(P.c * h64(D_col))
+    scaling = tp.equilibrate_matrix(P.orig[1], device=dev())[1]
+    return np.linalg.norm(P.q * h64(scaling.d_row)), np.linalg.norm(P.c * h64(scaling.d_col))
 
 
 def check_result_against_the_original_problem(res, P, precondition, tol, u, worst=None):

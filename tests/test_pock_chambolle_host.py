@@ -20,7 +20,8 @@ def no_device_work(monkeypatch):
     def never(*a, **k):
         raise AssertionError("device work before the argument checks")
     monkeypatch.setattr(tp.batch, "BatchEngine", None)
-    for name in ("load_problem", "ruiz_precondition", "pdlp_algorithm", "_solve_lp_sharded", "resolve_device"):
+    for name in ("load_problem", "ruiz_precondition", "equilibrate_matrix", "ruiz_precondition_batch", "pdlp_algorithm",
+                 "_solve_lp_sharded", "resolve_device"):
         monkeypatch.setattr(tp.api, name, never)
 
 
@@ -44,7 +45,8 @@ def test_solve_lp_batch_needs_precondition_for_the_pass(monkeypatch):
 
 def test_sharded_solves_refuse_the_pass(monkeypatch):
     _, prob = small_problem()
-    for name in ("load_problem", "ruiz_precondition", "pdlp_algorithm", "_solve_lp_sharded"):
+    for name in ("load_problem", "ruiz_precondition", "equilibrate_matrix", "ruiz_precondition_batch", "pdlp_algorithm",
+                 "_solve_lp_sharded"):
         monkeypatch.setattr(tp.api, name, lambda *a, **k: (_ for _ in ()).throw(AssertionError("device work")))
     two_ranks = types.SimpleNamespace(world=2, rank=0)
     with pytest.raises(ValueError, match="pock_chambolle"):

@@ -13,7 +13,8 @@ from .solver import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, check_t
 from .ops import (KKT_error, adaptive_one_step_pdhg, compute_residuals_and_duality_gap,       # noqa: F401
                   detect_infeasibility, fixed_one_step_pdhg, primal_weight_update, project_lambda_box,
                   spectral_norm_estimate_torch)
-from .precondition import pock_chambolle_pass, ruiz_precondition, ruiz_precondition_batch                              # noqa: F401
+from .precondition import (Scaling, equilibrate, equilibrate_matrix, pock_chambolle_pass, ruiz_precondition,   # noqa: F401
+                           ruiz_precondition_batch)
 from .synthetic import LPFamily, SyntheticLP, gen_lp, gen_lp_family       # noqa: F401
 from .mps import mps_to_standard_form, parse_mps                         # noqa: F401
 from .api import BatchResult, LPResult, report_fields, solve_lp, solve_lp_batch   # noqa: F401

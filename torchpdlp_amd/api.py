@@ -4,13 +4,14 @@
 from __future__ import annotations
 
 import os
+import time as _time
 from dataclasses import dataclass
 from typing import Optional, Union
 
 import torch
 
 from .mps import mps_to_standard_form
-from .precondition import ruiz_precondition
+from .precondition import Scaling, equilibrate_matrix, ruiz_precondition, ruiz_precondition_batch
 from .solver import is_mixed, pdlp_algorithm, resolve_device
 from .sparse import CsrPair
 
@@ -112,7 +113,6 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     if precondition:                                                    # main.py:106-110
         Ks, cs, qs, ls, us, data_precond, time_used = ruiz_precondition(c, K, q, l, u, device=device, pock_chambolle=pock_chambolle)
     if fishnet:                                                         # main.py:114-125 (k=32 points rounds, 2^5 points)
-        import time as _time
         from .spectral_casting import spectral_cast
         t0 = _time.time()
         gen = None if seed is None else torch.Generator().manual_seed(int(seed))
@@ -123,7 +123,7 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
         Ks, m_ineq, cs, qs, ls, us, device, verbose=verbose, data_precond=data_precond, time_used=time_used, x_init=x_init,
         y_init=y_init, seed=seed, comm=comm, precision=precision, report=rep, **run)
     if precondition:        # the reference returns the scaled iterate (quirk Q4); solve_lp un-scales: x = D_col x_s (pdhg.py:161)
-        x = data_precond[0].view(-1, 1).to(x.dtype) * x
+        x = Scaling(*data_precond[:2]).unscale_x(x)
     return LPResult(x, obj, k, n, j, status, total, **report_fields(rep))
 
 
@@ -148,14 +148,12 @@ def _solve_lp_sharded(problem, comm, device, run, *, dtype, verbose, seed, compa
     """``solve_lp`` over the ranks of ``comm``: the problem is read (or taken) on the host by every rank, cut into blocks balanced
     by non-zeros, and only this rank's blocks go to its GPU; Ruiz (enhancements.py:4-71) runs on the shards, the solve is
     ``run_pdlp`` (with the options ``run``) on the sharded engine (pdhg.py:7-181), and every rank returns the full un-scaled solution."""
-    from .distributed import engine_from_shard, gather_report, gather_solution, shard_arrays
+    from .distributed import engine_from_shard, gather_report, gather_solution, shard_arrays, start_blocks
     from .solver import run_pdlp
-    from .sparse import as_vec
     verbose = verbose and comm.rank == 0
     c, K, q, m_ineq, l, u = load_problem(problem, None, dtype, verbose, compat)
     n, m = K.n, K.m
     sh = shard_arrays(K, c, q, l, u, m_ineq, comm.rank, comm.world, vec_dtype=dtype, balance="nnz")
-    part = sh["part"]
     one = lambda t: t.to(device) if isinstance(t, torch.Tensor) else t
     mv = lambda v: tuple(one(t) for t in v) if isinstance(v, tuple) else one(v)
     sh = {k: (v if k == "part" else mv(v)) for k, v in sh.items() if v is not None}
@@ -166,19 +164,14 @@ def _solve_lp_sharded(problem, comm, device, run, *, dtype, verbose, seed, compa
         on = eng.enable_peer_exchange()
         if verbose:
             print("direct exchange:", "on" if on else "declined", "--", "; ".join(eng.peer_log))
-    vdt = eng.dtype
-    if x_init is not None and y_init is not None:          # full vectors in (of the scaled problem when preconditioned, like the
-        x_init = part.pad_cols(as_vec(x_init, n, device, vdt))[eng.cols[0]:eng.cols[1]]    # one-GPU path and main.py:114-130);
-        y_init = part.pad_rows(as_vec(y_init, m, device, vdt))[eng.rows[0]:eng.rows[1]]    # this rank's blocks of the padded layout on
+    x_init, y_init = start_blocks(eng, x_init, y_init, n, m)     # (of the scaled problem when preconditioned, like main.py:114-130)
     rep = {} if report else None
     x, obj, k, nr, j, status, total = run_pdlp(eng, verbose=verbose, time_used=time_used, x_init=x_init, y_init=y_init,
                                                seed=0 if seed is None else seed, report=rep, **run)
     if run["precondition"]:
-        x = x * eng.d_col
+        x = Scaling(eng.d_col, eng.d_row).unscale_x(x)
     if rep is not None:
         rep = gather_report(eng, rep, n, m)
-        for key in ("y", "reduced_costs", "row_activity"):
-            rep[key] = rep[key].view(-1, 1)
     return LPResult(gather_solution(eng, x, n).view(-1, 1), obj, k, nr, j, status, total, **report_fields(rep))
 
 
@@ -298,27 +291,17 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     time_used, data_precond, Ks, KsV, KsTV = 0.0, None, K, None, None
     if K_values is not None:
         KsV = K_values.to(dtype) if streamed else K_values.to(device=device, dtype=dtype)
-    if precondition and K_values is not None:    # main.py:106-110 per LP: each matrix equilibrated on its own, each column scaled
-        import time as _time
-        from .precondition import ruiz_precondition_batch
-        KsV, KsTV, D_col, D_row, time_used = ruiz_precondition_batch(K, KsV, device=device, pock_chambolle=pock_chambolle)
-        if setup_times is not None:
-            setup_times["ruiz_seconds"] = time_used
+    if precondition:                         # main.py:106-110: K equilibrated once, or each LP's matrix on its own; every column scaled
+        if K_values is not None:
+            KsV, KsTV, D_col, D_row, secs = ruiz_precondition_batch(K, KsV, device=device, pock_chambolle=pock_chambolle)
+            scaling = Scaling(D_col, D_row, seconds=secs)
+            if setup_times is not None:
+                setup_times["ruiz_seconds"] = secs
+        else:
+            Ks, scaling = equilibrate_matrix(K, device, pock_chambolle=pock_chambolle)
         t0 = _time.time()
-        data_precond = (D_col, D_row)
-        wide = lambda v: v.view(-1, 1) if v.dim() == 1 else v
-        C_, Q, L, U = wide(C_) * D_col, wide(Q) * D_row, wide(L) / D_col, wide(U) / D_col
-        time_used += _time.time() - t0
-    elif precondition:                       # main.py:106-110: one equilibration of K, every column of c, q, l, u scaled
-        import time as _time
-        ones_n, ones_m = torch.ones(K.n, dtype=dtype, device=device), torch.ones(K.m, dtype=dtype, device=device)
-        Ks, _, _, _, _, data_precond, time_used = ruiz_precondition(ones_n, K, ones_m, ones_n, ones_n, device=device, pock_chambolle=pock_chambolle)
-        t0 = _time.time()
-        D_col, D_row = data_precond[0].to(dtype).view(-1, 1), data_precond[1].to(dtype).view(-1, 1)
-        sc = lambda v, D, op: (op(v.view(-1, 1), D).view(-1) if v.dim() == 1 else op(v, D.to(v.device)))
-        C_, Q = sc(C_, D_col, torch.mul), sc(Q, D_row, torch.mul)
-        L, U = sc(L, D_col, torch.div), sc(U, D_col, torch.div)
-        time_used += _time.time() - t0
+        C_, Q, L, U = scaling.scale(C_, Q, L, U)
+        time_used, data_precond = scaling.seconds + _time.time() - t0, (scaling.d_col, scaling.d_row)
     traces = None
     if trace is not None:
         traces = [dict(kkt=[], omega=[], restarts=[]) for _ in range(B)]
@@ -331,9 +314,7 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     if trace is not None:
         trace.extend(traces)
     if precondition:                         # x = D_col x_s, y = D_row y_s (pdhg.py:161-162), per LP with a matrix each
-        wide = lambda d: d.reshape(d.shape[0], -1).to(X.dtype)
-        X = wide(data_precond[0]) * X
-        Y = wide(data_precond[1]) * Y
+        X, Y = scaling.unscale_x(X), scaling.unscale_y(Y)
     fields = report_fields(rep)
     fields.pop("y", None)                    # (the report's y is the same un-scaled Y)
     return BatchResult(X, Y, np.asarray(obj), np.asarray(k), np.asarray(n), np.asarray(j), status, total, **fields)

@@ -223,6 +223,15 @@ def engine_from_shard(shard: dict, comm: Optional[Comm], precision: Optional[str
     return eng
 
 
+def start_blocks(eng: PdlpEngine, x_init, y_init, n_true: int, m_true: int):
+    """full start vectors (original order) -> this rank's blocks of them in the padded layout; passed on unless both are given"""
+    if x_init is None or y_init is None:
+        return x_init, y_init
+    x = eng.part.pad_cols(as_vec(x_init, n_true, eng.device, eng.dtype))
+    y = eng.part.pad_rows(as_vec(y_init, m_true, eng.device, eng.dtype))
+    return x[eng.cols[0]:eng.cols[1]], y[eng.rows[0]:eng.rows[1]]
+
+
 def gather_solution(eng: PdlpEngine, x_local: torch.Tensor, n_true: int) -> torch.Tensor:
     """the full primal vector in the ORIGINAL variable order on every rank (drops the padding)"""
     if eng.comm is None:
@@ -235,17 +244,18 @@ def gather_solution(eng: PdlpEngine, x_local: torch.Tensor, n_true: int) -> torc
 
 
 def gather_report(eng: PdlpEngine, rep: dict, n_true: int, m_true: int) -> dict:
-    """``PdlpEngine.report``'s dict with the full ``y``, ``reduced_costs`` and ``row_activity`` in the ORIGINAL order on every rank
-    (the scalars are already those of the whole problem)"""
-    if eng.comm is None:
-        return rep
+    """``PdlpEngine.report``'s dict as ``pdlp_algorithm`` and ``solve_lp`` hand it out -- also on ONE rank (``eng.comm`` None), where
+    nothing is gathered: ``y``, ``reduced_costs`` and ``row_activity`` as ``(len, 1)`` columns like the solution, and, sharded, the
+    full vectors in the ORIGINAL order on every rank (the scalars are already those of the whole problem)"""
     part = getattr(eng, "part", None)
 
     def full(v_local, ln, blk, ln_true, unpad):
+        if eng.comm is None:
+            return v_local.view(-1, 1)
         out = torch.empty(ln, dtype=v_local.dtype, device=v_local.device)
         out[blk[0]:blk[1]] = v_local
         eng.comm.all_gather(out)
-        return out[:ln_true] if part is None else unpad(out)
+        return (out[:ln_true] if part is None else unpad(out)).view(-1, 1)
     rep = dict(rep)
     rep["y"] = full(rep["y"], eng.m, eng.rows, m_true, part and part.unpad_rows)
     rep["row_activity"] = full(rep["row_activity"], eng.m, eng.rows, m_true, part and part.unpad_rows)

@@ -1,23 +1,23 @@
 """Ruiz equilibration, and PDLP's Pock-Chambolle pass after it, on the two CSR copies of K, on the device.
 
-Drop-in for ``ruiz_precondition`` (``/root/reference/PDLP/enhancements.py:4-71``), which is
-dense-only (``torch.linalg.norm(K, ord=inf, dim=...)`` does not take sparse input) and therefore
-cannot run at the benchmark sizes.  Each sweep is: row factors of K (sqrt of the row's max |.|,
-1 when < eps), divide K's rows and K''s columns by them; row factors of K' (= K's columns),
-divide K''s rows and K's columns by them.  ``pock_chambolle=True`` adds one pass by the square roots of the row and column
-1-norms (``pock_chambolle_pass``); the reference has none.  The kernels are the ``pdlp_csr_*`` / ``pdlp_vec_*``
-entry points of the C ABI.
+``equilibrate`` is the one body (``_sweeps``, then ``pock_chambolle_pass`` when asked; the ``pdlp_csr_*`` / ``pdlp_vec_*`` entry points
+of the C ABI) and ``Scaling`` what it returns: the factors, and the one place that scales vectors by them and un-scales iterates.
+``ruiz_precondition`` is the drop-in for the reference's (``/root/reference/PDLP/enhancements.py:4-71``), which is dense-only
+(``torch.linalg.norm(K, ord=inf, dim=...)`` does not take sparse input) and cannot run at the benchmark sizes.  Each sweep is: row
+factors of K (sqrt of the row's max |.|, 1 when < eps), divide K's rows and K''s columns by them; the same from K' for the columns.
+``pock_chambolle=True`` adds one pass by the square roots of the row and column 1-norms (``pock_chambolle_pass``; not in the reference).
 """
 from __future__ import annotations
 
 import ctypes as C
 import time
+from dataclasses import dataclass
 
 import torch
 
 from . import _native as N
 from .engine import _DT
-from .sparse import CsrPair, as_vec
+from .sparse import CsrPair, as_vec, resolve_device
 
 
 def _sweeps(lib, code, stream, rows_K, rows_KT, K_blk, KT_blk, D_row, D_col, max_iter, eps, comm=None, r0=0, c0=0):
@@ -89,95 +89,131 @@ def pock_chambolle_pass(lib, code, stream, rows_K, rows_KT, K_blk, KT_blk, D_row
     return rn, cn
 
 
+@dataclass
+class Scaling:
+    """The factors of an equilibration, ``Ks = diag(1/D_row) K diag(1/D_col)``, and the one place where vectors are scaled by them and
+    iterates un-scaled.  ``d_col`` / ``d_row``: ``(len,)`` for a shared matrix, ``(len, B)`` for a matrix per LP.  ``sweeps``: the
+    Ruiz sweeps run; ``seconds``: the equilibration alone (no vector is scaled in them)."""
+    d_col: torch.Tensor
+    d_row: torch.Tensor
+    sweeps: int = 0
+    seconds: float = 0.0
+
+    @staticmethod
+    def _by(v, D, op):
+        """``op(v, D)`` broadcast over the LPs: ``v`` None (passed on), ``(len,)``, ``(len, 1)`` or ``(len, B)``; a 2-D ``v`` on another
+        device (a streamed family's host-resident columns) is scaled where it lives.  One LP's vector on the HIP device goes through
+        ``pdlp_vec_muldiv`` on a clone: the same bits as torch's ``*`` and ``/``, whose kernels such a process then need not load"""
+        if v is None:
+            return None
+        if v.is_cuda and v.shape == D.shape and v.dim() == 1 and v.dtype == D.dtype and D.is_contiguous():
+            v = v.clone(memory_format=torch.contiguous_format)
+            stream = torch.cuda.current_stream(v.device).cuda_stream
+            N.check(N.load().pdlp_vec_muldiv(_DT[v.dtype], v.numel(), v.data_ptr(), D.data_ptr(), int(op is torch.div), stream), "v *|/= D")
+            return v
+        if v.dim() == 2:
+            D = D.to(v.device).reshape(D.shape[0], -1)
+        elif D.dim() == 2:
+            v = v.view(-1, 1)
+        return op(v, D)
+
+    def scale(self, c, q, l, u):
+        """``c * D_col, q * D_row, l / D_col, u / D_col`` as new tensors (enhancements.py:64-67)"""
+        by, mul, div = self._by, torch.mul, torch.div
+        return by(c, self.d_col, mul), by(q, self.d_row, mul), by(l, self.d_col, div), by(u, self.d_col, div)
+
+    def unscale_x(self, x):
+        """``D_col x`` (pdhg.py:161), the factors in the iterate's dtype"""
+        return self._by(x, self.d_col.to(x.dtype), torch.mul)
+
+    def unscale_y(self, y):
+        """``D_row y`` (pdhg.py:162)"""
+        return self._by(y, self.d_row.to(y.dtype), torch.mul)
+
+
+def equilibrate(K_blk, KT_blk, *, comm=None, r0=0, c0=0, max_iter=20, eps=1e-6, pock_chambolle=False) -> Scaling:
+    """The one body of every preconditioner here: the Ruiz sweeps (enhancements.py:45-62; early exit on the ROW factors twice, quirk
+    Q3) and, with ``pock_chambolle`` (not in the reference), one ``pock_chambolle_pass`` composed into the same factors, IN PLACE on
+    the CSR triples ``K_blk`` / ``KT_blk``: the whole copies of K and K', or with ``comm`` this rank's equal padded row blocks of them,
+    which start at row ``r0`` resp. ``c0``.  Returns the factors of these rows of K and of K' (local blocks when sharded)."""
+    t0 = time.time()
+    comm = comm if comm is not None and comm.world > 1 else None
+    if pock_chambolle and comm is not None:
+        raise ValueError("pock_chambolle has no sharded form yet (the pass needs the sweeps' gather of the full factor vectors)")
+    dev, dt = K_blk[2].device, K_blk[2].dtype
+    if dev.type != "cuda":
+        raise N.PdlpError("the equilibration runs on the HIP device (there is no CPU fallback)")
+    lib, code = N.load(), _DT[dt]
+    stream = torch.cuda.current_stream(dev)
+    rows_K, rows_KT = int(K_blk[0].numel()) - 1, int(KT_blk[0].numel()) - 1
+    D_row = torch.ones(rows_K, dtype=dt, device=dev)
+    D_col = torch.ones(rows_KT, dtype=dt, device=dev)
+    sweeps = _sweeps(lib, code, stream.cuda_stream, rows_K, rows_KT, K_blk, KT_blk, D_row, D_col, max_iter, eps, comm, r0, c0)
+    if pock_chambolle:
+        pock_chambolle_pass(lib, code, stream.cuda_stream, rows_K, rows_KT, K_blk, KT_blk, D_row, D_col)
+    stream.synchronize()
+    return Scaling(D_col, D_row, sweeps, time.time() - t0)
+
+
+def equilibrate_matrix(K, device=None, max_iter=20, eps=1e-6, pock_chambolle=False):
+    """``(Ks, Scaling)`` of a matrix alone: ``Ks`` a new ``CsrPair`` with both copies scaled consistently; the caller's ``K`` (dense /
+    COO / scipy sparse / ``CsrPair``) is left as it is.  ``device`` None: the current HIP device."""
+    Ks = CsrPair.from_any(K, device=resolve_device(device)).clone()
+    return Ks, equilibrate((Ks.rowptr, Ks.colidx, Ks.val), (Ks.t_rowptr, Ks.t_colidx, Ks.t_val), max_iter=max_iter, eps=eps,
+                           pock_chambolle=pock_chambolle)
+
+
 def ruiz_precondition_shard(shard: dict, comm, max_iter=20, eps=1e-6) -> dict:
     """Ruiz on a problem that only exists as shards: ``shard`` = this rank's keyword arguments of ``PdlpEngine`` as
     ``distributed.shard_arrays`` / ``gen_lp_shard_arrays`` build them (row block of K and of K' in the padded layout, local
     ``c, q, l, u``).  Returns a new dict with the scaled blocks and vectors plus ``d_col`` / ``d_row`` (local blocks) -- no rank
     ever holds a full matrix.  ``shard["ruiz_seconds"]`` / ``["ruiz_sweeps"]`` record the cost.  (enhancements.py:4-71)"""
     t0 = time.time()
-    lib = N.load()
     (rp, ci, va), (t_rp, t_ci, t_va) = shard["K_rows"], shard["KT_rows"]
     dev, dt = va.device, va.dtype
     if dev.type != "cuda":
         raise N.PdlpError("ruiz_precondition_shard runs on the HIP device (there is no CPU fallback)")
-    code = _DT[dt]
-    stream = torch.cuda.current_stream(dev).cuda_stream
     (r0, r1), (c0, c1) = shard["rows"], shard["cols"]
     ml, nl = r1 - r0, c1 - c0
-    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
-    i64 = lambda t: t.to(device=dev, dtype=torch.int64).contiguous()
-    K_blk = (i64(rp), i32(ci), va.clone())
-    KT_blk = (i64(t_rp), i32(t_ci), t_va.to(dev).clone())
-    vec = lambda v, ln: as_vec(v, ln, dev, dt).clone()
-    c_s, q_s, l_s, u_s = vec(shard["c"], nl), vec(shard["q"], ml), vec(shard["l"], nl), vec(shard["u"], nl)
-    D_row = torch.ones(ml, dtype=dt, device=dev)
-    D_col = torch.ones(nl, dtype=dt, device=dev)
     world = 1 if comm is None else comm.world
     if ml * world != shard["m"] or nl * world != shard["n"]:
         raise ValueError("sharded Ruiz needs the equal, padded blocks of torchpdlp_amd/distributed.py")
-    sweeps = _sweeps(lib, code, stream, ml, nl, K_blk, KT_blk, D_row, D_col, max_iter, eps,
-                     comm if world > 1 else None, r0, c0)
-    p = lambda t: t.data_ptr()
-    N.check(lib.pdlp_vec_muldiv(code, nl, p(c_s), p(D_col), 0, stream), "c *= D_col")      # :64
-    N.check(lib.pdlp_vec_muldiv(code, ml, p(q_s), p(D_row), 0, stream), "q *= D_row")      # :65
-    N.check(lib.pdlp_vec_muldiv(code, nl, p(l_s), p(D_col), 1, stream), "l /= D_col")      # :66
-    N.check(lib.pdlp_vec_muldiv(code, nl, p(u_s), p(D_col), 1, stream), "u /= D_col")      # :67
+    idx = lambda t, it: t.to(device=dev, dtype=it).contiguous()
+    K_blk = (idx(rp, torch.int64), idx(ci, torch.int32), va.clone())
+    KT_blk = (idx(t_rp, torch.int64), idx(t_ci, torch.int32), t_va.to(dev).clone())
+    scaling = equilibrate(K_blk, KT_blk, comm=comm, r0=r0, c0=c0, max_iter=max_iter, eps=eps)
+    vec = lambda v, ln: as_vec(v, ln, dev, dt)
+    c_s, q_s, l_s, u_s = scaling.scale(vec(shard["c"], nl), vec(shard["q"], ml), vec(shard["l"], nl), vec(shard["u"], nl))
     torch.cuda.current_stream(dev).synchronize()
     out = dict(shard)
-    out.update(K_rows=K_blk, KT_rows=KT_blk, c=c_s, q=q_s, l=l_s, u=u_s, d_col=D_col, d_row=D_row,
-               ruiz_seconds=time.time() - t0, ruiz_sweeps=sweeps)
+    out.update(K_rows=K_blk, KT_rows=KT_blk, c=c_s, q=q_s, l=l_s, u=u_s, d_col=scaling.d_col, d_row=scaling.d_row,
+               ruiz_seconds=time.time() - t0, ruiz_sweeps=scaling.sweeps)
     return out
 
 
 def ruiz_precondition(c, K, q, l, u, device=None, max_iter=20, eps=1e-6, pock_chambolle=False):
-    """Returns ``(K_s, c_s, q_s, l_s, u_s, (D_col, D_row, K, c, q, l, u), time_used)`` like the reference.
-
-    ``K_s`` is a ``CsrPair`` (both copies scaled consistently).  Reproduces the reference's early-exit
-    test, which looks at the ROW factors twice (quirk Q3, enhancements.py:60-61).  ``pock_chambolle`` (not in the reference): one
-    ``pock_chambolle_pass`` after the sweeps, composed into the same ``D_col``, ``D_row``.
-    """
+    """Returns ``(K_s, c_s, q_s, l_s, u_s, (D_col, D_row, K, c, q, l, u), time_used)`` like the reference: ``equilibrate_matrix``
+    (``K_s`` a ``CsrPair``) and ``Scaling.scale`` of the four vectors, as ``(len, 1)`` columns."""
     t0 = time.time()
-    lib = N.load()
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    Kp = CsrPair.from_any(K, device=device)
-    dev, dt = Kp.device, Kp.dtype
-    if dev.type != "cuda":
-        raise N.PdlpError("ruiz_precondition runs on the HIP device (there is no CPU fallback)")
-    code = _DT[dt]
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    Ks = Kp.clone()
-    m, n, nnz = Ks.m, Ks.n, int(Ks.val.numel())
-    vec = lambda v, ln: as_vec(v, ln, dev, dt).clone()
-    c_s, q_s, l_s, u_s = vec(c, n), vec(q, m), vec(l, n), vec(u, n)
-    D_row = torch.ones(m, dtype=dt, device=dev)
-    D_col = torch.ones(n, dtype=dt, device=dev)
-    p = lambda t: t.data_ptr()
-    _sweeps(lib, code, stream, m, n, (Ks.rowptr, Ks.colidx, Ks.val), (Ks.t_rowptr, Ks.t_colidx, Ks.t_val), D_row, D_col, max_iter, eps)
-    if pock_chambolle:
-        pock_chambolle_pass(lib, code, stream, m, n, (Ks.rowptr, Ks.colidx, Ks.val), (Ks.t_rowptr, Ks.t_colidx, Ks.t_val), D_row, D_col)
-    N.check(lib.pdlp_vec_muldiv(code, n, p(c_s), p(D_col), 0, stream), "c *= D_col")      # :64
-    N.check(lib.pdlp_vec_muldiv(code, m, p(q_s), p(D_row), 0, stream), "q *= D_row")      # :65
-    N.check(lib.pdlp_vec_muldiv(code, n, p(l_s), p(D_col), 1, stream), "l /= D_col")      # :66
-    N.check(lib.pdlp_vec_muldiv(code, n, p(u_s), p(D_col), 1, stream), "u /= D_col")      # :67
-    torch.cuda.current_stream(dev).synchronize()
+    Ks, scaling = equilibrate_matrix(K, device, max_iter, eps, pock_chambolle)
+    vec = lambda v, ln: as_vec(v, ln, Ks.device, Ks.dtype)
+    scaled = scaling.scale(vec(c, Ks.n), vec(q, Ks.m), vec(l, Ks.n), vec(u, Ks.n))
+    torch.cuda.current_stream(Ks.device).synchronize()
     col = lambda v: v.view(-1, 1)
-    return (Ks, col(c_s), col(q_s), col(l_s), col(u_s), (col(D_col), col(D_row), K, c, q, l, u), time.time() - t0)
+    return (Ks, *map(col, scaled), (col(scaling.d_col), col(scaling.d_row), K, c, q, l, u), time.time() - t0)
 
 
 def ruiz_precondition_batch(K, K_values, device=None, max_iter=20, eps=1e-6, pock_chambolle=False):
-    """``ruiz_precondition`` (with its ``pock_chambolle``) of every LP's matrix of a batch over one pattern: ``K`` (a ``CsrPair``) gives the pattern, column b of
+    """``equilibrate_matrix`` of every LP's matrix of a batch over one pattern: ``K`` (a ``CsrPair``) gives the pattern, column b of
     ``K_values`` ``(nnz, B)`` the values of LP b in its CSR order.  A host loop over the LPs (set-up, once per solve).  Returns
     ``(Ks_values (nnz, B), KsT_values (nnz, B) in the order of K', D_col (n, B), D_row (m, B), seconds)``."""
     t0 = time.time()
     Kp = CsrPair.from_any(K, device=device)
     vals = K_values.to(device=Kp.device, dtype=Kp.dtype)
     perm = Kp.transpose_perm()
-    ones_n, ones_m = torch.ones(Kp.n, dtype=Kp.dtype, device=Kp.device), torch.ones(Kp.m, dtype=Kp.dtype, device=Kp.device)
     sv, stv, dc, dr = [], [], [], []
     for b in range(vals.shape[1]):
-        Ks, _, _, _, _, dp, _ = ruiz_precondition(ones_n, Kp.with_values(vals[:, b].contiguous(), perm), ones_m, ones_n, ones_n,
-                                                  device=Kp.device, max_iter=max_iter, eps=eps, pock_chambolle=pock_chambolle)
-        sv.append(Ks.val); stv.append(Ks.t_val); dc.append(dp[0].view(-1)); dr.append(dp[1].view(-1))
+        Ks, scaling = equilibrate_matrix(Kp.with_values(vals[:, b].contiguous(), perm), Kp.device, max_iter, eps, pock_chambolle)
+        sv.append(Ks.val); stv.append(Ks.t_val); dc.append(scaling.d_col); dr.append(scaling.d_row)
     st = lambda cols: torch.stack(cols, dim=1).contiguous()
     return st(sv), st(stv), st(dc), st(dr), time.time() - t0

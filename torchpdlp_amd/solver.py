@@ -17,7 +17,7 @@ from . import _native as N
 from .engine import Comm, PdlpEngine
 from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, kkt_error, np_type, previous_kkt_matters,   # noqa: F401
                     primal_weight, restart_decision, start_eta, start_omega, terminated)
-from .sparse import CsrPair, as_vec
+from .sparse import CsrPair, as_vec, resolve_device     # noqa: F401  (resolve_device: api.py and callers take it from here)
 
 
 def check_termination(primal_residual, dual_residual, duality_gap, prim_obj, adjusted_dual, q_norm, c_norm, tol):
@@ -28,14 +28,6 @@ def check_termination(primal_residual, dual_residual, duality_gap, prim_obj, adj
 
 kkt_from_residuals = kkt_error
 primal_weight_from_distances = primal_weight
-
-
-def resolve_device(device=None) -> torch.device:
-    """the device of a solve: the current HIP device unless given, always with its index"""
-    device = torch.device("cuda") if device is None else torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
 
 
 def precond_factors(precondition, data_precond):
@@ -353,6 +345,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     full problem and the same ``seed``/``b0``; each keeps its row blocks of K and K', the iterations exchange
     ``xbar`` and ``y`` over RCCL, and every rank returns the full solution.
     """
+    from .distributed import gather_report, gather_solution, shard_engine, start_blocks
     device = resolve_device(device)
     Kp = CsrPair.from_any(K, device=device)
     dtype = Kp.dtype
@@ -372,14 +365,10 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
         comm = Comm()
     sharded = comm is not None and comm.world > 1
     if sharded:
-        from .distributed import gather_solution, shard_engine
         if seed is None and b0 is None and sigma is None:
             seed = 0                                   # the ranks must draw the same power-iteration start
         eng = shard_engine(Kp, c, q, l, u, m_ineq, comm, d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, exact=exact_K)    # blocks balanced by non-zeros
-        if x_init is not None and y_init is not None:  # full vectors in, this rank's blocks of the padded layout on
-            xi = eng.part.pad_cols(as_vec(x_init, Kp.n, device, dtype))
-            yi = eng.part.pad_rows(as_vec(y_init, Kp.m, device, dtype))
-            x_init, y_init = xi[eng.cols[0]:eng.cols[1]], yi[eng.rows[0]:eng.rows[1]]
+        x_init, y_init = start_blocks(eng, x_init, y_init, Kp.n, Kp.m)
         if b0 is not None:
             b0 = eng.part.pad_cols(as_vec(b0, Kp.n, device, torch.float32))
         verbose = verbose and comm.rank == 0
@@ -390,12 +379,6 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
         primal_update=primal_update, adaptive=adaptive, time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init,
         b0=b0, sigma=sigma, seed=seed, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
         adaptive_retry=adaptive_retry, report=report)
-    if sharded:
-        x = gather_solution(eng, x, Kp.n)
-        if report is not None:
-            from .distributed import gather_report
-            report.update(gather_report(eng, report, Kp.n, Kp.m))
     if report is not None:
-        for key in ("y", "reduced_costs", "row_activity"):
-            report[key] = report[key].view(-1, 1)
-    return x.view(-1, 1), obj, k, n, j, status, total
+        report.update(gather_report(eng, report, Kp.n, Kp.m))
+    return gather_solution(eng, x, Kp.n).view(-1, 1), obj, k, n, j, status, total

@@ -227,6 +227,14 @@ def stack_matrices(mats, device=None, dtype=None) -> Tuple[CsrPair, torch.Tensor
     return CsrPair(m, n, rowptr, (union % n).to(torch.int32), vals[:, 0].contiguous()), vals
 
 
+def resolve_device(device=None) -> torch.device:
+    """the device of a solve: the current HIP device unless given, always with its index"""
+    device = torch.device("cuda") if device is None else torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
 def as_vec(v: torch.Tensor, length: Optional[int] = None, device=None, dtype=None) -> torch.Tensor:
     """(len,) contiguous view/copy of a (len,1) or (len,) tensor."""
     v = v.reshape(-1)
