@@ -208,6 +208,27 @@ int pdlp_iterate(pdlp_handle h, int iters, int adaptive);
 /* fixed step, multi-rank driver: eta_total += eta and k += 1, `iters` times (pdhg.py:76,109);
  * pdlp_iterate does this itself */
 int pdlp_fixed_advance(pdlp_handle h, int iters);
+/* `iters` iterations of the restarted, reflected Halpern iteration (rHPDHG) by plain launches on the handle's stream, without host
+ * synchronisation.  The reference has no counterpart (it averages: pdhg.py:107-119).  With z = (x, y) in PDLP_CUR, the anchor
+ * z0 = the point of the last pdlp_mark_restart_point / pdlp_set_iterate, t = the iterations since the last pdlp_restart /
+ * pdlp_set_iterate, tau = eta/omega and sigma = eta*omega from the scalar block (the fixed step), a = (t+1)/(t+2), b = 1/(t+2)
+ * (formed in double, rounded once to the working precision), one iteration is
+ *     x'   = clamp(x - tau (c - K'y), l, u)                 xbar = x' + (x' - x)
+ *     y'   = y + sigma (q - K xbar);  y'[:m_ineq] = max(., 0)
+ *     x+   = a xbar + b x0                                   y+ = a (2y' - y) + b y0
+ * as two fused products, like the PDHG step: x', xbar and y' are formed with the expressions of pdlp_primal_half / pdlp_dual_half at
+ * theta = 1, so (x', y') equals one fixed PDHG step from z bit for bit.  Afterwards PDLP_CUR is z+ = (x+, y+), PDLP_AVG holds the
+ * CANDIDATE (x', y') of the last iteration -- inside the bounds and with y >= 0 on the inequality rows, which z+ need not be -- and
+ * PDLP_PREV is not defined.  The candidate is what a restart check evaluates and what a restart adopts, with the calls that serve
+ * the average in the PDHG loop: pdlp_kkt_local(PDLP_AVG), pdlp_restart(PDLP_AVG) (t = 0 again), pdlp_restart_distance_local,
+ * pdlp_mark_restart_point (the adopted point is the new anchor), pdlp_get_iterate(PDLP_AVG).
+ * Everything carried from before is dropped: the K x cache, a K'y kept by a KKT pass, and the running sums (until the next
+ * restart), so pdlp_kkt_local(PDLP_AVG) afterwards multiplies.  The K'y that pass keeps is NOT reused by the first Halpern iteration
+ * after the restart (it multiplies again: one product in 2 * period + 2); a PDHG iteration that follows the restart does reuse it.
+ * PDLP_ERR_INVALID: null handle, iters < 0.  PDLP_ERR_STATE: PDLP_MIXED handles, a shard of a problem, a handle with a communicator
+ * or a peer exchange, PDLP_OPT_GRAPH switched on.  After Halpern iterations and before the next pdlp_set_iterate,
+ * pdlp_flush_average and pdlp_compute_average return PDLP_ERR_STATE (they would overwrite the candidate). */
+int pdlp_halpern_iterate(pdlp_handle h, int iters);
 
 /* ---- sharded problems: the exchange inside the library (RCCL over xGMI) ------------------------------------------------
  * One process per GPU; rank r owns block r of the constraints and of the variables (equal, padded blocks -- the layout of

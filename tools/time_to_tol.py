@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Time-to-tolerance on the bench LP (BASELINE.json metric, second half): full restarted solve, prints the
 restart log every check.  python tools/time_to_tol.py [n] [nnz_per_row] [tol] [ruiz 0/1] [max_kkt] [f32|f64|mixed] [--pock-chambolle]
+[--halpern | --fixed]
 (--pock-chambolle, with ruiz 1: the Pock-Chambolle pass after the sweeps, solve_lp's pock_chambolle=True)
+(--halpern: the reflected Halpern iteration, solve_lp's halpern=True -- fixed step, f32 / f64; --fixed: averaged PDHG with the fixed
+step, its like-for-like comparison; neither: the adaptive step)
 (mixed: the generator's matrix entries are float32 numbers, so holding K in float32 under float64 vectors is the same LP
 as the f64 run; PDLP_DELTA=0 switches its delta mode off)"""
 import os, sys, time
@@ -11,7 +14,8 @@ import torchpdlp_amd as tp
 from torchpdlp_amd.solver import run_pdlp
 
 pock = "--pock-chambolle" in sys.argv
-sys.argv = [a for a in sys.argv if a != "--pock-chambolle"]
+halpern, fixed = "--halpern" in sys.argv, "--fixed" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--pock-chambolle", "--halpern", "--fixed")]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 tol = float(sys.argv[3]) if len(sys.argv) > 3 else 1e-4
@@ -21,6 +25,8 @@ if pock and not ruiz:
 max_kkt = int(sys.argv[5]) if len(sys.argv) > 5 else 40000
 prec = sys.argv[6] if len(sys.argv) > 6 else "f32"        # f32 | f64 | mixed (float32 matrix, float64 vectors, delta mode)
 dt = torch.float32 if prec == "f32" else torch.float64
+if halpern and (fixed or prec == "mixed"):
+    sys.exit("--halpern runs in f32 or f64 and is a mode of its own (not with --fixed)")
 dev = torch.device("cuda", 0)
 time_limit = float(os.environ.get("TIME_LIMIT", "900"))
 
@@ -56,8 +62,10 @@ torch.cuda.synchronize()
 print(f"setup {time.time()-t0:.1f}s (ruiz{' + Pock-Chambolle' if pock else ''} {t_ruiz:.2f}s) kernels={eng.kernels} precision={prec} delta={eng.delta}", flush=True)
 trace = dict(kkt=[], omega=[], restarts=[])
 x, obj, it, nr, j, status, secs = run_pdlp(eng, max_kkt=max_kkt, tol=tol, verbose=True, precondition=ruiz, primal_update=True,
-                                           adaptive=True, time_limit=time_limit, seed=0, power_iters=100, trace=trace)
-print(f"RESULT n={n} k={k} tol={tol} ruiz={ruiz} pock_chambolle={pock} precision={prec}: status={status} obj={obj:.6f} iterations={it} restarts={nr} kkt_passes={j} "
+                                           adaptive=not (halpern or fixed), time_limit=time_limit, seed=0, power_iters=100, trace=trace,
+                                           halpern=halpern)
+print(f"RESULT n={n} k={k} tol={tol} ruiz={ruiz} pock_chambolle={pock} precision={prec} "
+      f"method={'halpern' if halpern else 'fixed' if fixed else 'adaptive'}: status={status} obj={obj:.6f} iterations={it} restarts={nr} kkt_passes={j} "
       f"solve_time={secs:.2f}s  ({it/secs:.1f} it/s incl. power iteration and checks)", flush=True)
 
 # ---- independent float64 check of the exit point (at 10M the only evaluator of the 1e-8 claim was the library's own
@@ -65,7 +73,8 @@ print(f"RESULT n={n} k={k} tol={tol} ruiz={ruiz} pock_chambolle={pock} precision
 # the three tests of check_termination (/root/reference/PDLP/helpers.py:110-128) on the un-scaled iterate.
 from torchpdlp_amd import _native as N
 from torchpdlp_amd.synthetic import _regular_matvec, _regular_rmatvec
-xs, ys = eng.get_iterate(N.CUR)
+# (a Halpern run that ended between restarts returned the candidate of its last iteration: that is the point to check)
+xs, ys = eng.get_iterate(N.AVG if halpern and status == "Unsolved (Time limit exceeded)" else N.CUR)
 xs, ys = xs.double(), ys.double()
 if ruiz:                                     # x = D_col x_s, y = D_row y_s (pdhg.py:161)
     xs, ys = xs * dcol.view(-1).double(), ys * drow.view(-1).double()

@@ -38,6 +38,9 @@ def parse_args(argv=None):
                    help="with --adaptive_stepsize: repeat a rejected step with the shrunk step size until one is accepted (the loop "
                         "the reference's adaptive step was meant to be, enhancements/test_ass.py:322-363); default: one trial, as the "
                         "live package does")
+    p.add_argument("--halpern", action="store_true",
+                   help="not in the reference's CLI: the restarted, reflected Halpern iteration instead of averaged PDHG (fixed step; "
+                        "not with --adaptive_stepsize, --infeasibility_detect, --dtype mixed or several ranks)")
     p.add_argument("--direct_exchange", action="store_true",
                    help="several ranks of one node (not in the reference's CLI): iterate without collectives -- every half-step stores "
                         "its block straight into the other ranks' memory over HIP IPC / xGMI; cross-checked against the "
@@ -142,7 +145,7 @@ def main(argv=None) -> int:
                          adaptive_stepsize=args.adaptive_stepsize, adaptive_retry=args.adaptive_retry, max_kkt=args.max_kkt, time_limit=args.time_limit,
                          verbose=args.verbose, dtype=dtype, seed=args.seed, fishnet=args.fishnet, comm=comm,
                          infeasibility_detect=args.infeasibility_detect, precision="mixed" if args.dtype == "mixed" else None,
-                         direct_exchange=args.direct_exchange, report=args.solution_dir is not None)
+                         direct_exchange=args.direct_exchange, report=args.solution_dir is not None, halpern=args.halpern)
             print(f"Solver uses {r.time:.4f} seconds.\nStatus: {r.status}")
             if args.solution_dir is not None and rank == 0:
                 print(f"Solution saved to {write_solution(args.solution_dir, name, r)}")

@@ -68,7 +68,7 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
              seed: Optional[int] = None, compat: bool = True, x_init=None, y_init=None, trace=None,
              fishnet: bool = False, comm=None, infeasibility_detect: bool = False, infeas_tol: float = 1e-4,
              precision: Optional[str] = None, adaptive_retry: bool = False, direct_exchange: bool = False,
-             report: bool = True, pock_chambolle: bool = False) -> LPResult:
+             report: bool = True, pock_chambolle: bool = False, halpern: bool = False) -> LPResult:
     """Solve ``min c'x, K[:m_ineq]x >= q[:m_ineq], K[m_ineq:]x = q[m_ineq:], l <= x <= u`` on the current HIP device.
 
     ``problem`` is an MPS path or ``(c, K, q, m_ineq, l, u)`` with ``K`` dense / COO / scipy-sparse / ``CsrPair``.
@@ -89,8 +89,16 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     alpha = 1 after the Ruiz sweeps -- rows and columns divided by the square roots of their 1-norms
     (``precondition.pock_chambolle_pass``).  It composes into the same ``D_col``, ``D_row``, so the solution and
     the report are un-scaled as with Ruiz alone.  Sharded solves do not have it yet and raise ``ValueError``.
+    ``halpern`` (not in the reference): the restarted, reflected Halpern iteration instead of averaged PDHG, with the fixed step
+    (``pdlp_algorithm``).  Works with ``precondition``, ``pock_chambolle``, ``primal_weight_update``,
+    ``x_init`` / ``y_init`` and ``fishnet``; ``ValueError`` with ``adaptive_stepsize``, ``adaptive_retry``, ``infeasibility_detect``,
+    ``precision="mixed"`` and for sharded solves (``comm``).
     """
     _check_pock_chambolle(pock_chambolle, precondition)
+    if halpern and (adaptive_stepsize or adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False)
+                    or direct_exchange):
+        from .solver import HALPERN_REFUSED
+        raise ValueError(HALPERN_REFUSED)
     device = resolve_device(device)
     if is_mixed(precision):
         dtype = torch.float64
@@ -98,6 +106,8 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     run = dict(max_kkt=max_kkt, tol=tol, restart_period=restart_period, precondition=precondition, primal_update=primal_weight_update,
                adaptive=adaptive_stepsize, time_limit=time_limit, trace=trace, infeasibility_detect=infeasibility_detect,
                infeas_tol=infeas_tol, adaptive_retry=adaptive_retry)
+    if halpern:
+        run["halpern"] = True
     if comm is not None and not fishnet:
         from .engine import Comm
         cm = Comm() if comm is True else comm

@@ -125,6 +125,55 @@ template <typename T, bool ADAPT, bool PEER = false> struct DualEpi {
     }
 };
 
+// Reflected Halpern iteration (pdlp_halpern_iterate; the reference has no counterpart), primal half over the rows of K'.
+// x' and xbar are formed with PrimalEpi's own expressions at theta = 1 (the candidate equals one fixed PDHG step bit for bit);
+// the new iterate is the reflected point xbar = 2x' - x pulled towards the anchor: x+ = a xbar + b x_last, a = (t+1)/(t+2),
+// b = 1/(t+2) rounded once on the host.  No running sums: five operand loads, three stores.
+template <typename T> struct HalpernPrimalEpi {
+    static constexpr int NA = 0;
+    const T* x_old; T* x_new; T* xbar; T* x_cand; const T* x_last; const T* c; const T* l; const T* u; const double* sc;
+    T a, b;
+    T tau = 0;
+    __device__ void load() { tau = (T)sc[S_TAU]; }
+    struct Pre { T xo, xl, cj, lo, hi; };
+    __device__ Pre pre(int j) const { return Pre{x_old[j], x_last[j], c[j], l[j], u[j]}; }
+    __device__ void operator()(int j, T kty, double* acc) const { (*this)(j, kty, pre(j), acc); }
+    __device__ void operator()(int j, T kty, const Pre& p, double*) const
+    {
+        const T xo = p.xo;
+        const T grad = p.cj - kty;
+        T v = xo - tau * grad;
+        const T lo = p.lo, hi = p.hi;
+        v = v < lo ? lo : v;
+        v = v > hi ? hi : v;
+        const T d = v - xo;
+        x_cand[j] = v;
+        const T xb = v + d;                // (PrimalEpi's v + theta * d at theta = 1: the product with 1 is exact)
+        xbar[j] = xb;
+        x_new[j] = a * xb + b * p.xl;
+    }
+};
+
+// Reflected Halpern iteration, dual half over the rows of K: y' as DualEpi forms it; y+ = a (2y' - y) + b y_last.
+template <typename T> struct HalpernDualEpi {
+    static constexpr int NA = 0;
+    const T* y_old; T* y_new; T* y_cand; const T* y_last; const T* q; const double* sc; int ineq_end;
+    T a, b;
+    T sigma = 0;
+    __device__ void load() { sigma = (T)sc[S_SIGMA]; }
+    struct Pre { T yo, yl, qi; };
+    __device__ Pre pre(int i) const { return Pre{y_old[i], y_last[i], q[i]}; }
+    __device__ void operator()(int i, T kxbar, double* acc) const { (*this)(i, kxbar, pre(i), acc); }
+    __device__ void operator()(int i, T kxbar, const Pre& p, double*) const
+    {
+        const T yo = p.yo;
+        T v = yo + sigma * (p.qi - kxbar);
+        if (i < ineq_end && v < (T)0) v = (T)0;
+        y_cand[i] = v;
+        y_new[i] = a * ((T)2 * v - yo) + b * p.yl;
+    }
+};
+
 // KKT, dual side (helpers.py:75-84,94 with project_lambda_box helpers.py:21-37 and pdhg.py:11-17)
 template <typename T, bool UNSCALE> struct KktDualEpi {
     static constexpr int NA = 4;

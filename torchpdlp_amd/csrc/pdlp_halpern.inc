@@ -1,0 +1,53 @@
+// pdlp_halpern.inc -- the restarted, reflected Halpern iteration (pdlp_halpern_iterate, include/pdlp_hip.h): two fused products
+// per iteration like the PDHG step, with HalpernPrimalEpi / HalpernDualEpi as their epilogues.  The iterate z lives in the PDLP_CUR
+// buffers, the candidate T(z) -- one fixed PDHG step from z -- in the PDLP_AVG buffers, the anchor is the restart point (x_last,
+// y_last) and t is the handle's count of iterations since the last restart.  The reference has no counterpart.
+// Part of pdlp_hip.hip (included at file scope; not a translation unit of its own).  Needs: pdlp_products.inc and what is before it.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+template <typename T> int halpern_iterate_t(pdlp_handle h, int iters)
+{
+    int rc;
+    for (int it = 0; it < iters; ++it) {
+        // a = (t+1)/(t+2), b = 1/(t+2) in double, rounded once to the working type
+        const double t2 = (double)(h->since_reset + 2);
+        const T a = (T)((double)(h->since_reset + 1) / t2), b = (T)(1.0 / t2);
+        const int cur = h->ix_cur, nxt = h->ix_prev, cand = h->ix_avg;
+        HalpernPrimalEpi<T> ep{xloc<T>(h, cur), xloc<T>(h, nxt), (T*)h->xbar + h->p.col0, xloc<T>(h, cand), (const T*)h->x_last,
+                               (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, h->sc, a, b};
+        if ((rc = launch_csr<T>(h, true, h->yb[cur], ep, h->partA)) != PDLP_OK) return rc;
+        HalpernDualEpi<T> ed{yloc<T>(h, cur), yloc<T>(h, nxt), yloc<T>(h, cand), (const T*)h->y_last, (const T*)h->p.q, h->sc,
+                             h->ineq_end, a, b};
+        if ((rc = launch_csr<T>(h, false, h->xbar, ed, h->partB)) != PDLP_OK) return rc;
+        h->ix_cur = nxt;           // the freshly written z becomes current; the old z's buffers are the next iteration's target
+        h->ix_prev = cur;
+        ++h->since_reset;
+    }
+    return PDLP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pdlp_halpern_iterate(pdlp_handle h, int iters)
+{
+    if (!h || iters < 0) return PDLP_ERR_INVALID;
+    // forms this mode does not have: mixed precision / delta mode, a shard of a problem, an exchange of any kind, graph replay
+    if (h->mixed || h->delta || h->nl != h->p.n || h->ml != h->p.m || h->comm || h->peer.on || h->graph_ok) return PDLP_ERR_STATE;
+    if (iters == 0) return PDLP_OK;
+    char rname[64];
+    if (g_roctx.level > 0) std::snprintf(rname, sizeof rname, "pdlp: %d Halpern iterations", iters);
+    Range range(rname, h->stream);
+    // nothing carried from before survives: the K x cache, a K'y kept by a KKT pass (every primal half here multiplies), the
+    // products of the candidates, and the running sums (broken until the next restart: pdlp_kkt_local(PDLP_AVG) multiplies)
+    h->kx_valid = false; h->cur_kx_cached = false;
+    h->cand_valid[0] = h->cand_valid[1] = false;
+    h->kty_cur = -1; h->kty_tail_done = false; h->avg_products = false;
+    h->sums_broken = true;
+    h->halpern = true;             // PDLP_AVG holds the candidate now: pdlp_flush_average / pdlp_compute_average are refused
+    return DISPATCH(h, halpern_iterate_t, h, iters);
+}
+
+}  // extern "C"

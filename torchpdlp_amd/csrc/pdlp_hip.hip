@@ -19,6 +19,7 @@
 //     pdlp_kkt.inc            KKT pass, report, flush / average / distance / infeasibility / power iteration; pdlp_restart
 //     pdlp_population.inc     the mv_* launchers; pdlp_mv_combine
 //     pdlp_driver.inc         the library's iteration driver: direct, graph replay, sharded over RCCL; pdlp_comm_*
+//     pdlp_halpern.inc        the reflected Halpern iteration (opt-in solve mode); pdlp_halpern_iterate
 //     pdlp_peer.inc           the direct exchange over HIP IPC: iterate_peer; pdlp_peer_*
 //     pdlp_ruiz.inc           entry points that take no handle: Ruiz blocks, pdlp_vec_*, the bandwidth probes
 //     pdlp_batch_host.inc     batched solves: launch shapes and pdlp_batch_*
@@ -140,6 +141,7 @@ inline int rows_grid(int64_t rows) { return rows > 0 ? grid_for(rows) : 0; }    
 #include "pdlp_kkt.inc"
 #include "pdlp_population.inc"
 #include "pdlp_driver.inc"
+#include "pdlp_halpern.inc"
 #include "pdlp_peer.inc"
 #include "pdlp_ruiz.inc"
 
@@ -148,8 +150,8 @@ inline int rows_grid(int64_t rows) { return rows > 0 ? grid_for(rows) : 0; }    
 // ================================================================================================
 extern "C" {
 
-// 18: pdlp_batch_* (batched solves over one matrix); pdlp_batch_attach_matrices and pdlp_batch_product joined them without a
-//     change to any existing signature or struct, so the number stands
+// 18: pdlp_batch_* (batched solves over one matrix); pdlp_batch_attach_matrices, pdlp_batch_product and pdlp_halpern_iterate joined
+//     them without a change to any existing signature or struct, so the number stands
 // 17: pdlp_peer_* (direct exchange over HIP IPC), PDLP_OPT_BEGIN_INLINE
 // 16: pdlp_set_option (the library reads no environment variables), pdlp_mv_product, pdlp_mv_combine, pdlp_vec_sqdist,
 //     pdlp_probe_gather, pdlp_tile_limits reports the threads per workgroup, pdlp_primal_half_piece / pdlp_dual_half_piece (results
@@ -332,6 +334,7 @@ int pdlp_set_iterate(pdlp_handle h, const void* x_local, const void* y_local)
     HIP_TRY(hipMemsetAsync(h->kx_sum, 0, h->ml * h->es, h->stream));
     HIP_TRY(hipMemsetAsync(h->kty_sum, 0, h->nl * h->es, h->stream));
     h->since_reset = 0; h->kty_tail_done = false; h->avg_products = false; h->sums_broken = false; h->cur_kx_cached = false;
+    h->halpern = false;
     return PDLP_OK;
 }
 
@@ -541,12 +544,14 @@ int pdlp_fixed_advance(pdlp_handle h, int iters)
 int pdlp_flush_average(pdlp_handle h, int adaptive)
 {
     if (!h) return PDLP_ERR_INVALID;
+    if (h->halpern) return PDLP_ERR_STATE;       // (the averaging calls would overwrite the Halpern candidate in PDLP_AVG)
     return DISPATCH(h, flush_t, h, adaptive ? 1 : 0);
 }
 
 int pdlp_compute_average(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
+    if (h->halpern) return PDLP_ERR_STATE;
     return DISPATCH(h, average_t, h);
 }
 

@@ -321,6 +321,13 @@ class PdlpEngine(KernelChoice, Exchange):
         else:
             N.check(self.lib.pdlp_iterate(self.h, iters, int(adaptive)), "pdlp_iterate")
 
+    def halpern_iterate(self, iters: int):
+        """``iters`` iterations of the restarted, reflected Halpern iteration (``pdlp_halpern_iterate``, include/pdlp_hip.h), no host
+        synchronisation: ``N.CUR`` is the Halpern iterate afterwards and ``N.AVG`` the candidate -- one fixed PDHG step from the
+        iterate before the last iteration -- which ``kkt(N.AVG)`` evaluates and ``restart(N.AVG)`` adopts.  Float32 / float64 engines
+        on one GPU without graph replay (``PdlpError`` otherwise)."""
+        N.check(self.lib.pdlp_halpern_iterate(self.h, int(iters)), "pdlp_halpern_iterate")
+
     def adaptive_retry(self):
         """discard the adaptive iteration just taken (its trial was rejected: ``scalars()["accepted"] == 0``) so that it can be
         issued again with the shrunk step size -- ``pdlp_adaptive_retry`` (include/pdlp_hip.h), SURVEY quirk Q1's optional flag"""

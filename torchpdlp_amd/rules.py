@@ -92,6 +92,15 @@ def start_omega(q_norm, c_norm, t=np.float32):
         return t(np.where((q_norm > 1e-6) & (c_norm > 1e-6), c_norm / q_norm, t(1.0)))
 
 
+def halpern_weights(t_iter, dtype=np.float32):
+    """``(a, b) = ((t+1)/(t+2), 1/(t+2))`` of Halpern iteration number ``t_iter`` since the last restart (0 for the first): the
+    new iterate is ``a * reflected point + b * anchor``.  Both are formed in float64 and rounded once to the working precision
+    ``dtype`` (a torch or numpy dtype, or a numpy scalar type) -- what ``pdlp_halpern_iterate`` hands its kernels"""
+    t = np_type(getattr(dtype, "__name__", dtype))
+    t2 = np.float64(int(t_iter) + 2)
+    return t(np.float64(int(t_iter) + 1) / t2), t(np.float64(1.0) / t2)
+
+
 def primal_weight(dx2, dy2, omega, smooth_theta=0.5, t=np.float32):
     """primal_weight_update (enhancements.py:73-78) given the two squared restart distances.
 

@@ -27,6 +27,8 @@ def check_termination(primal_residual, dual_residual, duality_gap, prim_obj, adj
 
 
 kkt_from_residuals = kkt_error
+HALPERN_REFUSED = ("halpern=True runs the fixed step on one GPU in float32 or float64: not with adaptive, adaptive_retry, "
+                   "infeasibility_detect, mixed precision or a communicator")
 primal_weight_from_distances = primal_weight
 
 
@@ -60,11 +62,23 @@ class PdhgDriver:
     ``restart_period`` iterations since the last restart), performs the check, and on a restart does the
     post-restart work (primal weight, KKT_first, termination test).  ``run_pdlp`` loops over it; the
     benchmark times the very same calls.
+
+    ``halpern=True``: the restarted, reflected Halpern iteration (rHPDHG) instead of averaged PDHG, with the fixed step.  A segment
+    is ``eng.halpern_iterate``; a check evaluates ONE point, the candidate ``N.AVG`` (one PDHG step from the Halpern iterate: inside
+    the bounds), and hands ``restart_decision`` ``kkt_cur = inf``, ``kkt_avg`` = the candidate's KKT error and ``kkt_prev`` = the
+    candidate's error at the previous check of this restart period (``inf`` at the first) -- so the decision is "restart at the
+    candidate" or "keep"; ``after_restart`` runs as it is.  KKT-pass accounting: ``j += iters`` per segment, ``j += 1`` per check,
+    and the two of ``after_restart``.
     """
 
     def __init__(self, eng: PdlpEngine, restart_period=40, primal_update=False, adaptive=False, precondition=False,
-                 tol=1e-4, verbose=False, trace=None, infeasibility_detect=False, infeas_tol=1e-4, adaptive_retry=False):
+                 tol=1e-4, verbose=False, trace=None, infeasibility_detect=False, infeas_tol=1e-4, adaptive_retry=False,
+                 halpern=False):
         self.eng, self.period = eng, int(restart_period)
+        self.halpern = bool(halpern)
+        if self.halpern and (adaptive or adaptive_retry or infeasibility_detect or getattr(eng, "mixed", False) or eng.comm is not None):
+            raise ValueError(HALPERN_REFUSED)
+        self.kkt_prev_cand = None                                           # Halpern: the candidate's KKT error at the previous check
         self.infeasibility_detect, self.infeas_tol = bool(infeasibility_detect), float(infeas_tol)
         self.infeasible = None                                              # the detector's verdict (pdhg.py:94-100)
         # SURVEY quirk Q1's optional flag: the adaptive step as it was meant (enhancements/test_ass.py:322-363) -- a rejected trial is
@@ -100,6 +114,7 @@ class PdhgDriver:
         self.n = self.k = self.j = self.tt = 0
         self.KKT_first = t(0)
         self.res, self.solved, self.infeasible = None, False, None
+        self.kkt_prev_cand = None
 
     def advance(self, max_iters: int) -> int:
         """Iterate up to the next restart check (at most ``max_iters``); returns the iterations done."""
@@ -134,7 +149,10 @@ class PdhgDriver:
         iters = min(self.period - self.tt % self.period, max_iters)
         if iters <= 0:
             return 0, False
-        if self.adaptive_retry:                    # every iteration is tried until a step is accepted, one KKT-pass count per trial
+        if self.halpern:
+            eng.halpern_iterate(iters)
+            self.j += iters
+        elif self.adaptive_retry:                    # every iteration is tried until a step is accepted, one KKT-pass count per trial
             for _ in range(iters):
                 trials = 0
                 while True:
@@ -152,8 +170,41 @@ class PdhgDriver:
         self.tt += iters
         return iters, self.tt % self.period == 0                            # pdhg.py:115
 
+    def _halpern_check(self):
+        """the restart check of the Halpern mode: one KKT pass at the candidate, the rules of ``restart_decision`` unchanged"""
+        eng, t = self.eng, self.t
+        timed = self.check_seconds is not None
+        if timed:
+            eng.synchronize()
+            t_check = time.perf_counter()
+        self.checks += 1
+        with N.trace_range("pdlp: restart check (Halpern candidate)", getattr(eng, "stream", None)):
+            r_cand = eng.kkt(N.AVG, self.omega)
+            k_cur, k_cand = t(np.inf), t(r_cand["kkt"])
+            k_prev = t(np.inf) if self.kkt_prev_cand is None else self.kkt_prev_cand
+            self.kkt_prev_cand = k_cand
+            self.j += 1
+            if self.trace is not None:
+                self.trace["kkt"] += [float(k_cur), float(k_cand), float(k_prev)]
+            dec = restart_decision(k_cur, k_cand, k_prev, self.KKT_first, self.tt, self.k, self.j, live=True, t=t)
+        crit = int(dec["crit"])
+        if crit >= 0:
+            if self.verbose:
+                print(f"{('Sufficient', 'Necessary', 'Artificial')[crit]} restart at iteration {self.tt} using the Halpern candidate.")
+            if self.trace is not None:
+                self.trace["restarts"].append((crit, self.tt, 1))
+            with N.trace_range("pdlp: restart work (restart, primal weight, termination test)", getattr(eng, "stream", None)):
+                eng.restart(N.AVG)
+                self.kkt_prev_cand = None
+                self.after_restart(r_cand)
+        if timed:
+            eng.synchronize()
+            self.check_seconds += time.perf_counter() - t_check
+
     def _restart_check(self):
         """pdhg.py:115-146: the three KKT errors, the decision and, when it says so, the restart with its work"""
+        if self.halpern:
+            return self._halpern_check()
         eng, t = self.eng, self.t
         timed = self.check_seconds is not None
         if timed:
@@ -195,8 +246,12 @@ class PdhgDriver:
         """pdhg.py:148-177: n += 1, primal weight, KKT_first, residuals, termination test."""
         eng, t = self.eng, self.t
         self.n += 1
-        self.tt = 0
-        if chosen is None:       # the KKT-pass cap ended the inner loop: continue from the current iterate
+        since, self.tt = self.tt, 0
+        if chosen is None and self.halpern and since > 0:
+            # Halpern: the point that is inside the bounds is the candidate of the last iteration, not the reflected iterate
+            eng.restart(N.AVG)
+            self.kkt_prev_cand = None
+        elif chosen is None:     # the KKT-pass cap ended the inner loop: continue from the current iterate
             eng.restart(N.CUR)
         if self.primal_update:                                              # pdhg.py:150-151
             dx2, dy2 = eng.restart_distance()
@@ -252,17 +307,18 @@ def estimate_sigma(eng: PdlpEngine, b0=None, power_iters=100, seed=None) -> floa
 def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_period=40, precondition=False,
              primal_update=False, adaptive=False, time_limit=3600, time_used=0, x_init=None, y_init=None,
              b0=None, sigma=None, power_iters=100, seed=None, trace=None, infeasibility_detect=False, infeas_tol=1e-4,
-             adaptive_retry=False, *, report=None):
+             adaptive_retry=False, *, report=None, halpern=False):
     """The outer loop over an existing engine.  Returns (x_local, prim_obj, k, n, j, status, total_time).
     ``report``: a dict that receives ``PdlpEngine.report`` of the returned iterate (this rank's blocks; of the un-preconditioned
     problem when ``precondition``) whatever the status, and ``q_norm`` / ``c_norm`` as the termination test used them -- in the
-    style of ``trace``."""
+    style of ``trace``.  ``halpern``: the restarted, reflected Halpern iteration (``PdhgDriver``); the returned iterate is then the
+    candidate of the last restart or, when the run ends between restarts, of the last iteration."""
     t0 = time.time()
     if adaptive_retry and (getattr(eng, "delta", False) or infeasibility_detect):
         raise ValueError("adaptive_retry works on float32 / float64 engines without the infeasibility detector")
     drv = PdhgDriver(eng, restart_period, primal_update=primal_update, adaptive=adaptive, precondition=precondition, tol=tol,
                      verbose=verbose, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
-                     adaptive_retry=adaptive_retry)
+                     adaptive_retry=adaptive_retry, halpern=halpern)
     if sigma is None:                                                       # pdhg.py:22
         sigma = estimate_sigma(eng, b0, power_iters, seed)
     drv.start(sigma, x_init, y_init)
@@ -302,9 +358,10 @@ def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_p
             if verbose:
                 print(f"Converged at iteration {drv.k} restart loop {drv.n}")
             break
-    x_local, _ = eng.get_iterate(N.CUR)
+    final = N.AVG if halpern and drv.tt > 0 else N.CUR     # (Halpern between restarts: the candidate, which is inside the bounds)
+    x_local, _ = eng.get_iterate(final)
     if report is not None:
-        report.update(eng.report(N.CUR, unscaled=bool(precondition), omega=drv.omega))
+        report.update(eng.report(final, unscaled=bool(precondition), omega=drv.omega))
         report.update(q_norm=float(drv.q_norm), c_norm=float(drv.c_norm))      # as the exit test took them (pdhg.py:19-20)
     eng.synchronize()                                  # the reference reads its clock without a sync (Q10)
     prim_obj = float(drv.res["p"]) if drv.res is not None else float("nan")
@@ -314,7 +371,8 @@ def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_p
 def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4, verbose=True, restart_period=40,
                    precondition=False, primal_update=False, adaptive=False, data_precond=None, infeasibility_detect=False,
                    infeas_tol=1e-4, time_limit=3600, time_used=0, x_init=None, y_init=None, *, b0=None, sigma=None,
-                   seed=None, trace=None, comm=None, precision=None, adaptive_retry=False, report=None):
+                   seed=None, trace=None, comm=None, precision=None, adaptive_retry=False, report=None,
+                   halpern=False):
     """Drop-in for the reference's ``pdlp_algorithm`` (primal_dual_hybrid_gradient.py:7) on one MI355X.
 
     ``K`` may be a dense / COO torch tensor (as the reference takes), a scipy sparse matrix or a
@@ -341,11 +399,19 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     ``precondition`` (un-like ``x``) -- for every exit status; ``q_norm``, ``c_norm``: the norms check_termination was given
     (pdhg.py:19-20,173: of the ``q`` and ``c`` passed in, i.e. of the scaled vectors when ``precondition``).
 
+    ``halpern`` (default off; the reference has no counterpart): the restarted, reflected Halpern iteration instead of averaged
+    PDHG -- fixed step, the restart rules and the primal weight unchanged, evaluated at the candidate (one PDHG step from the
+    Halpern iterate); see ``PdhgDriver`` and DESIGN.md 4.2.  Works with ``precondition``, ``primal_update`` and ``x_init`` /
+    ``y_init``; ``ValueError`` together with ``adaptive``, ``adaptive_retry``, ``infeasibility_detect``, ``precision="mixed"`` or
+    ``comm``.
+
     ``comm`` (a ``Comm``, or ``True`` for the default ``torch.distributed`` group): every rank calls with the SAME
     full problem and the same ``seed``/``b0``; each keeps its row blocks of K and K', the iterations exchange
     ``xbar`` and ``y`` over RCCL, and every rank returns the full solution.
     """
     from .distributed import gather_report, gather_solution, shard_engine, start_blocks
+    if halpern and (adaptive or adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False)):
+        raise ValueError(HALPERN_REFUSED)
     device = resolve_device(device)
     Kp = CsrPair.from_any(K, device=device)
     dtype = Kp.dtype
@@ -378,7 +444,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
         eng, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period, precondition=precondition,
         primal_update=primal_update, adaptive=adaptive, time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init,
         b0=b0, sigma=sigma, seed=seed, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
-        adaptive_retry=adaptive_retry, report=report)
+        adaptive_retry=adaptive_retry, report=report, halpern=halpern)
     if report is not None:
         report.update(gather_report(eng, report, Kp.n, Kp.m))
     return gather_solution(eng, x, Kp.n).view(-1, 1), obj, k, n, j, status, total
