@@ -156,7 +156,9 @@ int pdlp_buffer_ptr(pdlp_handle h, int which, void** ptr);
 int pdlp_set_iterate(pdlp_handle h, const void* x_local, const void* y_local);
 int pdlp_get_iterate(pdlp_handle h, int which, void* x_local, void* y_local);   /* device destinations */
 /* step size eta, primal weight omega, extrapolation theta (pdhg.py:22-25); rounded to the working
- * precision on the device exactly as the reference's 0-dim tensors are. iteration = global k so far. */
+ * precision on the device exactly as the reference's 0-dim tensors are. iteration = global k so far.
+ * Inside an averaging period (iterations since the last pdlp_set_iterate / pdlp_restart) the call also ends the period's running
+ * products (see pdlp_flush_average): every result stays what it would be, the restart checks multiply until the next restart. */
 int pdlp_set_step(pdlp_handle h, double eta, double omega, double theta, int64_t iteration);
 /* new primal weight after a restart (primal_weight_update enhancements.py:77); keeps the device eta */
 int pdlp_set_omega(pdlp_handle h, double omega);
@@ -289,6 +291,9 @@ int pdlp_dual_half_piece(pdlp_handle h, int adaptive, int piece, int pieces);
  *                         ranks those panels are a half / a quarter of the product and hide the transfer over the links, which
  *                         stores issued by the epilogue (the last microseconds of a half-step, same stream) cannot; same results as
  *                         PDLP_OPT_PEER_LOCAL_FIRST */
+/* Any switch may be flipped between any two calls (PDLP_ERR_STATE only in the middle of a split half-step).  PDLP_OPT_RUNNING_KKT
+ * switched back on, or PDLP_OPT_GRAPH flipped after having been on, inside an averaging period: the running sums were not kept in the
+ * meantime, so the checks of that period multiply (as after a pdlp_flush_average without K'y of the current iterate). */
 enum { PDLP_OPT_RUNNING_KKT = 0, PDLP_OPT_KTY_REUSE = 1, PDLP_OPT_GRAPH = 2, PDLP_OPT_SPLIT_SLOTS = 3, PDLP_OPT_PRODUCER_PIECES = 4,
        PDLP_OPT_BEGIN_INLINE = 5, PDLP_OPT_PEER_EXCHANGE = 6, PDLP_OPT_PEER_TIMEOUT_MS = 7, PDLP_OPT_PEER_LOCAL_FIRST = 8,
        PDLP_OPT_PEER_PUSH = 9 };
@@ -357,7 +362,9 @@ int pdlp_delta_state(pdlp_handle h, int32_t out[3]);
  * iterate to the sums (adaptive mode defers it by one step because the weight is only known after the step-size rule).
  * Both modes: the handle also keeps running sums of w_k K x_k and w_k K'y_k (K is linear: they are K x_avg and K'y_avg up to
  * the division), so that the check needs no product for the averaged iterate; K'y of the CURRENT y exists only once
- * pdlp_kkt_local(PDLP_CUR) has run, so call that first -- otherwise this call falls back to products for the average. */
+ * pdlp_kkt_local(PDLP_CUR) has run, so call that first -- otherwise this call falls back to products for the average.  So does a
+ * period in which pdlp_set_step was called after its first iteration (the fixed step weighs K'y of an iterate with the eta of the
+ * iteration AFTER it, when that product exists), pdlp_adaptive_retry or pdlp_halpern_iterate ran, or graph replay is switched on. */
 int pdlp_flush_average(pdlp_handle h, int adaptive);
 /* x_avg = x_sum / eta_sum, y_avg = y_sum / eta_sum for this rank's block -- pdhg.py:118-119 */
 int pdlp_compute_average(pdlp_handle h);

@@ -7,7 +7,6 @@ import os
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 import torch
 
 pytestmark = pytest.mark.gpu
@@ -15,15 +14,13 @@ pytestmark = pytest.mark.gpu
 from oracle import oracle as orc                                   # the checker (tests only)
 import torchpdlp_amd as tp
 from tests.conftest import GOLDEN
+from tests.host_lp import DEV, NP, get_lp          # the LPs (float64 numpy on the host; every value is a float32 number)
 from torchpdlp_amd import _native as N
 from torchpdlp_amd.rules import halpern_weights
-from torchpdlp_amd.tiled import build_tiles
 
-DEV = "cuda:0"
 AFIRO = os.path.join(GOLDEN, "mps", "afiro.mps")
 AFIRO_OPT = -464.7531428571
 DTYPES = [torch.float32, torch.float64]
-NP = {torch.float32: np.float32, torch.float64: np.float64}
 FORMS = ["csr", "sorted", "tiles", "tiles_groups", "tiles_remainder"]
 
 
@@ -32,116 +29,6 @@ def _setup():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     orc.set_threads(1)
     N.load()
-
-
-# ---------------------------------------------------------------------------------------------------
-# the LPs (float64 numpy on the host; every value is a float32 number, so both precisions see the same LP)
-# ---------------------------------------------------------------------------------------------------
-class HostLP:
-    def __init__(self, A, m_ineq, c, q, l, u):
-        self.A = sp.csr_matrix(A, dtype=np.float64)
-        self.A.sort_indices()
-        self.m, self.n = self.A.shape
-        self.m_ineq = int(m_ineq)
-        self.c, self.q, self.l, self.u = (np.asarray(v, np.float32).astype(np.float64) for v in (c, q, l, u))
-        self.A.data = self.A.data.astype(np.float32).astype(np.float64)
-
-    def norm2(self):
-        """||K||_2 by power iteration (float64, on the host)"""
-        b = np.ones(self.n) / np.sqrt(max(self.n, 1))
-        s = 0.0
-        for _ in range(40):
-            b = self.A.T @ (self.A @ b)
-            s = np.linalg.norm(b)
-            if s == 0:
-                return 1.0
-            b /= s
-        return float(np.sqrt(s))
-
-    def oracle(self, dtype):
-        return orc.OracleLP(self.m, self.n, self.m_ineq, self.A.indptr, self.A.indices, self.A.data, self.c, self.q, self.l, self.u,
-                            dtype=NP[dtype])
-
-    def engine(self, dtype, form="csr", **kw):
-        t = lambda v, dt=dtype: torch.tensor(np.asarray(v), dtype=dt, device=DEV)
-        K = tp.CsrPair(self.m, self.n, t(self.A.indptr, torch.int32), t(self.A.indices, torch.int32), t(self.A.data))
-        eng = tp.PdlpEngine.from_full(K, t(self.c), t(self.q), t(self.l), t(self.u), self.m_ineq, **kw)
-        for tr in (0, 1):                       # (whatever the engine chose by itself for this shape: start from the CSR kernel)
-            eng.attach_tiles(tr, None)
-            eng.attach_sorted(tr, on=False)
-        if form == "sorted":
-            for tr in (0, 1):
-                eng.attach_sorted(tr)
-                assert "sorted" in eng.kernels[tr] or int((eng.KT if tr else eng.K)[2].numel()) == 0
-        elif form != "csr":
-            lim = eng.tile_limits()
-            for tr, (rp, ci, va), rows, cols in ((0, eng.K, eng.ml, eng.n), (1, eng.KT, eng.nl, eng.m)):
-                tl = build_tiles(rp, ci, va, rows, cols, lw=6, rpt=1, groups=2 if form == "tiles_groups" else 1,
-                                 max_groups=lim["max_groups"], kernel_limits=(lim["rpt_max"], lim["cap"], lim["nt"]))
-                assert tl is not None, (form, tr)
-                eng.attach_tiles(tr, tl)
-                if form == "tiles_groups":
-                    assert tl.groups == 2 and "2 groups" in eng.kernels[tr]
-                if form == "tiles_remainder":
-                    assert tl.nrem > 0 and "remainder" in eng.kernels[tr]
-                else:
-                    assert tl.nrem == 0
-        return eng
-
-
-def _bounds(rng, n, classes):
-    l, u = np.full(n, -1.0), np.full(n, 2.0)
-    if classes:
-        l[::4], u[::4] = -np.inf, np.inf          # free
-        l[1::4], u[1::4] = 0.5, 0.5               # fixed
-        l[2::4] = -np.inf                         # upper only
-        u[3::4] = np.inf                          # lower only
-    return l, u
-
-
-def edge_lp(case):
-    """the five shapes of test_edge_cases_match_oracle (37 x 23; 1 x 1)"""
-    rng = np.random.default_rng(21)
-    if case == "one_by_one":
-        m, n, m_ineq = 1, 1, 1
-        Kd = np.array([[2.0]])
-    else:
-        m, n = 37, 23
-        Kd = rng.standard_normal((m, n)) * (rng.random((m, n)) < 0.2)
-        m_ineq = {"no_ineq": 0, "all_ineq": m}.get(case, 15)
-        if case == "empty_row_and_col":
-            Kd[5, :] = 0
-            Kd[30, :] = 0
-            Kd[:, 7] = 0
-    l, u = _bounds(rng, n, case == "free_and_fixed")
-    return HostLP(Kd, m_ineq, rng.standard_normal(n), rng.standard_normal(m), l, u)
-
-
-def sparse_lp(m, n, per_row, seed, dense=False):
-    """`per_row` entries in every row at random columns; `dense`: plus one full row and one full column"""
-    rng = np.random.default_rng(seed)
-    rows = np.repeat(np.arange(m), per_row)
-    cols = rng.integers(0, n, size=m * per_row)
-    A = sp.coo_matrix((rng.standard_normal(m * per_row), (rows, cols)), shape=(m, n)).tocsr()      # (duplicates are added up)
-    if dense:
-        A = A.tolil()
-        A[m // 3, :] = rng.standard_normal(n)
-        A[:, n // 2] = rng.standard_normal((m, 1))
-        A = A.tocsr()
-    l, u = _bounds(rng, n, True)
-    return HostLP(A, (2 * m) // 5, rng.standard_normal(n), rng.standard_normal(m), l, u)
-
-
-_LPS = {}
-
-
-def get_lp(name):
-    """built once per session, shared, never written to"""
-    if name not in _LPS:
-        _LPS[name] = (edge_lp(name[5:]) if name.startswith("edge_") else
-                      {"mid": lambda: sparse_lp(600, 520, 8, 5), "mid_dense": lambda: sparse_lp(600, 520, 8, 6, dense=True),
-                       "long": lambda: sparse_lp(2500, 2300, 3, 7, dense=True)}[name]())
-    return _LPS[name]
 
 
 EDGE = ["edge_no_ineq", "edge_all_ineq", "edge_empty_row_and_col", "edge_one_by_one", "edge_free_and_fixed"]

@@ -353,6 +353,10 @@ int pdlp_set_step(pdlp_handle h, double eta, double omega, double theta, int64_t
     if (!h || !(omega > 0.0)) return PDLP_ERR_INVALID;
     WITH_T(h->p.dtype, hipLaunchKernelGGL(k_set_step<T>, dim3(1), dim3(1), 0, h->stream, h->sc, eta, omega, theta, (double)iteration));
     HIP_TRY(hipGetLastError());
+    // inside an averaging period a new eta ends the running products: the fixed step adds K'y of an iterate to its running sum with
+    // the eta of the NEXT iteration (the product only exists then), y_sum has it with its own, so K'y_avg from the sums would not be
+    // K' y_avg any more; the checks multiply until the next restart
+    if (h->since_reset > 0) h->sums_broken = true;
     return PDLP_OK;
 }
 
@@ -417,10 +421,15 @@ int pdlp_set_option(pdlp_handle h, int option, int64_t value)
     if (!h) return PDLP_ERR_INVALID;
     if (h->sK.pending || h->sKT.pending) return PDLP_ERR_STATE;       // not in the middle of a split product
     switch (option) {
-        case PDLP_OPT_RUNNING_KKT: h->no_running = value == 0; return PDLP_OK;
+        case PDLP_OPT_RUNNING_KKT:
+            // (switched back on inside a period: the running sums were not kept meanwhile -- no running average before the next restart)
+            if (h->no_running && value != 0 && h->since_reset > 0) h->sums_broken = true;
+            h->no_running = value == 0;
+            return PDLP_OK;
         case PDLP_OPT_KTY_REUSE: h->no_kty_reuse = value == 0; return PDLP_OK;
         case PDLP_OPT_GRAPH:
             drop_graphs(h);
+            if (h->graph_ok && h->since_reset > 0) h->sums_broken = true;      // (nor while replay was on)
             h->graph_ok = value != 0 && h->side_ok && !h->comm;
             return (value != 0 && !h->graph_ok) ? PDLP_ERR_STATE : PDLP_OK;
         case PDLP_OPT_BEGIN_INLINE: h->begin_inline = value != 0; return PDLP_OK;
