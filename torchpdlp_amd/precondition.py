@@ -91,7 +91,7 @@ def pock_chambolle_pass(lib, code, stream, rows_K, rows_KT, K_blk, KT_blk, D_row
 
 @dataclass
 class Scaling:
-    """The factors of an equilibration, ``Ks = diag(1/D_row) K diag(1/D_col)``, and the one place where vectors are scaled by them and
+    """The factors of an equilibration, ``Ks = diag(D_row) K diag(D_col)``, and the one place where vectors are scaled by them and
     iterates un-scaled.  ``d_col`` / ``d_row``: ``(len,)`` for a shared matrix, ``(len, B)`` for a matrix per LP.  ``sweeps``: the
     Ruiz sweeps run; ``seconds``: the equilibration alone (no vector is scaled in them)."""
     d_col: torch.Tensor
