@@ -196,7 +196,10 @@ int pdlp_tile_limits(pdlp_handle h, int32_t out[6]);
  * /root/reference/enhancements/test_ass.py:322-363): after an adaptive iteration whose trial was REJECTED (scalar "accepted" = 0)
  * this discards the trial -- the old (x, y) is current again, its weight leaves the average, k goes back, the step size stays the
  * shrunk eta' -- so that the iteration can be issued again.  Off the default path (pdlp_algorithm(adaptive_retry=True)); float32 and
- * float64 handles; K x of the old x is recomputed by the next half-step and the running products of the period are dropped. */
+ * float64 handles; K x of the old x is recomputed by the next half-step and the running products of the period are dropped.
+ * Sharded handles: that product multiplies K by the WHOLE restored x (PDLP_BUF_X_CUR after this call), and the iterations exchange
+ * only xbar and y, so the caller must make x of the restored iterate complete over [0, n) -- all-gather PDLP_BUF_X_CUR -- before the
+ * next half-step (PdlpEngine.adaptive_retry does). */
 int pdlp_adaptive_retry(pdlp_handle h);
 /* adaptive rule, part 1: reduce this rank's ||dx||^2, ||dy||^2, dy'K dx into PDLP_BUF_RED[0..2]
  * (all-reduce them across ranks before part 2) -- step.py:91-96 */

@@ -332,6 +332,9 @@ class PdlpEngine(KernelChoice, Exchange):
         """discard the adaptive iteration just taken (its trial was rejected: ``scalars()["accepted"] == 0``) so that it can be
         issued again with the shrunk step size -- ``pdlp_adaptive_retry`` (include/pdlp_hip.h), SURVEY quirk Q1's optional flag"""
         N.check(self.lib.pdlp_adaptive_retry(self.h), "pdlp_adaptive_retry")
+        # the next dual half-step recomputes K x from the WHOLE restored x; sharded iterations exchange xbar and y only, so the other
+        # ranks' blocks of that buffer are not current: gather them (over the process group, whichever driver runs the iterations)
+        self._gather(N.BUF_X_CUR)
 
     # ---- restart machinery --------------------------------------------------------------------------
     def flush_average(self, adaptive: bool = True):
