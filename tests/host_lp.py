@@ -56,7 +56,11 @@ class HostLP:
                                                    self.q / self.d_row, self.l * self.d_col, self.u * self.d_col, dtype=np.float64)
         return self._cache["unscaled"]
 
-    def engine(self, dtype, form="csr", **kw):
+    def engine(self, dtype, form="csr", tile_args=None, before_attach=None, **kw):
+        """``tile_args``: for a tiled form, the ``build_tiles`` keywords of K and of K' (a pair of dicts: lw, rpt, groups, max_rest)
+        in place of the default ``lw=6, rpt=1``; a side whose matrix cannot be tiled with them stays on the CSR kernel, and what the
+        form says about groups and the remainder is then the caller's to assert.  ``before_attach(transpose, tiles)`` sees every
+        tile set before the library does (which does not validate the format)."""
         import torchpdlp_amd as tp
         from torchpdlp_amd.tiled import build_tiles
         t = lambda v, dt=dtype: torch.tensor(np.asarray(v), dtype=dt, device=DEV)
@@ -75,8 +79,15 @@ class HostLP:
         elif form != "csr":
             lim = eng.tile_limits()
             for tr, (rp, ci, va), rows, cols in ((0, eng.K, eng.ml, eng.n), (1, eng.KT, eng.nl, eng.m)):
-                tl = build_tiles(rp, ci, va, rows, cols, lw=6, rpt=1, groups=2 if form == "tiles_groups" else 1,
-                                 max_groups=lim["max_groups"], kernel_limits=(lim["rpt_max"], lim["cap"], lim["nt"]))
+                args = dict(lw=6, rpt=1, groups=2 if form == "tiles_groups" else 1) if tile_args is None else tile_args[tr]
+                tl = build_tiles(rp, ci, va, rows, cols, max_groups=lim["max_groups"], kernel_limits=(lim["rpt_max"], lim["cap"], lim["nt"]),
+                                 **args)
+                if tile_args is not None:
+                    if tl is not None:
+                        if before_attach is not None:
+                            before_attach(tr, tl)
+                        eng.attach_tiles(tr, tl)
+                    continue
                 assert tl is not None, (form, tr)
                 eng.attach_tiles(tr, tl)
                 if form == "tiles_groups":

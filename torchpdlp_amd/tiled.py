@@ -179,7 +179,9 @@ def choose_lw(nrows: int, nnz: int, ncols: int) -> int:
 
 
 def normalize_groups(groups: int, npanel: int, max_groups: int = 8) -> int:
-    """the kernel gives every group ceil(npanel/groups) panels: shrink the count until no group is empty"""
+    """the group count the builder settles on: with ceil(npanel/groups) panels per group, shrink the count until no group would be
+    empty.  (Stricter than the library: k_tiled_fused gives group g of n the panels [g*npanel/n, (g+1)*npanel/n), which leaves no
+    group empty for any n <= npanel, and ``pdlp_attach_tiles`` accepts any such n up to the row-sum scratch's limit.)"""
     g = max(1, min(int(groups), npanel, max_groups))
     ppg = -(-npanel // g)
     return -(-npanel // ppg)
