@@ -517,6 +517,16 @@ int pdlp_batch_product(pdlp_handle h, const pdlp_batch* b, int transpose, const 
  * count at which the LP of column b was admitted, and the adaptive rule of column b uses k0 + it + 1 - k_start[b] where
  * pdlp_batch_iterate uses k0 + it + 1.  k_start = NULL: pdlp_batch_iterate, bit for bit. */
 int pdlp_batch_iterate_from(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0, const int64_t* k_start);
+/* `iters` iterations of the restarted, reflected Halpern iteration of every live LP, no host synchronisation (no counterpart in
+ * the reference; pdlp_halpern_iterate per column).  The iterate z is in x / y and is updated in place; the candidate T(z) -- one
+ * fixed PDHG step of pdlp_batch_iterate from z, bit for bit -- goes to x_avg / y_avg (PDLP_AVG), xbar is written as that step
+ * writes it, and the anchor is the restart point x_last / y_last: z+ = a (2 T(z) - z) + bw z_last with a = (t+1)/(t+2),
+ * bw = 1/(t+2), divided in double and rounded once to the working precision.
+ * t_since: device array [Bp], the iterations of LP b since its last restart BEFORE this call (0 for a fresh or just restarted LP);
+ * iteration `it` of the call uses t = t_since[b] + it.  x_prev, y_prev, x_sum, y_sum, dy, eta_sum, wpend and part are neither read
+ * nor written; frozen and padding columns are never stored into.  pdlp_batch_restart with action 2 adopts the candidate.
+ * PDLP_ERR_INVALID for iters < 0 or t_since = NULL. */
+int pdlp_batch_halpern_iterate(pdlp_handle h, const pdlp_batch* b, int iters, const int64_t* t_since);
 /* The source of an admission: N columns, in the working precision, on the device. */
 typedef struct pdlp_batch_feed {
     int32_t N;                  /* columns of every array below                                                      */

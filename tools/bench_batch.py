@@ -14,12 +14,19 @@ same run, and the end-to-end comparison on a ``matrix_noise`` family (set-up -- 
     python tools/bench_batch.py --shapes 1m --batches 8 --skip-e2e --reps 1   # the rocprofv3 --kernel-trace --stats run
     python tools/bench_batch.py --per-lp-values         # + a matrix per LP
     python tools/bench_batch.py --stream 32             # a family of 256 LPs: streamed, chunked loop, one plain batch
+    python tools/bench_batch.py --halpern               # the Halpern iteration per LP against the fixed-step batched iteration
 
 ``--stream SLOTS`` solves one ``gen_lp_family`` of ``--family`` LPs (50k x 50k) three ways in one process -- streamed through SLOTS
 columns (``solve_lp_batch(slots=SLOTS)``), as the loop of plain ``solve_lp_batch`` calls over chunks of SLOTS LPs that a user writes
 without it, and as one plain batch -- each timed ``--reps`` times after a warm-up, all at the group width the chunks get.  It
 prints the three lists of wall times, the distribution of the per-LP iteration counts, and whether the three agree bit for bit.
 ``--spread F``: that fraction of the LPs starts at its built-in optimum (solved at its first check), which spreads the counts.
+
+``--halpern`` measures ``solve_lp_batch(halpern=True)`` (nothing else is run).  Rate: on ONE ``BatchEngine`` per B in --batches
+(default 32,8; the 50k shape), HIP events around ``iterate(steps, adaptive=False)`` and ``halpern_iterate(steps)``, alternating,
+--reps windows each after a warm-up of both -- ms per LP-iteration and their ratio, with the spread of the windows.  End to end:
+the 32-LP family solved with the fixed step and with ``halpern=True`` (primal weight on both sides): seconds, and per LP the
+iterations and KKT passes of the two methods and their ratios.
 """
 import argparse
 import json
@@ -253,6 +260,77 @@ def stream_family(slots, family, spread, reps, rows=50_000, only_streamed=False)
     return out
 
 
+def halpern_rates(batches, steps, rounds, warm, rows=50_000):
+    """ms per LP-iteration of the two batched iterations on one engine, alternating windows timed by HIP events on its stream"""
+    dev = torch.device("cuda", 0)
+    lp = tp.gen_lp(rows, rows, 5, seed=0, device=dev)
+    K = tp.CsrPair(lp.m, lp.n, lp.rowptr, lp.colidx, lp.val)
+    eng = tp.PdlpEngine.from_full(K, lp.c, lp.q, lp.l, lp.u, lp.m_ineq)
+    eta = 0.9 / tp.solver.estimate_sigma(eng, power_iters=20, seed=0)
+    del eng
+    g = torch.Generator(device=dev).manual_seed(1)
+    out = []
+    for B in batches:
+        Q = lp.q.view(-1, 1) * (1 + 0.01 * torch.randn(lp.m, B, generator=g, device=dev))
+        be = BatchEngine(K, lp.m_ineq, lp.c, Q, lp.l, lp.u, B)
+        be.start(np.full(B, eta, np.float32), np.ones(B, np.float32))
+        count = [0]
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            be.synchronize()
+            e0.record(be.stream)
+            fn()
+            e1.record(be.stream)
+            e1.synchronize()
+            count[0] += steps
+            return e0.elapsed_time(e1) / steps / B
+
+        pdhg = lambda: be.iterate(steps, False, count[0])
+        halp = lambda: be.halpern_iterate(steps, np.full(B, count[0], np.int64))
+        be.iterate(warm, False, 0), be.halpern_iterate(warm, np.zeros(B, np.int64))
+        timed(pdhg), timed(halp)                                    # warm-up of both
+        ms = {"fixed": [], "halpern": []}
+        for _ in range(rounds):
+            ms["fixed"].append(timed(pdhg))
+            ms["halpern"].append(timed(halp))
+        spread = {k: (max(v) - min(v)) / float(np.median(v)) for k, v in ms.items()}
+        row = dict(B=B, W=be.W, shape=f"{rows}x{rows}", steps=steps, ms_per_lp_iteration=ms, window_spread=spread,
+                   halpern_over_fixed=float(np.median(ms["halpern"]) / np.median(ms["fixed"])),
+                   halpern_over_fixed_per_window=[h / f for h, f in zip(ms["halpern"], ms["fixed"])])
+        out.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+        del be
+    return out
+
+
+def halpern_end_to_end(B=32, rows=50_000):
+    """the tool's 32-LP family with the fixed step and with halpern=True, primal weight on both sides"""
+    dev = torch.device("cuda", 0)
+    f = tp.gen_lp_family(rows, rows, 5, B, seed=0)
+    K = tp.CsrPair(f.m, f.n, f.rowptr, f.colidx, f.val).to(dev)
+    C, Q, L, U = (v.to(dev) for v in (f.C, f.Q, f.L, f.U))
+    prob = (C[:, 0], K, Q[:, 0], f.m_ineq, L[:, 0], U[:, 0])
+    out = dict(B=B, shape=f"{rows}x{rows}", tol=1e-4)
+    res = {}
+    for name, kw in (("fixed", {}), ("halpern", dict(halpern=True))):
+        tp.solve_lp_batch(prob, C[:, :2], Q[:, :2], L[:, :2], U[:, :2], device=dev, seed=0, max_kkt=200, primal_weight_update=True, **kw)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = res[name] = tp.solve_lp_batch(prob, C, Q, L, U, device=dev, seed=0, time_limit=600, primal_weight_update=True, **kw)
+        torch.cuda.synchronize()
+        rel = lambda a, b: abs(a - b) / (1 + abs(b))
+        out[name] = dict(seconds=time.perf_counter() - t0, solved=sum(s == "Solved" for s in r.status),
+                         iterations=r.iterations.tolist(), kkt_passes=r.kkt_passes.tolist(), restarts=r.restarts.tolist(),
+                         max_rel_obj_diff_vs_optimum=max(rel(r.objective[b], f.opt_obj[b]) for b in range(B)))
+    for key in ("iterations", "kkt_passes"):
+        h, p = np.asarray(getattr(res["halpern"], key), float), np.asarray(getattr(res["fixed"], key), float)
+        out[f"{key}_ratio"] = dict(of_sums=float(h.sum() / p.sum()), of_max=float(h.max() / p.max()), per_lp_min=float((h / p).min()),
+                                   per_lp_median=float(np.median(h / p)), per_lp_max=float((h / p).max()))
+    out["seconds_ratio"] = out["halpern"]["seconds"] / out["fixed"]["seconds"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="50k,1m")
@@ -267,7 +345,16 @@ def main():
     ap.add_argument("--family", type=int, default=256, help="LPs of the --stream family")
     ap.add_argument("--spread", type=float, default=0.0, help="fraction of the --stream family that starts at its optimum")
     ap.add_argument("--stream-only", action="store_true", help="--stream: the streamed solve alone (the kernel-trace run)")
+    ap.add_argument("--halpern", action="store_true", help="the Halpern iteration per LP against the fixed-step batched iteration: "
+                    "the rate on one engine (alternating windows) and the 32-LP family end to end (nothing else is run)")
     a = ap.parse_args()
+    if a.halpern:
+        batches = [32, 8] if a.batches == ap.get_default("batches") else [int(b) for b in a.batches.split(",")]
+        doc = dict(device=torch.cuda.get_device_name(0), dtype="float32", halpern_rates=halpern_rates(batches, a.steps, a.reps, a.warm))
+        if not a.skip_e2e:
+            doc["halpern_end_to_end"] = halpern_end_to_end()
+        print(json.dumps(doc, indent=1))
+        return
     if a.stream:
         print(json.dumps(dict(device=torch.cuda.get_device_name(0), dtype="float32",
                               stream=stream_family(a.stream, a.family, a.spread, a.reps, only_streamed=a.stream_only)), indent=1))

@@ -139,6 +139,7 @@ SIGNATURES = {
     "pdlp_batch_attach_matrices": (_I, [_H, _I, _P, _P, _P, _P]),
     "pdlp_batch_product": (_I, [_H, C.POINTER(PdlpBatch), _I, _P, _P]),
     "pdlp_batch_iterate_from": (_I, [_H, C.POINTER(PdlpBatch), _I, _I, _I64, _P]),
+    "pdlp_batch_halpern_iterate": (_I, [_H, C.POINTER(PdlpBatch), _I, _P]),
     "pdlp_batch_admit": (_I, [_H, C.POINTER(PdlpBatch), _I, _P, _P, C.POINTER(PdlpBatchFeed)]),
     "pdlp_batch_retire": (_I, [_H, C.POINTER(PdlpBatch), _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I]),
     "pdlp_spmv": (_I, [_H, _I, _P, _P]),

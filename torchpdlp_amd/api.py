@@ -230,7 +230,7 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
                    seed: Optional[int] = None, compat: bool = True, x_init=None, y_init=None, trace=None, verbose: bool = False,
                    group_width: Optional[int] = None, b0=None, report: bool = True, K_values=None, setup_times: Optional[dict] = None,
                    slots: Optional[int] = None, schedule: Optional[dict] = None, pock_chambolle: bool = False,
-                   **unsupported) -> BatchResult:
+                   halpern: bool = False, **unsupported) -> BatchResult:
     """Solve B LPs that share ``K`` (and ``m_ineq``) of ``problem`` and differ in ``c``, ``q``, ``l``, ``u`` in one batch.
 
     ``K_values`` ``(nnz, B)``: a constraint matrix per LP.  The LPs then share only the sparsity pattern of ``problem``'s K (its row
@@ -256,10 +256,17 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
     a shared K and per LP with ``K_values``.  ``report`` (default on): the reduced costs, row activities, residuals and gaps of every LP
     (``BatchResult``'s fields; ``res[i]`` passes them on).  ``trace``: a list that receives B dicts (``kkt``, ``omega``, ``restarts``).  Flags of
     ``solve_lp`` that have no batched form (sharding, fishnet, infeasibility detection, ``adaptive_retry``, the direct exchange,
-    ``precision="mixed"``) raise ``ValueError``."""
+    ``precision="mixed"``) raise ``ValueError``.
+
+    ``halpern`` (not in the reference): the restarted, reflected Halpern iteration per LP instead of averaged PDHG, with the fixed
+    step (``solve_lp``'s flag; ``BatchDriver``): one KKT pass per restart check instead of three.  Works with
+    ``precondition``, ``pock_chambolle``, ``primal_weight_update``, ``x_init`` / ``y_init``, ``K_values``, ``slots``, ``report`` and
+    ``trace`` in float32 and float64; ``ValueError`` with ``adaptive_stepsize``."""
     import numpy as np
-    from .batch import batch_size, check_slots, pdlp_algorithm_batch
+    from .batch import HALPERN_BATCH_REFUSED, batch_size, check_slots, pdlp_algorithm_batch
     _check_pock_chambolle(pock_chambolle, precondition)
+    if halpern and adaptive_stepsize:
+        raise ValueError(HALPERN_BATCH_REFUSED)
     for name, v in unsupported.items():
         if name == "precision":
             if v is not None:
@@ -320,7 +327,8 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
         Ks, m_ineq, C_, Q, L, U, device, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period,
         precondition=precondition, primal_update=primal_weight_update, adaptive=adaptive_stepsize, data_precond=data_precond,
         time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init, seed=seed, traces=traces, group_width=group_width,
-        b0=b0, report=rep, K_values=KsV, KT_values=KsTV, setup_times=setup_times, slots=slots if streamed else None, schedule=schedule)
+        b0=b0, report=rep, K_values=KsV, KT_values=KsTV, setup_times=setup_times, slots=slots if streamed else None, schedule=schedule,
+        halpern=halpern)
     if trace is not None:
         trace.extend(traces)
     if precondition:                         # x = D_col x_s, y = D_row y_s (pdhg.py:161-162), per LP with a matrix each

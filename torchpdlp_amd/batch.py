@@ -28,6 +28,7 @@ from .solver import estimate_sigma, power_iteration_start, precond_factors, reso
 from .sparse import CsrPair
 
 batch_decisions, kkt_finish, termination = restart_decision, kkt_from_sums, terminated      # (their earlier names)
+HALPERN_BATCH_REFUSED = ("halpern=True runs the fixed step of every LP of a batch: not with adaptive (adaptive_stepsize)")
 _DT = {torch.float32: N.PDLP_F32, torch.float64: N.PDLP_F64}
 
 
@@ -96,6 +97,7 @@ class BatchEngine:
                                 p(self.eta), p(self.omega), p(self.eta_sum), p(self.wpend), p(self.live), p(self.action),
                                 p(self.part), p(self.out))
         self.k_start = None        # [Bp] int64 once the batch streams a family (enable_stream): the count at each column's admission
+        self.t_since = None        # [Bp] int64 once the batch runs the Halpern iteration (halpern_iterate)
 
     def _pad(self, v: Optional[torch.Tensor], ln: int) -> torch.Tensor:
         """a fresh population [ln, Bp]: ``v`` [ln, B] in the columns of the LPs (1-D: the same in each; None: zeros), padding zero"""
@@ -144,6 +146,16 @@ class BatchEngine:
                                                      self.k_start.data_ptr()), "pdlp_batch_iterate_from")
             return
         N.check(self.lib.pdlp_batch_iterate(self.eng.h, C.byref(self.desc), int(iters), int(adaptive), int(k0)), "pdlp_batch_iterate")
+
+    def halpern_iterate(self, iters: int, t_since):
+        """``pdlp_batch_halpern_iterate``: ``iters`` iterations of the restarted, reflected Halpern iteration of every live LP, no
+        host synchronisation.  ``t_since`` ([B] or [Bp] host integers): every LP's iterations since its last restart before the
+        call.  Afterwards ``N.CUR`` is the Halpern iterate and ``N.AVG`` the candidate, one fixed PDHG step from it."""
+        if self.t_since is None:
+            self.t_since = torch.zeros(self.Bp, dtype=torch.int64, device=self.device)
+        self.set_scalars(t_since=np.asarray(t_since, np.int64))
+        N.check(self.lib.pdlp_batch_halpern_iterate(self.eng.h, C.byref(self.desc), int(iters), self.t_since.data_ptr()),
+                "pdlp_batch_halpern_iterate")
 
     def enable_stream(self):
         """the state of a batch whose columns change hands (``admit`` / ``retire``): ``k_start``, and sums of its own for the
@@ -244,11 +256,20 @@ class BatchEngine:
 
 class BatchDriver:
     """``PdhgDriver``'s state machine (solver.py) vectorised over the LPs of a batch: numpy arrays of per-LP counters and scalars
-    in the working precision, one host read per restart check (and one more when any LP restarts)."""
+    in the working precision, one host read per restart check (and one more when any LP restarts).
+
+    ``halpern=True``: the restarted, reflected Halpern iteration per LP with ``PdhgDriver``'s rules.  A
+    segment is ``be.halpern_iterate``; a check is ONE KKT pass at the candidate ``N.AVG`` and hands ``restart_decision``
+    ``inf``, the candidate's KKT error and the candidate's error at the previous check of the LP's restart period (``inf`` at the
+    first); a restart -- or the KKT-pass cap, or the clock, between restarts -- adopts the candidate (action 2).  KKT passes per
+    LP: the iterations, 1 per check, 2 per restart."""
 
     def __init__(self, be: BatchEngine, q_norm, c_norm, restart_period=40, primal_update=False, adaptive=False, precondition=False,
-                 tol=1e-4, max_kkt=100_000, traces=None):
+                 tol=1e-4, max_kkt=100_000, traces=None, halpern=False):
         self.be, self.period = be, int(restart_period)
+        self.halpern = bool(halpern)
+        if self.halpern and adaptive:
+            raise ValueError(HALPERN_BATCH_REFUSED)
         self.primal_update, self.adaptive, self.precondition = bool(primal_update), bool(adaptive), bool(precondition)
         self.tol, self.max_kkt, self.traces = tol, int(max_kkt), traces
         self.t = t = np_type(be.dtype)
@@ -256,6 +277,7 @@ class BatchDriver:
         self.q_norm, self.c_norm = np.asarray(q_norm, t), np.asarray(c_norm, t)
         self.k, self.n, self.j, self.tt = (np.zeros(B, np.int64) for _ in range(4))
         self.kkt_first = np.zeros(B, t)
+        self.k_prev_cand = np.full(B, np.inf, t)        # Halpern: the candidate's KKT error at the previous check of the period
         self.omega = np.ones(B, t)
         self.live = np.ones(B, bool)
         self.status = [STATUS_KKT_LIMIT] * B
@@ -273,6 +295,7 @@ class BatchDriver:
         self.q_norm[cols], self.c_norm[cols], self.omega[cols] = q_norm, c_norm, omega
         for a in (self.k, self.n, self.j, self.tt, self.kkt_first):
             a[cols] = 0
+        self.k_prev_cand[cols] = np.inf
         self.obj[cols] = np.nan
         self.live[cols] = True
         for i in cols:
@@ -289,10 +312,12 @@ class BatchDriver:
         if not self._segment(live, time_left):
             return
         if self.k_global % self.period == 0:                                 # pdhg.py:115 (tt = k mod period for every live LP)
-            action, capped, chosen = self._restart_check(live)
+            action, capped, chosen = self._halpern_check(live) if self.halpern else self._restart_check(live)
         else:                                                                # only the cap ends an inner loop between checks
             capped = live & (self.j >= self.max_kkt)
             action, chosen = np.where(capped, 1, 0).astype(np.int32), None
+        if self.halpern:           # a capped LP keeps its candidate (inside the bounds), never the reflected iterate
+            action = np.where(capped & (self.tt > 0), 2, action).astype(np.int32)
         if action.any():
             self._after_restart(action, capped, chosen)
 
@@ -300,13 +325,20 @@ class BatchDriver:
         """PDHG iterations of every live LP up to the next check or the first KKT-pass cap (pdhg.py:76-112); False when the clock
         or the cap ends the batch instead"""
         if not time_left:                                                    # pdhg.py:68-74, the global clock
+            if self.halpern and (live & (self.tt > 0)).any():                # the returned point is the candidate, as in run_pdlp
+                self.be.set_scalars(action=np.where(live & (self.tt > 0), 2, 0).astype(np.int32))
+                self.be.restart(0)
+                self.be.set_scalars(action=np.zeros(self.be.B, np.int32))
             self._finish(np.flatnonzero(live), STATUS_TIME_LIMIT)
             return False
         iters = min(self.period - self.k_global % self.period, int((self.max_kkt - self.j[live]).min()))
         if iters <= 0:                                                       # max_kkt <= 0: the reference's loop never runs
             self._finish(np.flatnonzero(live), STATUS_KKT_LIMIT)
             return False
-        self.be.iterate(iters, self.adaptive, self.k_global)
+        if self.halpern:
+            self.be.halpern_iterate(iters, self.tt)
+        else:
+            self.be.iterate(iters, self.adaptive, self.k_global)
         self.k_global += iters
         self.k[live] += iters
         self.j[live] += iters
@@ -332,6 +364,25 @@ class BatchDriver:
         chosen = {key: np.where(dec["use_avg"], r[1][key], r[0][key]) for key in r[0]}
         return dec["action"], dec["capped"], chosen
 
+    def _halpern_check(self, live):
+        """the restart check of the Halpern mode for every live LP: one KKT pass at the candidate, one host read, the rules of
+        ``restart_decision`` unchanged -> (action, capped, the residuals at the candidate)"""
+        be, t = self.be, self.t
+        be.kkt(N.AVG, 1)
+        r = kkt_from_sums(be.read_out()[1], self.omega, t)
+        self.j[live] += 1
+        k_cur, k_cand, k_prev = np.full(be.B, np.inf, t), t(r["kkt"]), self.k_prev_cand.copy()
+        self.k_prev_cand[live] = k_cand[live]
+        dec = restart_decision(k_cur, k_cand, k_prev, self.kkt_first, self.tt, self.k, self.j, live, self.max_kkt, t)
+        if self.traces is not None:
+            for i in np.flatnonzero(live):
+                tr = self.traces[self.lp[i]]
+                tr["kkt"] += [float(k_cur[i]), float(k_cand[i]), float(k_prev[i])]
+                if dec["crit"][i] >= 0:
+                    tr["restarts"].append((int(dec["crit"][i]), int(self.tt[i]), 1))
+        action = np.where(dec["crit"] >= 0, 2, dec["action"]).astype(np.int32)       # a restart is always at the candidate
+        return action, dec["capped"], r
+
     def _after_restart(self, action, capped, chosen):
         """pdhg.py:148-177 for the LPs that leave their inner loop: n += 1, primal weight, KKT_first, residuals, termination test"""
         be, t = self.be, self.t
@@ -346,6 +397,7 @@ class BatchDriver:
         be.set_scalars(action=np.zeros(be.B, np.int32))
         self.n[act] += 1
         self.tt[act] = 0
+        self.k_prev_cand[act] = np.inf
         if self.primal_update:                                               # pdhg.py:150-151
             self.omega[act] = primal_weight(out[0, act, 0], out[0, act, 1], self.omega[act], 0.5, t)
             be.set_scalars(omega=self.omega)
@@ -551,7 +603,8 @@ def _solve_stream(drv: BatchDriver, B, perm, C_, Q, L, U, x_init, y_init, K_valu
 def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, tol=1e-4, verbose=False, restart_period=40,
                          precondition=False, primal_update=False, adaptive=False, data_precond=None, time_limit=3600, time_used=0,
                          x_init=None, y_init=None, *, b0=None, sigma=None, seed=None, traces=None, group_width=None,
-                         report=None, K_values=None, KT_values=None, setup_times=None, slots=None, schedule=None):
+                         report=None, K_values=None, KT_values=None, setup_times=None, slots=None, schedule=None,
+                         halpern=False):
     """``pdlp_algorithm`` on B LPs with the same ``K`` at once.  ``C_``, ``Q``, ``L``, ``U``: 1-D (shared) or [len, B] (one column
     per LP), of the scaled problem when ``precondition`` (then ``data_precond`` = ``ruiz_precondition``'s: ``D_col``, ``D_row``
     give the un-scaled residuals).  ``traces``: a list of B dicts (``kkt``, ``omega``, ``restarts``) that receive every LP's trace.
@@ -567,9 +620,14 @@ def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, t
     ``slots`` < B: the family is streamed through ``slots`` columns (``_solve_stream``: the same results, bit for bit, from the
     memory of ``slots`` LPs); ``c, q, l, u, x_init, y_init, K_values`` may then stay on the host.  ``schedule``: a dict that receives
     ``column``, ``admitted_at``, ``retired_at`` ([B]) of such a run.
+    ``halpern`` (the reference has no counterpart): the restarted, reflected Halpern iteration per LP instead of averaged PDHG, with
+    the fixed step (``BatchDriver``); every returned iterate is a candidate, inside the bounds.  ``ValueError`` with
+    ``adaptive``.
     Returns ``(X, Y, obj, k, n, j, status, total_time)`` with X [n, B], Y [m, B] (the scaled iterates when preconditioned, like
     ``pdlp_algorithm``'s x) and numpy arrays / a list of status strings per LP."""
     t0 = time.time()
+    if halpern and adaptive:
+        raise ValueError(HALPERN_BATCH_REFUSED)
     B = batch_size(C_, Q, L, U, K_values)
     streamed = check_slots(slots, B, group_width, K.val.dtype if isinstance(K, CsrPair) else C_.dtype, K_values is not None, precondition)
     Kp = CsrPair.from_any(K, device=resolve_device(device))
@@ -589,7 +647,7 @@ def pdlp_algorithm_batch(K, m_ineq, C_, Q, L, U, device=None, max_kkt=100_000, t
     perm = Kp.transpose_perm() if streamed and K_values is not None else None
     qn, cn, sigma = _setup(be, B, Q, C_, K_values, perm, b0, sigma, seed, setup_times)
     drv = BatchDriver(be, qn[:width].copy(), cn[:width].copy(), restart_period, primal_update=primal_update, adaptive=adaptive,
-                      precondition=precondition, tol=tol, max_kkt=max_kkt, traces=traces)
+                      precondition=precondition, tol=tol, max_kkt=max_kkt, traces=traces, halpern=halpern)
     time_left = lambda: time.time() - t0 + time_used < time_limit
     if streamed:
         X, Y, rc, act, sums, res = _solve_stream(drv, B, perm, C_, Q, L, U, x_init, y_init, K_values, qn, cn, sigma, time_left, verbose,

@@ -131,6 +131,23 @@ template <typename T, int W, bool ADAPT> int batch_iterate_w(pdlp_handle h, cons
     return PDLP_OK;
 }
 
+// the restarted, reflected Halpern iteration: the two products of batch_iterate_w under BHalpernPrimal / BHalpernDual; the iterate
+// is updated in place (x, y), the candidate goes to x_avg / y_avg, the anchor is x_last / y_last
+template <typename T, int W> int batch_halpern_w(pdlp_handle h, const pdlp_batch* b, int iters, const int64_t* t_since)
+{
+    const BSelLive live{b->live};
+    const T *eta = (const T*)b->eta, *omega = (const T*)b->omega;
+    for (int it = 0; it < iters; ++it) {
+        const BHalpernWeights<T> w{t_since, (int64_t)it};
+        const BHalpernPrimal<T> ep{(T*)b->x, (T*)b->xbar, (T*)b->x_avg, (const T*)b->x_last, (const T*)b->c, (const T*)b->l,
+                                   (const T*)b->u, b->c_per_lp, b->l_per_lp, b->u_per_lp, eta, omega, w};
+        const BHalpernDual<T> ed{(T*)b->y, (T*)b->y_avg, (const T*)b->y_last, (const T*)b->q, b->q_per_lp, eta, omega, (int)h->p.m_ineq, w};
+        BATCH_TRY((batch_launch<T, W>(h, b, true, (const T*)b->y, live, ep, nullptr)));
+        BATCH_TRY((batch_launch<T, W>(h, b, false, (const T*)b->xbar, live, ed, nullptr)));
+    }
+    return PDLP_OK;
+}
+
 template <typename T> int batch_average_t(pdlp_handle h, const pdlp_batch* b, int adaptive)
 {
     const int64_t tn = h->p.n * (int64_t)b->Bp, tm = h->p.m * (int64_t)b->Bp;
@@ -230,6 +247,15 @@ int pdlp_batch_iterate_from(pdlp_handle h, const pdlp_batch* b, int iters, int a
 int pdlp_batch_iterate(pdlp_handle h, const pdlp_batch* b, int iters, int adaptive, int64_t k0)
 {
     return pdlp_batch_iterate_from(h, b, iters, adaptive, k0, nullptr);
+}
+
+int pdlp_batch_halpern_iterate(pdlp_handle h, const pdlp_batch* b, int iters, const int64_t* t_since)
+{
+    if (iters < 0 || !t_since) return PDLP_ERR_INVALID;
+    const int rc = batch_check(h, b);
+    if (rc != PDLP_OK) return rc;
+    Range range("pdlp: batch Halpern iterations", h->stream);
+    return batch_dispatch(h, b, [&](auto t, auto w) { return batch_halpern_w<TYPE(t), VAL(w)>(h, b, iters, t_since); });
 }
 
 int pdlp_batch_admit(pdlp_handle h, const pdlp_batch* b, int count, const int32_t* cols, const int32_t* ids, const pdlp_batch_feed* f)

@@ -104,6 +104,62 @@ template <typename T, bool ADAPT> struct BDual {
     }
 };
 
+// Reflected Halpern iteration per column (pdlp_batch_halpern_iterate; the reference has no counterpart).  The weights of column
+// b at iteration t = t_since[b] + it since its last restart: a = (t+1)/(t+2), bw = 1/(t+2), divided in double and rounded once
+// to the working type (rules.halpern_weights); t stays in 64 bits.
+template <typename T> struct BHalpernWeights {
+    const int64_t* t_since; int64_t it;
+    __device__ void operator()(int b, T& a, T& bw) const
+    {
+        const int64_t t = t_since[b] + it;
+        const double t2 = (double)(t + 2);
+        a = (T)((double)(t + 1) / t2);
+        bw = (T)(1.0 / t2);
+    }
+};
+
+// Primal half: the candidate x' = BPrimal<T, false>'s X goes to x_avg and xbar = x' + (x' - x) is stored as there (one fixed
+// batched PDHG step from z bit for bit); the iterate becomes the reflected point pulled towards the anchor, x+ = a xbar + bw x_last
+// (HalpernPrimalEpi).  In place: the launch gathers y and touches element `at` of the x side only.  No sums, no x_prev.
+template <typename T> struct BHalpernPrimal {
+    static constexpr int NA = 0;
+    T* X; T* Xbar; T* Xcand; const T* Xlast; const T* c; const T* l; const T* u; int cs, ls, us;
+    const T* eta; const T* omega; BHalpernWeights<T> w;
+    __device__ void operator()(int j, size_t at, int b, int, T kty, double*) const
+    {
+        T a, bw;
+        w(b, a, bw);                                  // before the first store: the load of t_since and the divisions overlap the others
+        const T xo = X[at], xl = Xlast[at];
+        const T tau = eta[b] / omega[b];
+        T v = xo - tau * (BCOL(c, cs, j, at) - kty);
+        const T lo = BCOL(l, ls, j, at), hi = BCOL(u, us, j, at);
+        v = v < lo ? lo : v;
+        v = v > hi ? hi : v;
+        Xcand[at] = v;
+        const T xb = v + (v - xo);
+        Xbar[at] = xb;
+        X[at] = a * xb + bw * xl;
+    }
+};
+
+// Dual half: the candidate y' = BDual<T, false>'s Y goes to y_avg; y+ = a (2y' - y) + bw y_last (HalpernDualEpi).  In place: the
+// launch gathers xbar and touches element `at` of the y side only.
+template <typename T> struct BHalpernDual {
+    static constexpr int NA = 0;
+    T* Y; T* Ycand; const T* Ylast; const T* q; int qs; const T* eta; const T* omega; int ineq_end; BHalpernWeights<T> w;
+    __device__ void operator()(int i, size_t at, int b, int, T kx, double*) const
+    {
+        T a, bw;
+        w(b, a, bw);                                  // (as in the primal half)
+        const T yo = Y[at], yl = Ylast[at];
+        const T sigma = eta[b] * omega[b];
+        T v = yo + sigma * (BCOL(q, qs, i, at) - kx);
+        if (i < ineq_end && v < (T)0) v = (T)0;
+        Ycand[at] = v;
+        Y[at] = a * ((T)2 * v - yo) + bw * yl;
+    }
+};
+
 // the adaptive rule's other two sums (step.py:96-100): (K'dy).dx and ||dx||^2; rows of K', gathers dy
 template <typename T> struct BDen {
     static constexpr int NA = 2;
