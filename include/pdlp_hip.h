@@ -235,6 +235,24 @@ int pdlp_fixed_advance(pdlp_handle h, int iters);
  * pdlp_flush_average and pdlp_compute_average return PDLP_ERR_STATE (they would overwrite the candidate). */
 int pdlp_halpern_iterate(pdlp_handle h, int iters);
 
+/* ---- two-sided constraint rows -------------------------------------------------------------------------------------------
+ * q_i <= (K x)_i <= q_upper_i on the inequality rows (i < m_ineq) without entering the row twice (no counterpart in the
+ * reference, whose reader splits a RANGES row into two ">=" rows).  q_upper_local: this handle's rows, in the working dtype,
+ * device memory the caller keeps alive like q; NULL switches two-sided rows off again.  Entries: q_upper_i >= q_i, +inf = a
+ * one-sided row exactly as without this call, q_upper_i == q_i behaves as an equality row; the entries of the equality rows are
+ * not read.  The library does not inspect the values (they are device memory): the caller validates them.
+ * Sign of y on a two-sided row: y_i > 0 the lower side is active, y_i < 0 the upper side.  With k = (K xbar)_i the dual
+ * half-step (fixed, adaptive and Halpern) forms a = y + sigma (q - k) as always and b = y + sigma (q_upper - k), and
+ * y' = a if a > 0, b if b < 0, else 0; pdlp_kkt_local and pdlp_report_local add max(k - q_upper, 0)^2 to the primal residual's
+ * sum and take q_upper_i y_i instead of q_i y_i in the dual objective where y_i < 0 and q_upper_i is finite.  The variable side,
+ * the restart distance and the averages do not change.
+ * The call drops the captured graphs (PDLP_OPT_GRAPH captures again with the new functors) and what the handle carries from a KKT
+ * pass: the candidates' products and the kept K'y.
+ * PDLP_ERR_STATE: PDLP_MIXED handles (delta mode or not), a shard of a problem, a handle with a communicator or a peer exchange.
+ * While it is set, pdlp_infeas_begin / pdlp_infeas_local, pdlp_mv_steps / pdlp_mv_gap / pdlp_mv_product, pdlp_set_delta,
+ * pdlp_comm_init and pdlp_peer_connect return PDLP_ERR_STATE. */
+int pdlp_set_row_upper(pdlp_handle h, const void* q_upper_local);
+
 /* ---- sharded problems: the exchange inside the library (RCCL over xGMI) ------------------------------------------------
  * One process per GPU; rank r owns block r of the constraints and of the variables (equal, padded blocks -- the layout of
  * torchpdlp_amd/distributed.py).  The reference is single-device, so these have no counterpart there; SURVEY.md 8b sketched

@@ -16,7 +16,7 @@ from .ops import (KKT_error, adaptive_one_step_pdhg, compute_residuals_and_duali
 from .precondition import (Scaling, equilibrate, equilibrate_matrix, pock_chambolle_pass, ruiz_precondition,   # noqa: F401
                            ruiz_precondition_batch)
 from .synthetic import LPFamily, SyntheticLP, gen_lp, gen_lp_family       # noqa: F401
-from .mps import mps_to_standard_form, parse_mps                         # noqa: F401
+from .mps import mps_to_ranged_form, mps_to_standard_form, parse_mps                         # noqa: F401
 from .api import BatchResult, LPResult, report_fields, solve_lp, solve_lp_batch   # noqa: F401
 from .batch import BatchDriver, BatchEngine, batch_decisions, pdlp_algorithm_batch   # noqa: F401
 from .spectral_casting import fishnet, sample_points, spectral_cast      # noqa: F401

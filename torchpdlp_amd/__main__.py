@@ -16,7 +16,7 @@ import sys
 import torch
 
 from .api import solve_lp
-from .mps import mps_to_standard_form
+from .mps import mps_to_ranged_form, mps_to_standard_form
 
 COLUMNS = ["File", "Objective", "Iterations (k)", "Restarts (n)", "KKT Passes (j)", "Time (s)", "Status"]
 
@@ -41,6 +41,9 @@ def parse_args(argv=None):
     p.add_argument("--halpern", action="store_true",
                    help="not in the reference's CLI: the restarted, reflected Halpern iteration instead of averaged PDHG (fixed step; "
                         "not with --adaptive_stepsize, --infeasibility_detect, --dtype mixed or several ranks)")
+    p.add_argument("--ranged_rows", action="store_true",
+                   help="not in the reference's CLI: a RANGES row stays one two-sided row q <= a'x <= q_upper instead of two >= rows "
+                        "(one GPU, fp32 / fp64; not with --infeasibility_detect, --fishnet or --adaptive_retry)")
     p.add_argument("--direct_exchange", action="store_true",
                    help="several ranks of one node (not in the reference's CLI): iterate without collectives -- every half-step stores "
                         "its block straight into the other ranks' memory over HIP IPC / xGMI; cross-checked against the "
@@ -131,8 +134,11 @@ def main(argv=None) -> int:
         dtype = torch.float32 if args.dtype == "fp32" else torch.float64
         try:                            # main.py:88-103: a file that does not load gets its own kind of row
             # (sharded runs parse on the host and put only this rank's blocks on its GPU: api._solve_lp_sharded)
-            problem = mps_to_standard_form(path, device="cpu" if world > 1 else torch.device("cuda", torch.cuda.current_device()),
-                                           verbose=args.verbose, compat=not args.standard_mps, dtype=dtype)
+            reader = mps_to_ranged_form if args.ranged_rows else mps_to_standard_form
+            problem = reader(path, device="cpu" if world > 1 else torch.device("cuda", torch.cuda.current_device()),
+                             verbose=args.verbose, compat=not args.standard_mps, dtype=dtype)
+            q_upper = problem[6] if args.ranged_rows else None
+            problem = problem[:6]
         except Exception as e:
             print(f"Failed to load MPS file: {path}. Error: {e}")
             msg = str(e)
@@ -145,7 +151,7 @@ def main(argv=None) -> int:
                          adaptive_stepsize=args.adaptive_stepsize, adaptive_retry=args.adaptive_retry, max_kkt=args.max_kkt, time_limit=args.time_limit,
                          verbose=args.verbose, dtype=dtype, seed=args.seed, fishnet=args.fishnet, comm=comm,
                          infeasibility_detect=args.infeasibility_detect, precision="mixed" if args.dtype == "mixed" else None,
-                         direct_exchange=args.direct_exchange, report=args.solution_dir is not None, halpern=args.halpern)
+                         direct_exchange=args.direct_exchange, report=args.solution_dir is not None, halpern=args.halpern, q_upper=q_upper)
             print(f"Solver uses {r.time:.4f} seconds.\nStatus: {r.status}")
             if args.solution_dir is not None and rank == 0:
                 print(f"Solution saved to {write_solution(args.solution_dir, name, r)}")

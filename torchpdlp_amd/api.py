@@ -10,7 +10,7 @@ from typing import Optional, Union
 
 import torch
 
-from .mps import mps_to_standard_form
+from .mps import mps_to_ranged_form, mps_to_standard_form
 from .precondition import Scaling, equilibrate_matrix, ruiz_precondition, ruiz_precondition_batch
 from .solver import is_mixed, pdlp_algorithm, resolve_device
 from .sparse import CsrPair
@@ -68,7 +68,8 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
              seed: Optional[int] = None, compat: bool = True, x_init=None, y_init=None, trace=None,
              fishnet: bool = False, comm=None, infeasibility_detect: bool = False, infeas_tol: float = 1e-4,
              precision: Optional[str] = None, adaptive_retry: bool = False, direct_exchange: bool = False,
-             report: bool = True, pock_chambolle: bool = False, halpern: bool = False) -> LPResult:
+             report: bool = True, pock_chambolle: bool = False, halpern: bool = False, q_upper=None,
+             ranged_rows: bool = False) -> LPResult:
     """Solve ``min c'x, K[:m_ineq]x >= q[:m_ineq], K[m_ineq:]x = q[m_ineq:], l <= x <= u`` on the current HIP device.
 
     ``problem`` is an MPS path or ``(c, K, q, m_ineq, l, u)`` with ``K`` dense / COO / scipy-sparse / ``CsrPair``.
@@ -93,8 +94,26 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     (``pdlp_algorithm``).  Works with ``precondition``, ``pock_chambolle``, ``primal_weight_update``,
     ``x_init`` / ``y_init`` and ``fishnet``; ``ValueError`` with ``adaptive_stepsize``, ``adaptive_retry``, ``infeasibility_detect``,
     ``precision="mixed"`` and for sharded solves (``comm``).
+    ``q_upper`` (length m; not in the reference): two-sided rows, ``q_i <= (K x)_i <= q_upper_i`` on the inequality rows, each
+    entered ONCE instead of as two ``>=`` rows.  ``+inf`` is an ordinary row, ``q_upper_i == q_i`` behaves as
+    an equality row; on the equality rows the entry must be ``+inf`` or ``q_i`` and is ignored.  In the report ``y_i > 0`` says the
+    lower side of a two-sided row is active, ``y_i < 0`` the upper side.  ``ranged_rows=True`` (MPS paths): the ``RANGES`` rows of
+    the file are read that way (``mps_to_ranged_form``) instead of being split.  Both work with ``precondition``,
+    ``pock_chambolle``, ``primal_weight_update``, ``adaptive_stepsize``, ``halpern``, ``x_init`` / ``y_init`` and ``report`` in
+    float32 and float64; ``ValueError`` (before any device work) for a malformed ``q_upper`` and together with
+    ``precision="mixed"``, ``comm``, ``infeasibility_detect``, ``fishnet`` and ``adaptive_retry``.
     """
     _check_pock_chambolle(pock_chambolle, precondition)
+    from_file = isinstance(problem, (str, os.PathLike))
+    if ranged_rows and (not from_file or q_upper is not None):
+        raise ValueError("ranged_rows=True reads the RANGES rows of an MPS path; arrays carry q_upper themselves")
+    if q_upper is not None or ranged_rows:
+        from .ranged import REFUSED, check_row_upper
+        if (is_mixed(precision) or comm not in (None, False) or infeasibility_detect or fishnet or adaptive_retry
+                or direct_exchange):
+            raise ValueError(REFUSED)
+        if q_upper is not None:
+            check_row_upper(problem[2], q_upper, problem[3])
     if halpern and (adaptive_stepsize or adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False)
                     or direct_exchange):
         from .solver import HALPERN_REFUSED
@@ -117,10 +136,16 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
                                  "vectors): solve on one GPU, or with precondition alone")
             return _solve_lp_sharded(problem, cm, device, run, dtype=dtype, verbose=verbose, seed=seed, compat=compat, x_init=x_init,
                                      y_init=y_init, precision=precision, direct_exchange=direct_exchange, report=report)
-    c, K, q, m_ineq, l, u = load_problem(problem, device, dtype, verbose, compat)
+    if ranged_rows:
+        c, K, q, m_ineq, l, u, q_upper = mps_to_ranged_form(os.fspath(problem), device=device, verbose=verbose, compat=compat, dtype=dtype)
+    else:
+        c, K, q, m_ineq, l, u = load_problem(problem, device, dtype, verbose, compat)
     time_used, data_precond = 0.0, None
-    Ks, cs, qs, ls, us = K, c, q, l, u
-    if precondition:                                                    # main.py:106-110
+    Ks, cs, qs, ls, us, qus = K, c, q, l, u, q_upper
+    if precondition and q_upper is not None:
+        Ks, cs, qs, ls, us, qus, data_precond, time_used = ruiz_precondition(c, K, q, l, u, device=device, pock_chambolle=pock_chambolle,
+                                                                             q_upper=q_upper)
+    elif precondition:                                                  # main.py:106-110
         Ks, cs, qs, ls, us, data_precond, time_used = ruiz_precondition(c, K, q, l, u, device=device, pock_chambolle=pock_chambolle)
     if fishnet:                                                         # main.py:114-125 (k=32 points rounds, 2^5 points)
         from .spectral_casting import spectral_cast
@@ -131,7 +156,7 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     rep = {} if report else None
     x, obj, k, n, j, status, total = pdlp_algorithm(
         Ks, m_ineq, cs, qs, ls, us, device, verbose=verbose, data_precond=data_precond, time_used=time_used, x_init=x_init,
-        y_init=y_init, seed=seed, comm=comm, precision=precision, report=rep, **run)
+        y_init=y_init, seed=seed, comm=comm, precision=precision, report=rep, **({} if qus is None else dict(q_upper=qus)), **run)
     if precondition:        # the reference returns the scaled iterate (quirk Q4); solve_lp un-scales: x = D_col x_s (pdhg.py:161)
         x = Scaling(*data_precond[:2]).unscale_x(x)
     return LPResult(x, obj, k, n, j, status, total, **report_fields(rep))

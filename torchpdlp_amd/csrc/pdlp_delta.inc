@@ -143,7 +143,7 @@ extern "C" {
 int pdlp_set_delta(pdlp_handle h, int on)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (on && !h->mixed) return PDLP_ERR_STATE;           // float32 matrix values under float64 vectors only
+    if (on && (!h->mixed || h->q_upper)) return PDLP_ERR_STATE;           // float32 matrix values under float64 vectors only, one-sided rows
     if ((on != 0) == h->delta) return PDLP_OK;
     drop_graphs(h);
     h->graph_ok = false;

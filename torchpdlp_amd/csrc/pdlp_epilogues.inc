@@ -37,6 +37,17 @@ template <typename T> struct StoreEpi {
     __device__ void operator()(int i, T s, const Pre&, double* a) const { (*this)(i, s, a); }
 };
 
+// Two-sided rows (pdlp_set_row_upper): q_i <= (K x)_i <= q_upper_i on the inequality rows.  RANGED = true adds ONE operand to the
+// constraint-side functors -- q_upper[i], loaded in pre() beside q[i] -- and the upper side's arithmetic; RANGED = false (the default)
+// has neither the pointer in the kernel arguments nor the value in the operand set (the tiled kernel sizes its epilogue groups by
+// sizeof(Pre)), so those instantiations are what they were before two-sided rows existed.
+template <typename T, bool RANGED> struct RowUpper { const T* p = nullptr; };
+template <typename T> struct RowUpper<T, false> {};
+// y' of an inequality row from a = y + sigma (q - k) and b = y + sigma (q_upper - k): a above zero (the lower side pushes), b below
+// zero (the upper side pushes), else 0.  Every operation is monotone, so a <= b after rounding too and at most one side is active.
+// Written from a < 0 so that with q_upper = +inf (b = +inf) the value is the one-sided `a < 0 ? 0 : a` bit for bit (a = -0 included).
+template <typename T> __device__ __forceinline__ T ranged_dual(T a, T b) { return a < (T)0 ? (b < (T)0 ? b : (T)0) : a; }
+
 // primal half-step over this rank's rows of K' (= its variables).  kty = (K'y)_j.
 // step.py:25-30 (fixed) / :74-82 (adaptive); running sum pdhg.py:107.
 template <typename T, bool ADAPT, bool PEER = false> struct PrimalEpi {
@@ -83,7 +94,9 @@ template <typename T, bool ADAPT, bool PEER = false> struct PrimalEpi {
 
 // dual half-step over this rank's rows of K (= its constraints).  kxbar = (K xbar)_i.
 // step.py:33-38 / :85-96; running sum pdhg.py:108.
-template <typename T, bool ADAPT, bool PEER = false> struct DualEpi {
+template <typename T, bool RANGED> struct DualPre { T yo, qi, sum, kxo, kxs; };
+template <typename T> struct DualPre<T, true> { T yo, qi, sum, kxo, kxs, qu; };
+template <typename T, bool ADAPT, bool PEER = false, bool RANGED = false> struct DualEpi {
     static constexpr int NA = ADAPT ? 2 : 0;
     const T* y_old; T* y_new; const T* q; T* y_sum; T* kx; const double* sc; int ineq_end;
     // kx: K x of the current iterate, carried along (K x+ = K x + (K xbar - K x)/(1 + theta)); kx_sum (or null): running sum of
@@ -91,20 +104,29 @@ template <typename T, bool ADAPT, bool PEER = false> struct DualEpi {
     T* kx_sum = nullptr;
     T sigma = 0, w = 0, inv1pt = 0;
     PeerOut<T, PEER> peer{};               // the other ranks' copy of the y buffer being written, at this rank's block
+    [[no_unique_address]] RowUpper<T, RANGED> upper{};      // q_upper of this rank's rows
     __device__ void load()
     {
         sigma = (T)sc[S_SIGMA];
         w = ADAPT ? (T)sc[S_WPEND] : (T)sc[S_ETA];
         inv1pt = (T)sc[S_INV1PT];
     }
-    struct Pre { T yo, qi, sum, kxo, kxs; };
-    __device__ Pre pre(int i) const { return Pre{y_old[i], q[i], y_sum[i], kx[i], kx_sum ? kx_sum[i] : (T)0}; }
+    typedef DualPre<T, RANGED> Pre;
+    __device__ Pre pre(int i) const
+    {
+        if constexpr (RANGED) return Pre{y_old[i], q[i], y_sum[i], kx[i], kx_sum ? kx_sum[i] : (T)0, upper.p[i]};
+        else return Pre{y_old[i], q[i], y_sum[i], kx[i], kx_sum ? kx_sum[i] : (T)0};
+    }
     __device__ void operator()(int i, T kxbar, double* acc) const { (*this)(i, kxbar, pre(i), acc); }
     __device__ void operator()(int i, T kxbar, const Pre& p, double* acc) const
     {
         const T yo = p.yo;
         T v = yo + sigma * (p.qi - kxbar);
-        if (i < ineq_end && v < (T)0) v = (T)0;
+        if constexpr (RANGED) {
+            if (i < ineq_end) v = ranged_dual(v, yo + sigma * (p.qu - kxbar));
+        } else {
+            if (i < ineq_end && v < (T)0) v = (T)0;
+        }
         y_new[i] = v;
         peer(i, v);
         // K dx = (K xbar - K x) / (1 + theta) because xbar = x + (1 + theta) dx; kx caches K x
@@ -155,20 +177,31 @@ template <typename T> struct HalpernPrimalEpi {
 };
 
 // Reflected Halpern iteration, dual half over the rows of K: y' as DualEpi forms it; y+ = a (2y' - y) + b y_last.
-template <typename T> struct HalpernDualEpi {
+template <typename T, bool RANGED> struct HalpernDualPre { T yo, yl, qi; };
+template <typename T> struct HalpernDualPre<T, true> { T yo, yl, qi, qu; };
+template <typename T, bool RANGED = false> struct HalpernDualEpi {
     static constexpr int NA = 0;
     const T* y_old; T* y_new; T* y_cand; const T* y_last; const T* q; const double* sc; int ineq_end;
     T a, b;
     T sigma = 0;
+    [[no_unique_address]] RowUpper<T, RANGED> upper{};
     __device__ void load() { sigma = (T)sc[S_SIGMA]; }
-    struct Pre { T yo, yl, qi; };
-    __device__ Pre pre(int i) const { return Pre{y_old[i], y_last[i], q[i]}; }
+    typedef HalpernDualPre<T, RANGED> Pre;
+    __device__ Pre pre(int i) const
+    {
+        if constexpr (RANGED) return Pre{y_old[i], y_last[i], q[i], upper.p[i]};
+        else return Pre{y_old[i], y_last[i], q[i]};
+    }
     __device__ void operator()(int i, T kxbar, double* acc) const { (*this)(i, kxbar, pre(i), acc); }
     __device__ void operator()(int i, T kxbar, const Pre& p, double*) const
     {
         const T yo = p.yo;
         T v = yo + sigma * (p.qi - kxbar);
-        if (i < ineq_end && v < (T)0) v = (T)0;
+        if constexpr (RANGED) {
+            if (i < ineq_end) v = ranged_dual(v, yo + sigma * (p.qu - kxbar));
+        } else {
+            if (i < ineq_end && v < (T)0) v = (T)0;
+        }
         y_cand[i] = v;
         y_new[i] = a * ((T)2 * v - yo) + b * p.yl;
     }
@@ -207,25 +240,49 @@ template <typename T, bool UNSCALE> struct KktDualEpi {
 };
 
 // KKT, primal side (helpers.py:77,87-91).  Optionally keeps K x for the adaptive step's cache.
-template <typename T, bool UNSCALE> struct KktPrimalEpi {
+// Two-sided rows (RANGED): the upper violation max(k - q_upper, 0) joins the lower one min(k - q, 0) in acc[0] (0 for +inf), and the
+// dual objective takes q_upper_i y_i where y_i < 0 on a row with a finite q_upper (the upper side is the active one).
+template <typename T, bool RANGED> struct KktPrimalPre { T qi, yi, d; };
+template <typename T> struct KktPrimalPre<T, true> { T qi, yi, d, qu; };
+// the two sums of a constraint row from r = k - q and ru = k - q_upper (RANGED), after UNSCALE has divided them
+template <typename T, bool RANGED>
+__device__ __forceinline__ void row_sums(int i, int ineq_end, T r, T ru, T qi, T qu, T yi, double* acc)
+{
+    if (i < ineq_end && r > (T)0) r = (T)0;
+    acc[0] += (double)r * (double)r;
+    if constexpr (RANGED) {
+        if (i < ineq_end) {
+            ru = ru > (T)0 ? ru : (T)0;
+            acc[0] += (double)ru * (double)ru;
+            if (yi < (T)0 && !isinf(qu)) qi = qu;
+        }
+    }
+    acc[1] += (double)qi * (double)yi;
+}
+template <typename T, bool UNSCALE, bool RANGED = false> struct KktPrimalEpi {
     static constexpr int NA = 2;
     const T* y; const T* q; const T* drow; T* kx_out; int ineq_end;
+    [[no_unique_address]] RowUpper<T, RANGED> upper{};
     __device__ void load() {}
-    struct Pre { T qi, yi, d; };
-    __device__ Pre pre(int i) const { return Pre{q[i], y[i], UNSCALE ? drow[i] : (T)1}; }
+    typedef KktPrimalPre<T, RANGED> Pre;
+    __device__ Pre pre(int i) const
+    {
+        if constexpr (RANGED) return Pre{q[i], y[i], UNSCALE ? drow[i] : (T)1, upper.p[i]};
+        else return Pre{q[i], y[i], UNSCALE ? drow[i] : (T)1};
+    }
     __device__ void operator()(int i, T kx, double* acc) const { (*this)(i, kx, pre(i), acc); }
     __device__ void operator()(int i, T kx, const Pre& p, double* acc) const
     {
         if (kx_out) kx_out[i] = kx;
-        T qi = p.qi, yi = p.yi;
+        T qi = p.qi, yi = p.yi, qu = (T)0, ru = (T)0;
         T r = kx - qi;
+        if constexpr (RANGED) { qu = p.qu; ru = kx - qu; }
         if (UNSCALE) {            // K_u (D_col x) = (K_s x)/D_row, q_u = q_s/D_row, y_u = D_row y
             const T d = p.d;
             r = r / d; qi = qi / d; yi = yi * d;
+            if constexpr (RANGED) { ru = ru / d; qu = qu / d; }
         }
-        if (i < ineq_end && r > (T)0) r = (T)0;
-        acc[0] += (double)r * (double)r;
-        acc[1] += (double)qi * (double)yi;
+        row_sums<T, RANGED>(i, ineq_end, r, ru, qi, qu, yi, acc);
     }
 };
 
@@ -267,25 +324,32 @@ template <typename T, bool UNSCALE> struct ReportDualEpi {
 
 // Solution report, constraint side: the same after K x stored into `buf`.  The sums of KktPrimalEpi (helpers.py:77,87-91); buf[i]
 // keeps the row activity (K x)_i -- UNSCALE: act_u = (K_s x_s) / D_row.
-template <typename T, bool UNSCALE> struct ReportPrimalEpi {
+template <typename T, bool RANGED> struct ReportPrimalPre { T kx, qi, yi, d; };
+template <typename T> struct ReportPrimalPre<T, true> { T kx, qi, yi, d, qu; };
+template <typename T, bool UNSCALE, bool RANGED = false> struct ReportPrimalEpi {
     static constexpr int NA = 2;
     T* buf; const T* y; const T* q; const T* drow; int ineq_end;
+    [[no_unique_address]] RowUpper<T, RANGED> upper{};
     __device__ void load() {}
-    struct Pre { T kx, qi, yi, d; };
-    __device__ Pre pre(int i) const { return Pre{buf[i], q[i], y[i], UNSCALE ? drow[i] : (T)1}; }
+    typedef ReportPrimalPre<T, RANGED> Pre;
+    __device__ Pre pre(int i) const
+    {
+        if constexpr (RANGED) return Pre{buf[i], q[i], y[i], UNSCALE ? drow[i] : (T)1, upper.p[i]};
+        else return Pre{buf[i], q[i], y[i], UNSCALE ? drow[i] : (T)1};
+    }
     __device__ void operator()(int i, T, double* acc) const { (*this)(i, (T)0, pre(i), acc); }
     __device__ void operator()(int i, T, const Pre& p, double* acc) const
     {
-        T qi = p.qi, yi = p.yi;
+        T qi = p.qi, yi = p.yi, qu = (T)0, ru = (T)0;
         T r = p.kx - qi;
+        if constexpr (RANGED) { qu = p.qu; ru = p.kx - qu; }
         if (UNSCALE) {
             const T d = p.d;
             r = r / d; qi = qi / d; yi = yi * d;
             buf[i] = p.kx / d;
+            if constexpr (RANGED) { ru = ru / d; qu = qu / d; }
         }
-        if (i < ineq_end && r > (T)0) r = (T)0;
-        acc[0] += (double)r * (double)r;
-        acc[1] += (double)qi * (double)yi;
+        row_sums<T, RANGED>(i, ineq_end, r, ru, qi, qu, yi, acc);
     }
 };
 

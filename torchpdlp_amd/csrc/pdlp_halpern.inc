@@ -17,9 +17,16 @@ template <typename T> int halpern_iterate_t(pdlp_handle h, int iters)
         HalpernPrimalEpi<T> ep{xloc<T>(h, cur), xloc<T>(h, nxt), (T*)h->xbar + h->p.col0, xloc<T>(h, cand), (const T*)h->x_last,
                                (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, h->sc, a, b};
         if ((rc = launch_csr<T>(h, true, h->yb[cur], ep, h->partA)) != PDLP_OK) return rc;
-        HalpernDualEpi<T> ed{yloc<T>(h, cur), yloc<T>(h, nxt), yloc<T>(h, cand), (const T*)h->y_last, (const T*)h->p.q, h->sc,
-                             h->ineq_end, a, b};
-        if ((rc = launch_csr<T>(h, false, h->xbar, ed, h->partB)) != PDLP_OK) return rc;
+        if (h->q_upper) {          // two-sided rows (pdlp_set_row_upper)
+            HalpernDualEpi<T, true> ed{yloc<T>(h, cur), yloc<T>(h, nxt), yloc<T>(h, cand), (const T*)h->y_last, (const T*)h->p.q, h->sc,
+                                       h->ineq_end, a, b};
+            ed.upper.p = (const T*)h->q_upper;
+            if ((rc = launch_mat<T, T>(h, false, h->xbar, ed, h->partB)) != PDLP_OK) return rc;
+        } else {
+            HalpernDualEpi<T> ed{yloc<T>(h, cur), yloc<T>(h, nxt), yloc<T>(h, cand), (const T*)h->y_last, (const T*)h->p.q, h->sc,
+                                 h->ineq_end, a, b};
+            if ((rc = launch_csr<T>(h, false, h->xbar, ed, h->partB)) != PDLP_OK) return rc;
+        }
         h->ix_cur = nxt;           // the freshly written z becomes current; the old z's buffers are the next iteration's target
         h->ix_prev = cur;
         ++h->since_reset;

@@ -338,6 +338,20 @@ int pdlp_set_iterate(pdlp_handle h, const void* x_local, const void* y_local)
     return PDLP_OK;
 }
 
+int pdlp_set_row_upper(pdlp_handle h, const void* q_upper_local)
+{
+    if (!h) return PDLP_ERR_INVALID;
+    // forms without two-sided rows: mixed precision / delta mode, a shard of a problem, an exchange of any kind
+    if (q_upper_local && (h->mixed || h->delta || h->nl != h->p.n || h->ml != h->p.m || h->comm || h->peer.on)) return PDLP_ERR_STATE;
+    if (h->sK.pending || h->sKT.pending) return PDLP_ERR_STATE;       // not in the middle of a split product
+    drop_graphs(h);               // captured launches hold the functors without (or with the old) q_upper
+    h->q_upper = q_upper_local;
+    // what a KKT pass left behind belongs to the other set of rows: the candidates' products and the kept K'y
+    h->cand_valid[0] = h->cand_valid[1] = false;
+    h->kty_cur = -1; h->cur_kx_cached = false;
+    return PDLP_OK;
+}
+
 int pdlp_get_iterate(pdlp_handle h, int which, void* x_local, void* y_local)
 {
     if (!h) return PDLP_ERR_INVALID;
@@ -624,12 +638,14 @@ int pdlp_infeas_reset(pdlp_handle h)
 int pdlp_infeas_begin(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
+    if (h->q_upper) return PDLP_ERR_STATE;       // (the detector's tests know one-sided rows only)
     return DISPATCH(h, infeas_begin_t, h);
 }
 
 int pdlp_infeas_local(pdlp_handle h, double tol)
 {
     if (!h) return PDLP_ERR_INVALID;
+    if (h->q_upper) return PDLP_ERR_STATE;
     return DISPATCH(h, infeas_local_t, h, tol);
 }
 
@@ -646,21 +662,21 @@ int pdlp_infeas_finish(pdlp_handle h, double tol, int32_t* status, double diag[8
 int pdlp_mv_steps(pdlp_handle h, int nvp, int steps, double eta, double omega, double theta, void* X, void* Y, void* work)
 {
     if (!h || !X || !Y || !work || steps < 0 || (nvp != 8 && nvp != 16 && nvp != 32)) return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed) return PDLP_ERR_STATE;
+    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper) return PDLP_ERR_STATE;   // (q_upper: one-sided rows only)
     return DISPATCH(h, mv_steps_t, h, nvp, steps, eta, omega, theta, X, Y, work);
 }
 
 int pdlp_mv_gap(pdlp_handle h, int nvp, const void* X, const void* Y, void* work, double* gaps)
 {
     if (!h || !X || !Y || !work || !gaps || (nvp != 8 && nvp != 16 && nvp != 32)) return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed) return PDLP_ERR_STATE;
+    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper) return PDLP_ERR_STATE;   // (q_upper: one-sided rows only)
     return DISPATCH(h, mv_gap_t, h, nvp, X, Y, work, gaps);
 }
 
 int pdlp_mv_product(pdlp_handle h, int nvp, const void* X, void* Y)
 {
     if (!h || !X || !Y || (nvp != 8 && nvp != 16 && nvp != 32)) return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed) return PDLP_ERR_STATE;
+    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper) return PDLP_ERR_STATE;   // (q_upper: one-sided rows only)
     return DISPATCH(h, mv_product_t, h, nvp, X, Y);
 }
 

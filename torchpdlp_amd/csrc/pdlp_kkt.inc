@@ -6,7 +6,21 @@
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-template <typename T, bool UNSCALE> int kkt_local_u(pdlp_handle h, int which)
+// the constraint side's functors of a KKT pass / a report, with q_upper when the handle has two-sided rows (RANGED), and their
+// product with K: a handle with two-sided rows is never in mixed precision, so its matrix has the working type
+template <typename T, bool UNSCALE, bool RANGED> KktPrimalEpi<T, UNSCALE, RANGED> kkt_primal_epi(pdlp_handle h, int ix, const T* drow, T* kx_out)
+{
+    KktPrimalEpi<T, UNSCALE, RANGED> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, kx_out, h->ineq_end};
+    if constexpr (RANGED) ep.upper.p = (const T*)h->q_upper;
+    return ep;
+}
+template <typename T, bool RANGED, class Epi> int launch_rows(pdlp_handle h, const void* vin, Epi e, double* partials)
+{
+    if constexpr (RANGED) return launch_mat<T, T>(h, false, vin, e, partials);
+    else return launch_csr<T>(h, false, vin, e, partials);
+}
+
+template <typename T, bool UNSCALE, bool RANGED = false> int kkt_local_u(pdlp_handle h, int which)
 {
     const int ix = iterate_index(h, which);
     const T* dcol = UNSCALE ? (const T*)h->p.d_col : nullptr;
@@ -16,7 +30,7 @@ template <typename T, bool UNSCALE> int kkt_local_u(pdlp_handle h, int which)
         // K'y_avg (ktyb[1]) and K x_avg (kxb[2]) were formed from the running sums by pdlp_compute_average: two vector passes
         KktDualEpi<T, UNSCALE> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, nullptr};
         if ((rc = epilogue_pass<T>(h, h->nl, h->ktyb[1], ed, h->partA)) != PDLP_OK) return rc;
-        KktPrimalEpi<T, UNSCALE> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, nullptr, h->ineq_end};
+        const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, nullptr);
         if ((rc = epilogue_pass<T>(h, h->ml, h->kxb[2], ep, h->partB)) != PDLP_OK) return rc;
         gridA = rows_grid(h->nl);
         gridB = rows_grid(h->ml);
@@ -30,13 +44,13 @@ template <typename T, bool UNSCALE> int kkt_local_u(pdlp_handle h, int which)
         if ((rc = launch_csr<T>(h, true, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
         if (which == PDLP_CUR && h->kx_valid && !h->no_running) {
             // K x of the current iterate is carried along by the dual half-steps (kxb[0]): no product
-            KktPrimalEpi<T, UNSCALE> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, nullptr, h->ineq_end};
+            const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, nullptr);
             if ((rc = epilogue_pass<T>(h, h->ml, h->kxb[0], ep, h->partB)) != PDLP_OK) return rc;
             gridB = rows_grid(h->ml);
             h->cur_kx_cached = true;
         } else {
-            KktPrimalEpi<T, UNSCALE> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, kx_out, h->ineq_end};
-            if ((rc = launch_csr<T>(h, false, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
+            const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, kx_out);
+            if ((rc = launch_rows<T, RANGED>(h, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
             if (which == PDLP_CUR) h->cur_kx_cached = false;
         }
     }
@@ -47,6 +61,7 @@ template <typename T, bool UNSCALE> int kkt_local_u(pdlp_handle h, int which)
 
 template <typename T> int kkt_local_t(pdlp_handle h, int which, int unscaled)
 {
+    if (h->q_upper) return unscaled ? kkt_local_u<T, true, true>(h, which) : kkt_local_u<T, false, true>(h, which);
     return unscaled ? kkt_local_u<T, true>(h, which) : kkt_local_u<T, false>(h, which);
 }
 
@@ -56,7 +71,7 @@ template <typename T> int kkt_local_t(pdlp_handle h, int which, int unscaled)
 // then forms the sums and turns K'y into lam in place.  A vector the caller does not want (null) costs nothing extra: that side
 // runs the KKT pass's own fused epilogue without its stores.  Nothing of the solver's state is read except the iterate and
 // nothing is written except scratch (partial sums, row sums, PDLP_BUF_RED).
-template <typename T, bool UNSCALE> int report_local_u(pdlp_handle h, int which, void* rc_local, void* act_local)
+template <typename T, bool UNSCALE, bool RANGED = false> int report_local_u(pdlp_handle h, int which, void* rc_local, void* act_local)
 {
     const int ix = iterate_index(h, which);
     const T* dcol = UNSCALE ? (const T*)h->p.d_col : nullptr;
@@ -75,18 +90,21 @@ template <typename T, bool UNSCALE> int report_local_u(pdlp_handle h, int which,
     if (act_local) {
         StoreEpi<T> st{(T*)act_local};
         if ((rc = launch_csr<T>(h, false, h->xb[ix], st, h->partB)) != PDLP_OK) return rc;
-        ReportPrimalEpi<T, UNSCALE> ep{(T*)act_local, yloc<T>(h, ix), (const T*)h->p.q, drow, h->ineq_end};
+        ReportPrimalEpi<T, UNSCALE, RANGED> ep{(T*)act_local, yloc<T>(h, ix), (const T*)h->p.q, drow, h->ineq_end};
+        if constexpr (RANGED) ep.upper.p = (const T*)h->q_upper;
         if ((rc = epilogue_pass<T>(h, h->ml, nullptr, ep, h->partB)) != PDLP_OK) return rc;
         gridB = rows_grid(h->ml);
     } else {
-        KktPrimalEpi<T, UNSCALE> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, nullptr, h->ineq_end};
-        if ((rc = launch_csr<T>(h, false, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
+        const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, nullptr);
+        if ((rc = launch_rows<T, RANGED>(h, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
     }
     return finalize_kkt(h, gridA, gridB);
 }
 
 template <typename T> int report_local_t(pdlp_handle h, int which, int unscaled, void* rc_local, void* act_local)
 {
+    if (h->q_upper)
+        return unscaled ? report_local_u<T, true, true>(h, which, rc_local, act_local) : report_local_u<T, false, true>(h, which, rc_local, act_local);
     return unscaled ? report_local_u<T, true>(h, which, rc_local, act_local) : report_local_u<T, false>(h, which, rc_local, act_local);
 }
 

@@ -237,14 +237,22 @@ template <typename T> int refresh_kx_t(pdlp_handle h)
     return rc;
 }
 
-template <typename T, bool ADAPT, bool PEER> int dual_half_e(pdlp_handle h, T* ksum)
+// RANGED: the handle has two-sided rows (pdlp_set_row_upper: float32 / float64, one GPU, no exchange -- so never PEER, and the
+// matrix has the working type)
+template <typename T, bool ADAPT, bool PEER, bool RANGED = false> int dual_half_e(pdlp_handle h, T* ksum)
 {
-    DualEpi<T, ADAPT, PEER> e{yloc<T>(h, h->ix_cur), yloc<T>(h, h->ix_prev), (const T*)h->p.q, (T*)h->y_sum, (T*)h->kxb[0],
-                              h->sc, h->ineq_end, ksum};
+    DualEpi<T, ADAPT, PEER, RANGED> e{yloc<T>(h, h->ix_cur), yloc<T>(h, h->ix_prev), (const T*)h->p.q, (T*)h->y_sum, (T*)h->kxb[0],
+                                      h->sc, h->ineq_end, ksum};
     peer_targets(h, e.peer, 1 + h->ix_prev);
     if (ADAPT) h->last_gridB = grid_of(h->sK, h->ml);
     h->use_split = true;
-    const int rc = launch_csr<T>(h, false, h->xbar, e, h->partB);
+    int rc;
+    if constexpr (RANGED) {
+        e.upper.p = (const T*)h->q_upper;
+        rc = launch_mat<T, T>(h, false, h->xbar, e, h->partB);
+    } else {
+        rc = launch_csr<T>(h, false, h->xbar, e, h->partB);
+    }
     h->use_split = false;
     return rc;
 }
@@ -256,7 +264,9 @@ template <typename T> int dual_half_t(pdlp_handle h, int adaptive)
     T* ksum = (h->sums_broken || h->no_running || h->graph_ok) ? nullptr : (T*)h->kx_sum;
     const PieceCtl pc = piece_ctl(h, h->sK);
     rc = PDLP_OK;
-    if (!pc.skip)            // (else: all of this half-step went out with piece 0)
+    if (!pc.skip && h->q_upper)
+        rc = adaptive ? dual_half_e<T, true, false, true>(h, ksum) : dual_half_e<T, false, false, true>(h, ksum);
+    else if (!pc.skip)       // (else: all of this half-step went out with piece 0)
         rc = with_adapt_peer(h, adaptive, [&](auto A, auto P) { return dual_half_e<T, decltype(A)::value, decltype(P)::value>(h, ksum); });
     if (rc != PDLP_OK) { h->sK.pending = false; return rc; }
     if (!pc.finish) return PDLP_OK;                          // (more pieces of this half-step to come)

@@ -84,8 +84,9 @@ class PdlpEngine(KernelChoice, Exchange):
 
     def __init__(self, m: int, n: int, m_ineq: int, K_rows, KT_rows, c, q, l, u, rows: Tuple[int, int] = None,
                  cols: Tuple[int, int] = None, d_col=None, d_row=None, comm: Optional[Comm] = None, vec_dtype=None,
-                 delta: Optional[bool] = None, exact=None, tiles: bool = True):
-        """``vec_dtype=torch.float64`` over float32 matrix values selects the mixed precision (``PDLP_MIXED``): float64 vectors,
+                 delta: Optional[bool] = None, exact=None, tiles: bool = True, q_upper=None):
+        """``q_upper`` (length row1-row0, or None): two-sided rows ``q <= K x <= q_upper`` on the inequality rows (``set_row_upper``).
+        ``vec_dtype=torch.float64`` over float32 matrix values selects the mixed precision (``PDLP_MIXED``): float64 vectors,
         products and sums on a float32 matrix (12 -> 8 bytes per non-zero); ``delta`` (default: ``PDLP_DELTA`` in the environment,
         else on) then runs the iterations on the float32 kernels over float32 difference vectors added to float64 anchor
         products (``pdlp_set_delta`` in include/pdlp_hip.h).  ``exact`` = ``(K_rows, KT_rows)`` in float64: the TRUE matrix when the
@@ -140,6 +141,9 @@ class PdlpEngine(KernelChoice, Exchange):
                                      nbytes.value), "pdlp_create")
         self._views = {}
         self._want_tiles = bool(tiles)
+        self.q_upper = None
+        if q_upper is not None:
+            self.set_row_upper(q_upper)
         # test / tool knobs of the handle (knobs_from_env)
         kn = self.knobs = knobs_from_env()
         if not kn.running_kkt:
@@ -182,6 +186,22 @@ class PdlpEngine(KernelChoice, Exchange):
         """``pdlp_set_option``: the handle's test / tool switches (``N.OPT_*``)"""
         N.check(self.lib.pdlp_set_option(self.h, int(option), int(value)), "pdlp_set_option")
 
+    def set_row_upper(self, q_upper):
+        """Two-sided rows (``pdlp_set_row_upper``, include/pdlp_hip.h): ``q_i <= (K x)_i <= q_upper_i`` on the inequality rows, ``+inf``
+        = a one-sided row; ``y_i > 0``: the lower side is active, ``y_i < 0``: the upper side.  ``None`` switches them off.  Validated
+        here (``ranged.check_row_upper``: ``ValueError``); float32 / float64 engines on one GPU (``ValueError`` otherwise).  While set,
+        ``detect_infeasibility`` and the population calls raise ``PdlpError``."""
+        from .ranged import REFUSED, check_row_upper
+        if q_upper is None:
+            N.check(self.lib.pdlp_set_row_upper(self.h, None), "pdlp_set_row_upper")
+            self.q_upper = None
+            return
+        if self.mixed or self.comm is not None:
+            raise ValueError(REFUSED)
+        qu = check_row_upper(self.q, as_vec(q_upper, self.ml, self.device, self.dtype), self.m_ineq)
+        N.check(self.lib.pdlp_set_row_upper(self.h, qu.data_ptr()), "pdlp_set_row_upper")
+        self.q_upper = qu                      # (kept alive: the library points into it)
+
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
         th = getattr(self, "_comm_init_thread", None)
@@ -199,11 +219,11 @@ class PdlpEngine(KernelChoice, Exchange):
 
     @classmethod
     def from_full(cls, K: CsrPair, c, q, l, u, m_ineq: int, d_col=None, d_row=None, vec_dtype=None, delta=None,
-                  exact: Optional[CsrPair] = None) -> "PdlpEngine":
+                  exact: Optional[CsrPair] = None, q_upper=None) -> "PdlpEngine":
         """single-GPU engine over a whole problem (``exact``: the float64 matrix of which ``K`` is the float32 rounding)"""
         ex = None if exact is None else ((exact.rowptr, exact.colidx, exact.val), (exact.t_rowptr, exact.t_colidx, exact.t_val))
         return cls(K.m, K.n, m_ineq, (K.rowptr, K.colidx, K.val), (K.t_rowptr, K.t_colidx, K.t_val), c, q, l, u,
-                   d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, delta=delta, exact=ex)
+                   d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, delta=delta, exact=ex, q_upper=q_upper)
 
     # ---- buffers ------------------------------------------------------------------------------------
     def buffer(self, which: int) -> torch.Tensor:

@@ -31,8 +31,10 @@ from .sparse import CsrPair
 _SECTIONS = ("ROWS", "COLUMNS", "RHS", "RANGES", "BOUNDS")
 
 
-def parse_mps(mps_file: str, compat: bool = True):
-    """Parse into numpy pieces: (c, (rowptr, colidx, val, m, n), q, m_ineq, l, u), all float64 / int64."""
+def parse_mps(mps_file: str, compat: bool = True, ranged: bool = False):
+    """Parse into numpy pieces: (c, (rowptr, colidx, val, m, n), q, m_ineq, l, u), all float64 / int64.  ``ranged``: a RANGES row
+    stays ONE row ``lb <= a'x <= ub`` -- the first of the two it is split into otherwise, the second is left out -- and a seventh
+    piece ``q_upper`` holds ``ub`` on those rows and ``+inf`` on every other."""
     with open(mps_file, "r") as f:       # util.py:93-94: blank lines and lines starting with '*' are dropped
         lines = [ln.strip() for ln in f if ln.strip() and not ln.startswith("*")]
     section = None
@@ -121,7 +123,7 @@ def parse_mps(mps_file: str, compat: bool = True):
     starts = np.zeros(len(row_order) + 1, np.int64)
     starts[1:] = np.cumsum(np.bincount(R, minlength=len(row_order)))
     # constraint rows in ROWS order: inequality block then equality block (util.py:190-231,250-261)
-    g_src, g_sign, g_rhs, a_src, a_rhs = [], [], [], [], []
+    g_src, g_sign, g_rhs, a_src, a_rhs, g_up = [], [], [], [], [], []
     for name in row_order:
         if name == obj_row:
             continue
@@ -138,6 +140,12 @@ def parse_mps(mps_file: str, compat: bool = True):
                 lb, ub = (b, b + rng) if rng > 0 else (b + rng, b)
             else:
                 raise ValueError(f"Unsupported ranged sense: {sense}")
+            if ranged:
+                g_src.append(src)
+                g_sign.append(1.0)
+                g_rhs.append(lb)
+                g_up.append(ub)
+                continue
             g_src += [src, src]
             g_sign += [1.0, -1.0]
             g_rhs += [lb, -ub]
@@ -148,10 +156,12 @@ def parse_mps(mps_file: str, compat: bool = True):
             g_src.append(src)
             g_sign.append(1.0)
             g_rhs.append(b)
+            g_up.append(np.inf)
         elif sense == "L":                            # util.py:226-228
             g_src.append(src)
             g_sign.append(-1.0)
             g_rhs.append(-b)
+            g_up.append(np.inf)
     m_ineq, m = len(g_src), len(g_src) + len(a_src)
     if m == 0:
         raise RuntimeError("the model has no constraint rows (the reference fails in torch.vstack, util.py:260)")
@@ -166,6 +176,9 @@ def parse_mps(mps_file: str, compat: bool = True):
     q = np.array(g_rhs + a_rhs, dtype=np.float64)
     l = np.array([lo.get(v, 0.0) if lo.get(v, 0.0) is not None else 0.0 for v in var_names], dtype=np.float64)   # util.py:234-239
     u = np.array([up.get(v, np.inf) if up.get(v, np.inf) is not None else np.inf for v in var_names], dtype=np.float64)
+    if ranged:
+        q_upper = np.array(g_up + [np.inf] * len(a_src), dtype=np.float64)
+        return c, (rowptr, colidx.astype(np.int64), vals.astype(np.float64), m, n), q, m_ineq, l, u, q_upper
     return c, (rowptr, colidx.astype(np.int64), vals.astype(np.float64), m, n), q, m_ineq, l, u
 
 
@@ -180,3 +193,18 @@ def mps_to_standard_form(mps_file, device="cpu", support_sparse=True, verbose=Fa
     if verbose:
         print(f"Using Sparse operations ({m} x {n}, {K.nnz} non-zeros)")
     return t(c), K, t(q), m_ineq, t(l), t(u)
+
+
+def mps_to_ranged_form(mps_file, device="cpu", verbose=False, *, compat: bool = True, dtype=torch.float32):
+    """``(c, K, q, m_ineq, l, u, q_upper)``: ``mps_to_standard_form`` with every RANGES row kept as ONE two-sided row
+    ``q_i <= (K x)_i <= q_upper_i`` (``solve_lp(q_upper=...)``) at the position of the first of the two ``>=`` rows it becomes there;
+    deleting every second row of those pairs from the split form gives this ``K``, ``q`` and row order, and ``q_upper`` on the row is
+    minus the deleted row's ``q``.  ``q_upper`` is ``+inf`` on every other row; ``L`` rows are negated as always."""
+    c, (rowptr, colidx, vals, m, n), q, m_ineq, l, u, q_upper = parse_mps(mps_file, compat=compat, ranged=True)
+    dev = torch.device(device)
+    t = lambda a: torch.tensor(a, dtype=dtype, device=dev).view(-1, 1)
+    K = CsrPair(m, n, torch.from_numpy(rowptr).to(torch.int64), torch.from_numpy(colidx).to(torch.int32),
+                torch.from_numpy(vals).to(dtype)).to(dev)
+    if verbose:
+        print(f"Using Sparse operations ({m} x {n}, {K.nnz} non-zeros, {int(np.isfinite(q_upper).sum())} two-sided rows)")
+    return t(c), K, t(q), m_ineq, t(l), t(u), t(q_upper)

@@ -17,6 +17,7 @@ from . import _native as N
 from .engine import Comm, PdlpEngine
 from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, kkt_error, np_type, previous_kkt_matters,   # noqa: F401
                     primal_weight, restart_decision, start_eta, start_omega, terminated)
+from .ranged import REFUSED as RANGED_REFUSED, check_row_upper, norm_vector as ranged_norm_vector
 from .sparse import CsrPair, as_vec, resolve_device     # noqa: F401  (resolve_device: api.py and callers take it from here)
 
 
@@ -89,7 +90,11 @@ class PdhgDriver:
         self.primal_update, self.adaptive, self.precondition = bool(primal_update), bool(adaptive), bool(precondition)
         self.tol, self.verbose, self.trace = tol, verbose, trace
         self.t = np_type(eng.dtype)
-        self.q_norm = self.t(_global_norm(eng.q, eng.comm))                 # pdhg.py:19-20
+        # pdhg.py:19-20; with two-sided rows (the engine's q_upper) ||q|| is the norm of max(|q_i|, |q_upper_i|) on those rows
+        q_upper = getattr(eng, "q_upper", None)
+        if q_upper is not None and (adaptive_retry or infeasibility_detect or getattr(eng, "mixed", False) or eng.comm is not None):
+            raise ValueError(RANGED_REFUSED)
+        self.q_norm = self.t(_global_norm(ranged_norm_vector(eng.q, q_upper, getattr(eng, "m_ineq", 0)), eng.comm))
         self.c_norm = self.t(_global_norm(eng.c, eng.comm))
         self.n = self.k = self.j = self.tt = 0
         self.KKT_first = self.t(0)                                          # pdhg.py:48
@@ -372,7 +377,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
                    precondition=False, primal_update=False, adaptive=False, data_precond=None, infeasibility_detect=False,
                    infeas_tol=1e-4, time_limit=3600, time_used=0, x_init=None, y_init=None, *, b0=None, sigma=None,
                    seed=None, trace=None, comm=None, precision=None, adaptive_retry=False, report=None,
-                   halpern=False):
+                   halpern=False, q_upper=None):
     """Drop-in for the reference's ``pdlp_algorithm`` (primal_dual_hybrid_gradient.py:7) on one MI355X.
 
     ``K`` may be a dense / COO torch tensor (as the reference takes), a scipy sparse matrix or a
@@ -405,6 +410,13 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     ``y_init``; ``ValueError`` together with ``adaptive``, ``adaptive_retry``, ``infeasibility_detect``, ``precision="mixed"`` or
     ``comm``.
 
+    ``q_upper`` (length m, default None): two-sided rows ``q_i <= (K x)_i <= q_upper_i`` on the inequality rows, entered once
+    (``+inf``: a one-sided row; ``== q_i``: behaves as an equality row; on equality rows ``+inf`` or ``q_i``, ignored); the sign
+    of ``y`` says which side is active (``y_i > 0`` the lower, ``y_i < 0`` the upper); with ``precondition`` pass the scaled one
+    (``Scaling.scale``).  DESIGN.md 4.3.  Works with ``precondition``, ``primal_update``, ``adaptive``, ``halpern`` and ``x_init`` /
+    ``y_init`` in float32 and float64; ``ValueError`` (before any device work) for a malformed ``q_upper`` and together with
+    ``precision="mixed"``, ``comm``, ``infeasibility_detect`` or ``adaptive_retry``.
+
     ``comm`` (a ``Comm``, or ``True`` for the default ``torch.distributed`` group): every rank calls with the SAME
     full problem and the same ``seed``/``b0``; each keeps its row blocks of K and K', the iterations exchange
     ``xbar`` and ``y`` over RCCL, and every rank returns the full solution.
@@ -412,6 +424,10 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     from .distributed import gather_report, gather_solution, shard_engine, start_blocks
     if halpern and (adaptive or adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False)):
         raise ValueError(HALPERN_REFUSED)
+    if q_upper is not None:
+        if adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False):
+            raise ValueError(RANGED_REFUSED)
+        q_upper = check_row_upper(q, q_upper, m_ineq)
     device = resolve_device(device)
     Kp = CsrPair.from_any(K, device=device)
     dtype = Kp.dtype
@@ -439,7 +455,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
             b0 = eng.part.pad_cols(as_vec(b0, Kp.n, device, torch.float32))
         verbose = verbose and comm.rank == 0
     else:
-        eng = PdlpEngine.from_full(Kp, c, q, l, u, m_ineq, d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, exact=exact_K)
+        eng = PdlpEngine.from_full(Kp, c, q, l, u, m_ineq, d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, exact=exact_K, q_upper=q_upper)
     x, obj, k, n, j, status, total = run_pdlp(
         eng, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period, precondition=precondition,
         primal_update=primal_update, adaptive=adaptive, time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init,
