@@ -93,7 +93,14 @@ typedef struct pdlp_problem {
  * any 64 consecutive rows (one i of one wave) may hold at most 255 items of a tile -- the kernel scans the lanes'
  * counts in 8-bit fields.  float32 (and PDLP_MIXED, whose tiles are float32): rpt <= 40, cap <= 16384; float64: rpt <= 24,
  * cap <= 8192.  (slot, column) must pack into 32 bits: (cap + 8) << lw <= 2^32, i.e. lw <= 17 at the full float32 capacity
- * (the builder uses 16: a 256 KB panel stays L2-resident on every XCD and keeps the gathered lines dense). */
+ * (the builder uses 16: a 256 KB panel stays L2-resident on every XCD and keeps the gathered lines dense).
+ * The packed index stream (optional, PDLP_F32 handles, derived from idx and attached next to it: pdlp_pack_tile_items /
+ * pdlp_attach_packed_items; nothing of this struct changes): per group of 256 stored items the four index words of lane l
+ * (positions 4l..4l+3, one item of each 64-item run j = 0..3) become 12 bytes, four little-endian 24-bit fields
+ * (slot << 10) | (local column - run_base[j]), so a wave's chunk is 768 contiguous bytes and item offset i is byte 3 i (offsets
+ * are multiples of 256 items: 768-byte, 4-byte aligned steps).  run_base: one 16-bit number per run, four per chunk in two
+ * little-endian words, the smallest local column of the run's real items; padding items keep their slot and get column field 0.
+ * Item = 7 bytes plus 1/32 byte of bases.  A tile set qualifies when every run spans at most 1023 columns, cap <= 16384, lw <= 16. */
 typedef struct pdlp_tiles {
     int32_t lw, rpt, cap;       /* panel = 2^lw columns; rows per thread              ; most items per tile  */
     int32_t nblk, npanel;       /* row blocks, column panels                                               */
@@ -137,6 +144,21 @@ void pdlp_destroy(pdlp_handle h);
  * NULL goes back to the CSR arrays.  The arrays must outlive the handle and be 16-byte aligned.
  * Same results up to summation order; several times faster when the gathered vector exceeds the L2. */
 int pdlp_attach_tiles(pdlp_handle h, int transpose, const pdlp_tiles* t);
+/* 7-byte items for PDLP_F32 handles: the index stream of a float32 tile set in 24 bits per item (layout: the comment of struct
+ * pdlp_tiles).  pdlp_pack_tile_items (no handle; one device kernel on `stream`) reads idx[items] (items: a multiple of 256, lw: the
+ * tile set's) and writes, into the caller's buffers,
+ *   idx24     3 * items bytes, 4-byte aligned,
+ *   run_base  2 * (items / 256 + 32) words, 4-byte aligned: four 16-bit bases per chunk, then 32 zero entries (the kernel requests
+ *             a register group's bases unconditionally: up to 31 chunks past the last tile's end),
+ *   *flag     (device int32) 0, or 1 when some field does not fit: a 64-item run whose real items span more than 1023 columns, or
+ *             a slot above 16383.  The caller reads it once; with 1 the stream must not be attached.
+ * pdlp_attach_packed_items: products of a PDLP_F32 handle with K (transpose = 0) or K' (1) read idx24 / run_base instead of
+ * t->idx from now on, in fused launches and in panel groups alike -- the same products into the same slots, every result bit for bit
+ * what the 32-bit stream gives.  Valid after pdlp_attach_tiles, which detaches any earlier packed stream; NULLs detach.  t->idx must
+ * stay what it was.  PDLP_ERR_STATE: no tiles attached, a PDLP_F64 or PDLP_MIXED handle (their kernels keep the 32-bit words), the
+ * middle of a split product; PDLP_ERR_INVALID: cap above 16384, lw above 16, misaligned arrays. */
+int pdlp_pack_tile_items(const uint32_t* idx, int64_t items, int lw, uint32_t* idx24, uint32_t* run_base, int32_t* flag, void* stream);
+int pdlp_attach_packed_items(pdlp_handle h, int transpose, const uint32_t* idx24, const uint32_t* run_base);
 /* The CSR kernel's row blocks (built by pdlp_create: <= 256 rows, <= 2048 non-zeros each): *blocks = device array of
  * (first row, first non-zero) pairs, nblk + 1 of them.  For building the column-sorted copy below. */
 int pdlp_schedule_info(pdlp_handle h, int transpose, int32_t* nblk, const int64_t** blocks);

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """A/B timing of the two fused half-step kernels for several builds of the library in ONE process on ONE LP (run-to-run and
 box-to-box spread of a bench line is +-3 %, more than most kernel changes): python tools/ab_kernels.py lib1.so lib2.so ...
+A build is "lib.so", "lib.so:ENV=VALUE[,ENV=VALUE]" (the variables are set while that engine is built) or "packed=0" / "packed=1": the
+shipped library with that value of PDLP_PACKED_ITEMS, i.e. the 32-bit index stream and the 7-byte items of ONE library on the same
+LP -- list them alternately (packed=0 packed=1 packed=0 packed=1 ...): engine-to-engine placement noise is +-3-4 %.
 env: N (10M), K (100), REPS (60), ROUNDS (3), PDLP_RUNNING_KKT etc. apply to all."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,6 +42,8 @@ def measure(eng, adaptive=1):
 
 engines = []
 for spec in libs:                      # "lib.so" or "lib.so:ENV=VALUE" (the variable is set while that engine is built)
+    if spec.startswith("packed="):
+        spec = f"{N.LIB_PATH}:PDLP_PACKED_ITEMS={spec[7:]}"
     path, _, env = spec.partition(":")
     envs = [e.split("=") for e in env.split(",")] if env else []      # "lib.so:A=1,B=2"
     for kk, vv in envs:
@@ -47,10 +52,10 @@ for spec in libs:                      # "lib.so" or "lib.so:ENV=VALUE" (the var
     eng = tp.PdlpEngine.from_full(K, lp.c, lp.q, lp.l, lp.u, lp.m_ineq)
     eng.set_step(0.01, 1.0, 1.0, 0)
     eng.iterate(2, True)
-    engines.append((spec, eng))
+    engines.append((spec if ":" not in spec else os.path.basename(path) + ":" + env, eng))
     for kk, _ in envs:
         os.environ.pop(kk, None)
-    print(spec, eng.kernels, flush=True)
+    print(spec, eng.kernels, [None if t is None else t.stats.get("bytes_per_nnz") for t in eng.tiles], flush=True)
     for tr in (0, 1):
         t = eng.tiles[tr]
         if t is not None:

@@ -75,6 +75,8 @@ SIGNATURES = {
     "pdlp_create": (_I, [C.POINTER(_H), C.POINTER(PdlpProblem), _P, _I64]),
     "pdlp_destroy": (None, [_H]),
     "pdlp_attach_tiles": (_I, [_H, _I, C.POINTER(PdlpTiles)]),
+    "pdlp_pack_tile_items": (_I, [_P, _I64, _I, _P, _P, _P, _P]),
+    "pdlp_attach_packed_items": (_I, [_H, _I, _P, _P]),
     "pdlp_schedule_info": (_I, [_H, _I, C.POINTER(C.c_int32), C.POINTER(_P)]),
     "pdlp_attach_sorted": (_I, [_H, _I, _P, _P, _P]),
     "pdlp_buffer_ptr": (_I, [_H, _I, C.POINTER(_P)]),

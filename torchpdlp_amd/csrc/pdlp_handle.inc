@@ -25,6 +25,9 @@ struct Schedule {
     // panel-tiled copy (optional, attached by the caller): used instead of the CSR arrays when set
     bool tiled = false;
     pdlp_tiles t{};
+    // the tile set's packed index stream (pdlp_attach_packed_items: float32 handles; null = the kernel reads t.idx)
+    const uint32_t* idx24 = nullptr;
+    const uint32_t* run_base = nullptr;
     // sharded problems: the panels lying wholly inside the locally owned block of the gathered vector, [loc_pa, loc_pb),
     // can be multiplied before the all-gather of that vector has finished (pdlp_*_half_begin)
     int loc_pa = 0, loc_pb = 0;

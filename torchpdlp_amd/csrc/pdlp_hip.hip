@@ -150,7 +150,8 @@ inline int rows_grid(int64_t rows) { return rows > 0 ? grid_for(rows) : 0; }    
 // ================================================================================================
 extern "C" {
 
-// 18: pdlp_batch_* (batched solves over one matrix); pdlp_batch_attach_matrices, pdlp_batch_product and pdlp_halpern_iterate joined
+// 18: pdlp_batch_* (batched solves over one matrix); pdlp_batch_attach_matrices, pdlp_batch_product, pdlp_halpern_iterate and then
+//     pdlp_pack_tile_items / pdlp_attach_packed_items (7-byte items on the float32 path; struct pdlp_tiles is unchanged) joined
 //     them without a change to any existing signature or struct, so the number stands
 // 17: pdlp_peer_* (direct exchange over HIP IPC), PDLP_OPT_BEGIN_INLINE
 // 16: pdlp_set_option (the library reads no environment variables), pdlp_mv_product, pdlp_mv_combine, pdlp_vec_sqdist,
@@ -276,6 +277,7 @@ int pdlp_attach_tiles(pdlp_handle h, int transpose, const pdlp_tiles* t)
     if (!h) return PDLP_ERR_INVALID;
     Schedule& s = transpose ? h->sKT : h->sK;
     drop_graphs(h);               // captured launches name the old kernel and arrays
+    s.idx24 = s.run_base = nullptr;      // (a packed index stream belongs to the tile set it was made from: attach it again)
     if (!t) { s.tiled = false; return configure_split(h, transpose != 0); }
     const int64_t rows = transpose ? h->nl : h->ml;
     const int rpt_max = h->p.dtype == PDLP_F64 ? TileCfg<double, double>::RPT_MAX : TileCfg<float, float>::RPT_MAX;   // (mixed: float32 tiles)
@@ -295,6 +297,36 @@ int pdlp_attach_tiles(pdlp_handle h, int transpose, const pdlp_tiles* t)
     s.t = *t;
     s.tiled = true;
     return configure_split(h, transpose != 0);
+}
+
+int pdlp_pack_tile_items(const uint32_t* idx, int64_t items, int lw, uint32_t* idx24, uint32_t* run_base, int32_t* flag, void* stream)
+{
+    if (!idx || !idx24 || !run_base || !flag || items < 0 || (items & 255) || lw < 4 || lw > 16) return PDLP_ERR_INVALID;      // (a run base is 16 bits)
+    if (((uintptr_t)idx & 15u) || ((uintptr_t)idx24 & 3u) || ((uintptr_t)run_base & 3u) || ((uintptr_t)flag & 3u)) return PDLP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nchunks = items >> 8;
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(run_base + nchunks * 2, 0, (size_t)P24_BASE_TAIL * 8, st));      // the spare entries behind the last chunk
+    if (nchunks > 0) {
+        hipLaunchKernelGGL(k_pack_items24, dim3(grid_for(nchunks * 64)), dim3(BLOCK), 0, st, idx, nchunks, lw, idx24, run_base, flag);
+        HIP_TRY(hipGetLastError());
+    }
+    return PDLP_OK;
+}
+
+int pdlp_attach_packed_items(pdlp_handle h, int transpose, const uint32_t* idx24, const uint32_t* run_base)
+{
+    if (!h || (idx24 == nullptr) != (run_base == nullptr)) return PDLP_ERR_INVALID;
+    Schedule& s = transpose ? h->sKT : h->sK;
+    if (idx24) {
+        if (!s.tiled || h->p.dtype != PDLP_F32) return PDLP_ERR_STATE;      // float32 handles with tiles attached
+        if (s.t.cap > (1 << P24_SLOT_BITS) || s.t.lw > 16 || ((uintptr_t)idx24 & 3u) || ((uintptr_t)run_base & 3u)) return PDLP_ERR_INVALID;
+    }
+    if (s.pending) return PDLP_ERR_STATE;        // not in the middle of a split product
+    drop_graphs(h);               // captured launches name the other kernel
+    s.idx24 = idx24;
+    s.run_base = run_base;
+    return PDLP_OK;
 }
 
 int pdlp_schedule_info(pdlp_handle h, int transpose, int32_t* nblk, const int64_t** blocks)

@@ -24,6 +24,7 @@
 //   chunk u's gathers before issuing chunk u+1's; without the skip -- chunks past the end gather one cached word -- 2.0-2.2; with the skip and an
 //   explicit s_waitcnt vmcnt(0) at the top of the group, after which the chunks' gathers go out back to back, 2.01-2.12:
 //   four gathers at a time per wave, one chunk after the other, is what the memory pipeline likes).
+// float32 tile sets that qualify are read as 7-byte items (24-bit index words: the PACKED variant below, k_pack_items24).
 // After the last panel the row sums go through LDS once more so that the epilogue runs with consecutive lanes
 // on consecutive rows (coalesced vector traffic).
 // ------------------------------------------------------------------------------------------------
@@ -68,10 +69,22 @@ __device__ __forceinline__ double clamp01_t(double x) { return __builtin_fmin(__
 // a row block are split over `groups` workgroups (blockIdx = group * nblk + row block; needed when there are too
 // few rows for one workgroup per row block to fill the chip, e.g. one rank's shard of a sharded problem): each
 // writes its partial row sums to rowsum[group] and k_rowsum_epilogue adds them in fixed order.
-template <typename T, typename TV, class Epi, bool FUSED>
+// PACKED (float32 only; format: pack_items24 in torchpdlp_amd/tiled.py, written by k_pack_items24 below): the index stream is 3 bytes
+// per item instead of 4.  The four index words of a lane (one item of each of the chunk's four 64-item runs) are four little-endian
+// 24-bit fields (slot << 10) | (local column - run base) in 12 bytes, and trb holds the four run bases of every 256-item chunk as
+// four 16-bit numbers (8 bytes).  tidx then points to that stream (item offset i = byte 3 i) and only load_into / consume differ: one
+// 12-byte streaming load per lane and chunk, the bases of a wave's TU chunks in ONE vector load requested ahead of the group's
+// streaming loads (lane l gets word l & 1 of chunk (l >> 1) & 3; consume takes a base out with v_readlane), and gather j of a chunk
+// reads (xin + base j) + 4 * (field & 1023): the base goes into the SCALAR part of the address, the vector part costs what it cost.
+// (The bases as scalar loads, 16 scalar registers a group ahead, spilled: the 32-bit kernel already uses every scalar register, and
+// spilled scalars land in vector registers, of which it has none to spare either.  One vector register holds all sixteen.)
+// Same products into the same slots: bit for bit the sums of the 32-bit stream.
+constexpr int P24_COL_BITS = 10, P24_SLOT_BITS = 14;
+constexpr int P24_BASE_TAIL = TNT * 4 * TileCfg<float, float>::TU / 256;     // chunks a group may reach past the last tile's end: trb has that many spare (zero) entries
+template <typename T, typename TV, class Epi, bool FUSED, bool PACKED = false>
 __global__ __launch_bounds__(TNT, (TileCfg<T, TV>::MINW)) void k_tiled_fused(const uint32_t* __restrict__ tidx, const TV* __restrict__ tval,
                                                         const int32_t* __restrict__ tile_ptr, const int64_t* __restrict__ blk_base,
-                                                        const uint32_t* __restrict__ tcnt,
+                                                        const uint32_t* __restrict__ tcnt, const uint32_t* __restrict__ trb,
                                                         int npanel, int lw, int rpt, int nrows, int nblk,
                                                         int vtotal, const int32_t* __restrict__ ptab, int slot0, int b0, int nbl,
                                                         const T* __restrict__ vin, T* __restrict__ rowsum,
@@ -117,17 +130,44 @@ __global__ __launch_bounds__(TNT, (TileCfg<T, TV>::MINW)) void k_tiled_fused(con
     // One matrix copy may hold more than 2^31 items, but a row block never does: the block's position in the item arrays is a
     // 64-bit, wave-uniform number that goes into the base pointers once, and everything a thread indexes with is relative to it and
     // 32-bit (64-bit per-thread indices cost ten spilled registers and 7 % of the kernel: measured)
-    tidx += blk_base[b];
+    static_assert(!PACKED || (sizeof(T) == 4 && sizeof(TV) == 4 && TCAP <= (1 << P24_SLOT_BITS)), "packed items: float32 tiles only");
+    tidx += PACKED ? (blk_base[b] >> 2) * 3 : blk_base[b];       // (packed: 3 words per 4 items; the bases are multiples of 256 items)
     tval += blk_base[b];
-    auto load_into = [&](u32x4 (&pk)[TU], V4 (&vv)[TU], int g0, int i1) {
+    static_assert(!PACKED || TU == 4, "packed items: lane l holds bases of chunk (l >> 1) & 3");
+    if (PACKED) trb += (blk_base[b] >> 8) * 2;                    // two words (four 16-bit run bases) per 256-item chunk
+    // PACKED: pk[u].xyz are the lane's 12 bytes (w is not used); rbv: lanes 2u, 2u + 1 hold the four run bases of the wave's chunk u
+    auto load_into = [&](u32x4 (&pk)[TU], V4 (&vv)[TU], uint32_t& rbv, int g0, int i1) {
+        // the run bases first, so that they have landed when the first chunk's items have: an unconditional load (a chunk past the
+        // tile's end reads the entry of whatever chunk lies there, or one of the P24_BASE_TAIL spare entries behind the last)
+        // (PACKED addresses: uniform base + 32-bit byte offset per lane -- a row block of a packed tile set holds fewer than 2^30 items.
+        //  The empty asm makes the group's position an opaque scalar, so the offsets are computed from it where they are used: left
+        //  alone, the compiler turns every stream's address into a per-lane induction variable kept across the whole tile, as in the
+        //  32-bit form -- 18 vector registers as 64-bit addresses, 9 as 32-bit offsets, and the kernel then spills 9 or 2)
+        uint32_t gq = (uint32_t)g0 >> 2;
+        if (PACKED) {
+            asm volatile("" : "+s"(gq));
+            const uint32_t ob = ((((gq >> 6) + ((lane >> 1) & (TU - 1)) * (TNT / 64) + wv) << 1) + (lane & 1)) << 2;
+            rbv = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(trb) + ob);
+        }
 #pragma unroll
         for (int u = 0; u < TU; ++u) {
             const int i = g0 + (u * TNT + tid) * 4;
             if (i < i1) {
-                pk[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(tidx + i));
-                vv[u] = __builtin_nontemporal_load(reinterpret_cast<const V4*>(tval + i));
+                if (PACKED) {
+                    // three 4-byte loads of consecutive words: the compiler makes them ONE 12-byte load (global_load_dwordx3 ... nt; a
+                    // 3-element vector type would be loaded as 16 bytes, one word past the lane's items and, at the very end, past the array)
+                    const uint32_t i4 = gq + (uint32_t)(u * TNT + tid);               // = i / 4
+                    const uint32_t* __restrict__ q = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(tidx) + i4 * 12u);
+                    pk[u] = u32x4{__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1), __builtin_nontemporal_load(q + 2), 0u};
+                    vv[u] = __builtin_nontemporal_load(reinterpret_cast<const V4*>(reinterpret_cast<const char*>(tval) + i4 * 16u));
+                } else {
+                    pk[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(tidx + i));
+                    vv[u] = __builtin_nontemporal_load(reinterpret_cast<const V4*>(tval + i));
+                }
             } else {
-                pk[u] = u32x4{trash, trash, trash, trash};
+                // (a wave's chunk is 256 aligned items and so are the tiles: it lies wholly inside a tile or wholly past its end, where
+                //  consume skips it -- what is filled in here is never consumed; the 24-bit fields cannot name the trash slot, they get 0)
+                pk[u] = PACKED ? u32x4{0u, 0u, 0u, 0u} : u32x4{trash, trash, trash, trash};
                 vv[u] = V4{(TV)0, (TV)0, (TV)0, (TV)0};
             }
         }
@@ -144,19 +184,27 @@ __global__ __launch_bounds__(TNT, (TileCfg<T, TV>::MINW)) void k_tiled_fused(con
 #ifndef PDLP_ROUND
 #define PDLP_ROUND 4
 #endif
-    auto consume = [&](u32x4 (&pk)[TU], V4 (&vv)[TU], int g0, int i1, const T* __restrict__ xin) {
+    auto consume = [&](u32x4 (&pk)[TU], V4 (&vv)[TU], uint32_t rbv, int g0, int i1, const T* __restrict__ xin) {
         constexpr int RPC = 4 / PDLP_ROUND, NR = TU * RPC;          // rounds per chunk, rounds per group
         T xg[TU * 4];
         bool on[TU];
 #pragma unroll
         for (int u = 0; u < TU; ++u) on[u] = g0 + (u * TNT + __builtin_amdgcn_readfirstlane(wv) * 64) * 4 < i1;
-        auto pkw = [&](int u, int k) -> uint32_t { return k == 0 ? pk[u].x : k == 1 ? pk[u].y : k == 2 ? pk[u].z : pk[u].w; };
+        // PACKED: field k of the lane's 12 bytes in the low 24 bits (bits 24..31: the neighbouring field's, masked off by the users)
+        auto pkw = [&](int u, int k) -> uint32_t {
+            if (PACKED)
+                return k == 0 ? pk[u].x : k == 1 ? __builtin_amdgcn_alignbit(pk[u].y, pk[u].x, 24)
+                              : k == 2 ? __builtin_amdgcn_alignbit(pk[u].z, pk[u].y, 16) : pk[u].z >> 8;
+            return k == 0 ? pk[u].x : k == 1 ? pk[u].y : k == 2 ? pk[u].z : pk[u].w;
+        };
+        auto rbw = [&](int u, int k) -> uint32_t { return ((uint32_t)__builtin_amdgcn_readlane((int)rbv, 2 * u + (k >> 1)) >> (16 * (k & 1))) & 0xffffu; };
+        auto slot = [&](int u, int k) -> uint32_t { return PACKED ? (pkw(u, k) >> P24_COL_BITS) & ((1u << P24_SLOT_BITS) - 1u) : pkw(u, k) >> lw; };
         auto vvw = [&](int u, int k) -> TV { return k == 0 ? vv[u].x : k == 1 ? vv[u].y : k == 2 ? vv[u].z : vv[u].w; };
         auto products = [&](int r) {
             const int u = r / RPC, k0 = (r % RPC) * PDLP_ROUND;
             if (on[u]) {
 #pragma unroll
-                for (int k = k0; k < k0 + PDLP_ROUND; ++k) prod[pkw(u, k) >> lw] = (T)vvw(u, k) * xg[4 * u + k];
+                for (int k = k0; k < k0 + PDLP_ROUND; ++k) prod[slot(u, k)] = (T)vvw(u, k) * xg[4 * u + k];
             }
         };
 #pragma unroll
@@ -166,7 +214,11 @@ __global__ __launch_bounds__(TNT, (TileCfg<T, TV>::MINW)) void k_tiled_fused(con
             if (on[u]) {
 #pragma unroll
                 for (int k = k0; k < k0 + PDLP_ROUND; ++k) {
-                    xg[4 * u + k] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(xin) + ((pkw(u, k) & mask) * (uint32_t)sizeof(T)));
+                    if (PACKED)         // scalar base xin + run base, vector offset 4 * (field & 1023)
+                        xg[4 * u + k] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(xin + rbw(u, k)) +
+                                                                    ((pkw(u, k) << 2) & (((1u << P24_COL_BITS) - 1u) << 2)));
+                    else
+                        xg[4 * u + k] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(xin) + ((pkw(u, k) & mask) * (uint32_t)sizeof(T)));
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -191,10 +243,11 @@ __global__ __launch_bounds__(TNT, (TileCfg<T, TV>::MINW)) void k_tiled_fused(con
         for (int q = 4; q < TCW; ++q) cwd[q] = __builtin_nontemporal_load(tcnt + ntiles * TNT * 4 + (tile * (TCW > 4 ? TCW - 4 : 1) + (q - 4)) * TNT + tid);
     };
     u32x4 pk[TU];
+    uint32_t rbv = 0;
     V4 vv[TU];
     int i0 = has_panels ? tile_ptr[tp0 + pmap(p_lo)] : 0;
     int i1 = has_panels ? tile_ptr[tp0 + pmap(p_lo) + 1] : 0;
-    load_into(pk, vv, i0, i1);
+    load_into(pk, vv, rbv, i0, i1);
 
     for (int i = tid; i < TCAP + 8; i += TNT) prod[i] = (T)0;      // pass 2 reads past short rows with weight 0: never uninitialised words
     __syncthreads();
@@ -232,11 +285,11 @@ __global__ __launch_bounds__(TNT, (TileCfg<T, TV>::MINW)) void k_tiled_fused(con
         // otherwise delay the memory instructions everything waits for: 2.07 -> 1.87 ms per launch at 10M x 10M)
         __builtin_amdgcn_s_setprio(PDLP_PRIO_P1);
         for (int g0 = i0; g0 < i1; g0 += TGRP) {
-            consume(pk, vv, g0, i1, xin);
-            if (g0 + TGRP < i1) load_into(pk, vv, g0 + TGRP, i1);
-            else load_into(pk, vv, i0n, i1n);
+            consume(pk, vv, rbv, g0, i1, xin);
+            if (g0 + TGRP < i1) load_into(pk, vv, rbv, g0 + TGRP, i1);
+            else load_into(pk, vv, rbv, i0n, i1n);
         }
-        if (i0 >= i1) load_into(pk, vv, i0n, i1n);       // (an empty tile consumed nothing)
+        if (i0 >= i1) load_into(pk, vv, rbv, i0n, i1n);       // (an empty tile consumed nothing)
         {   // the next tile's segment lengths: unconditional loads (after the last tile: this tile's again), behind the streaming
             // loads of the next group; they have pass 2 and two barriers to land
             load_counts(cwn, tile0 + (v + 1 < p_hi ? pmap(v + 1) : p));
@@ -416,6 +469,53 @@ __global__ __launch_bounds__(BLOCK) void k_rowsum_epilogue(const T* __restrict__
             const double v = block_sum(acc[r], dred);
             if (threadIdx.x == 0) partials[(size_t)blockIdx.x * NACC + r] = v;
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// the packed index stream of a float32 tile set, made once from the 32-bit one (k_tiled_fused<..., PACKED>; the CPU model is
+// pack_items24 in torchpdlp_amd/tiled.py).  One wave per 256-item chunk: lane l holds positions 4l..4l+3, i.e. sorted items 64j + l
+// of the chunk's runs j = 0..3.  Padding items sit at the end of a tile's sorted order and all carry the same word (slot = the
+// tile's number of real items, column 0), so inside a chunk they are the items equal to the chunk's LAST sorted item when that one
+// has column 0 (if that item is a real one, every item of the chunk has column 0 and nothing depends on the distinction).  Run base =
+// smallest local column of the run's real items (0 for a run of padding); field = (slot << 10) | (column - base), column part 0 for
+// padding; the four bases of a chunk are stored as 16-bit numbers in two words (lw <= 16).  *flag is raised when a field does not
+// fit: a run spanning more than 1023 columns or a slot above 16383.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void k_pack_items24(const uint32_t* __restrict__ idx, int64_t nchunks, int lw, uint32_t* __restrict__ idx24,
+                                                        uint32_t* __restrict__ run_base, int32_t* __restrict__ flag)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t mask = (1u << lw) - 1u;
+    const int64_t stride = (int64_t)gridDim.x * (BLOCK / 64);
+    for (int64_t c = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); c < nchunks; c += stride) {
+        const u32x4 w4 = *(reinterpret_cast<const u32x4*>(idx) + c * 64 + lane);
+        const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+        const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)w4.w, 63);
+        const bool has_pad = (last & mask) == 0u;
+        uint32_t f[4], rb[4];
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool pad = has_pad && w[j] == last;
+            const uint32_t col = w[j] & mask, sl = w[j] >> lw;
+            uint32_t m = pad ? 0xffffffffu : col;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const uint32_t o = (uint32_t)__shfl_xor((int)m, off, 64);
+                m = o < m ? o : m;
+            }
+            rb[j] = m == 0xffffffffu ? 0u : m;
+            const uint32_t d = pad ? 0u : col - rb[j];
+            bad = bad || d >= (1u << P24_COL_BITS) || sl >= (1u << P24_SLOT_BITS);
+            f[j] = ((sl & ((1u << P24_SLOT_BITS) - 1u)) << P24_COL_BITS) | (d & ((1u << P24_COL_BITS) - 1u));
+        }
+        uint32_t* __restrict__ o = idx24 + (c * 64 + lane) * 3;
+        o[0] = f[0] | (f[1] << 24);
+        o[1] = (f[1] >> 8) | (f[2] << 16);
+        o[2] = (f[2] >> 16) | (f[3] << 8);
+        if (lane < 2) run_base[c * 2 + lane] = lane ? rb[2] | (rb[3] << 16) : rb[0] | (rb[1] << 16);
+        if (bad) *flag = 1;
     }
 }
 

@@ -17,9 +17,18 @@ void launch_tiled_groups(pdlp_handle h, const Schedule& s, int rows, const void*
     if (vtotal <= 0 || vgroups <= 0 || nbl <= 0) return;
     const int groups = vgroups < vtotal ? vgroups : vtotal;       // (the kernel splits the panels evenly: no group without panels)
     StoreEpi<T> none{nullptr};
+    if constexpr (std::is_same<T, float>::value && std::is_same<TV, float>::value) {
+        if (s.idx24) {      // the packed index stream (pdlp_attach_packed_items): same sums from 7 bytes per item
+            hipLaunchKernelGGL((k_tiled_fused<T, TV, StoreEpi<T>, false, true>), dim3(nbl * groups), dim3(TNT), 0, stream, s.idx24,
+                               (const TV*)s.t.val, s.t.tile_ptr, s.t.blk_base, s.t.cnt, s.run_base, s.t.npanel, s.t.lw, s.t.rpt, rows, s.t.nblk,
+                               vtotal, ptab, slot0, b0, nbl, (const T*)vin, (T*)h->rowsum, h->rs_stride, (const T*)nullptr, none, (double*)nullptr);
+            return;
+        }
+    }
     hipLaunchKernelGGL((k_tiled_fused<T, TV, StoreEpi<T>, false>), dim3(nbl * groups), dim3(TNT), 0, stream, s.t.idx,
-                       (const TV*)s.t.val, s.t.tile_ptr, s.t.blk_base, s.t.cnt, s.t.npanel, s.t.lw, s.t.rpt, rows, s.t.nblk, vtotal, ptab,
-                       slot0, b0, nbl, (const T*)vin, (T*)h->rowsum, h->rs_stride, (const T*)nullptr, none, (double*)nullptr);
+                       (const TV*)s.t.val, s.t.tile_ptr, s.t.blk_base, s.t.cnt, (const uint32_t*)nullptr, s.t.npanel, s.t.lw, s.t.rpt, rows,
+                       s.t.nblk, vtotal, ptab, slot0, b0, nbl, (const T*)vin, (T*)h->rowsum, h->rs_stride, (const T*)nullptr, none,
+                       (double*)nullptr);
 }
 
 // one phase of a split product (0: the own block's panels, 1 + c: the panels completed by chunk c of the exchange), over all row
@@ -59,9 +68,18 @@ int launch_mat(pdlp_handle h, bool transpose, const void* vin, Epi epi, double* 
             extra = ex;
         }
         if (s.t.groups == 1 && !(s.pending && h->use_split)) {
-            hipLaunchKernelGGL((k_tiled_fused<T, TV, Epi, true>), dim3(s.t.nblk), dim3(TNT), 0, h->stream, s.t.idx, (const TV*)s.t.val,
-                               s.t.tile_ptr, s.t.blk_base, s.t.cnt, s.t.npanel, s.t.lw, s.t.rpt, rows, s.t.nblk, s.t.npanel,
-                               (const int32_t*)nullptr, 0, 0, s.t.nblk, (const T*)vin, (T*)h->rowsum, h->rs_stride, extra, epi, partials);
+            bool packed = false;
+            if constexpr (std::is_same<T, float>::value && std::is_same<TV, float>::value) {
+                if ((packed = s.idx24 != nullptr))
+                    hipLaunchKernelGGL((k_tiled_fused<T, TV, Epi, true, true>), dim3(s.t.nblk), dim3(TNT), 0, h->stream, s.idx24, (const TV*)s.t.val,
+                                       s.t.tile_ptr, s.t.blk_base, s.t.cnt, s.run_base, s.t.npanel, s.t.lw, s.t.rpt, rows, s.t.nblk, s.t.npanel,
+                                       (const int32_t*)nullptr, 0, 0, s.t.nblk, (const T*)vin, (T*)h->rowsum, h->rs_stride, extra, epi, partials);
+            }
+            if (!packed)
+                hipLaunchKernelGGL((k_tiled_fused<T, TV, Epi, true>), dim3(s.t.nblk), dim3(TNT), 0, h->stream, s.t.idx, (const TV*)s.t.val,
+                                   s.t.tile_ptr, s.t.blk_base, s.t.cnt, (const uint32_t*)nullptr, s.t.npanel, s.t.lw, s.t.rpt, rows, s.t.nblk,
+                                   s.t.npanel, (const int32_t*)nullptr, 0, 0, s.t.nblk, (const T*)vin, (T*)h->rowsum, h->rs_stride, extra, epi,
+                                   partials);
         } else if (s.pending && h->use_split) {
             // the local panels were multiplied by pdlp_*_half_begin on the side stream (and the first chunks' panels by
             // pdlp_half_chunk as they arrived); now the remaining chunks' panels, then the sum over all slots in fixed order.

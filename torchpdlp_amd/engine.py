@@ -61,6 +61,8 @@ def knobs_from_env(env=None) -> Knobs:
     PDLP_LIB_COMM         off    "1" exactly: ``enable_library_comm()`` at construction (RCCL backend, an engine that may tile)
     PDLP_TILED            auto   0 / 1 / auto / time: the mode of ``engine_kernels.wants_tiles``
     PDLP_SORTED           auto   1: column-sorted row blocks for every matrix; 0: never; else for clustered matrices, if they pay
+    (PDLP_PACKED_ITEMS is not one of these: ``engine_kernels.packed_items_mode`` reads it whenever tiles are attached, so that one
+    process can alternate the two index streams engine by engine.)
     PDLP_TILE_LW, PDLP_TILE_RPT, PDLP_TILE_GROUPS  unset  integers (empty = unset): ``build_tiles(lw=, rpt=, groups=)``
     PDLP_PEER_TRACE       unset  non-empty: ``enable_peer_exchange`` reports its progress on stderr
 

@@ -3,6 +3,7 @@ panel-tiled one (the formats themselves: ``tiled.py``).  Mixed into ``PdlpEngine
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional
 
 import torch
@@ -14,6 +15,13 @@ from . import tiled as _tiled
 TILED_MIN_NNZ = 1 << 20          # non-zeros of the matrix
 TILED_MIN_COLS = 1 << 16         # entries of the gathered vector
 TILED_MIN_PER_ROW = 10           # non-zeros per row on average (``auto`` only)
+PACKED_ITEMS_DEFAULT = True      # float32 handles: 7-byte items for every tile set that qualifies (PDLP_PACKED_ITEMS unset)
+
+
+def packed_items_mode(env=None) -> str:
+    """``PDLP_PACKED_ITEMS``, read when tiles are attached (for A/B in one process, like ``PDLP_TILED``): "0" the 32-bit index words,
+    "1" 7-byte items or an error, anything else (unset: "auto") ``PACKED_ITEMS_DEFAULT`` for every tile set that qualifies"""
+    return (os.environ if env is None else env).get("PDLP_PACKED_ITEMS", "auto") or "auto"
 
 
 def wants_tiles(mode: str, rows: int, cols: int, nnz: int) -> bool:
@@ -132,4 +140,46 @@ class KernelChoice:
         N.check(self.lib.pdlp_attach_tiles(self.h, int(transpose), C.byref(desc)), "pdlp_attach_tiles")
         self._plans = {}
         self.tiles[int(transpose)] = t       # keep the arrays alive
-        self.kernels[int(transpose)] = ("tiled" if t.groups == 1 else f"tiled/{t.groups} groups") + (f" + remainder {t.nrem}" if t.nrem else "")
+        packed = self._maybe_attach_packed_items(int(transpose), t)
+        # (a float32 engine's tiles are read as 7-byte items unless the name says otherwise; the other precisions know 32-bit words only)
+        self.kernels[int(transpose)] = ("tiled" if t.groups == 1 else f"tiled/{t.groups} groups") + (f" + remainder {t.nrem}" if t.nrem else "") + \
+            (", 32-bit items" if self._packed_items_apply() and not packed else "")
+
+    def _packed_items_apply(self) -> bool:
+        """7-byte items exist for the float32 kernels only (mixed precision shares the float32 tile set and keeps its 32-bit words)"""
+        return self.dtype == torch.float32 and not self.mixed
+
+    def _maybe_attach_packed_items(self, transpose: int, t: "_tiled.Tiles") -> bool:
+        """7-byte items (``tiled.pack_items24``: 24-bit index words next to the 32-bit ones, which stay for the other precisions) for the
+        float32 kernels of this handle: ``PDLP_PACKED_ITEMS`` = 0 never, 1 always (an error if a run does not fit), else
+        ``PACKED_ITEMS_DEFAULT``.  Whether a tile set qualifies depends on the matrix alone, like the choice between tiles and CSR:
+        every run decides the same (and the results are the same bits either way).  Recorded in ``t.stats`` (``packed_items``,
+        ``bytes_per_nnz``) and in ``self.kernels``: a float32 engine's tile set that stays on the 32-bit words is named
+        "..., 32-bit items"."""
+        mode = packed_items_mode()
+        want = self._packed_items_apply() and (mode == "1" or (mode != "0" and PACKED_ITEMS_DEFAULT))
+        packed = False
+        if want and not _tiled.packed_items_shape_ok(t):
+            if mode == "1":
+                raise N.PdlpError(f"PDLP_PACKED_ITEMS=1: the tile set does not qualify (cap {t.cap}, lw {t.lw}, or a row block of 2^30 items)")
+        elif want:
+            idx24 = torch.empty(t.items // 4 * 3, dtype=torch.int32, device=self.device)
+            run_base = torch.empty(2 * (t.items // _tiled.GROUP + _tiled.P24_TAIL), dtype=torch.int32, device=self.device)
+            flag = torch.empty(1, dtype=torch.int32, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()          # (t.idx may have been written on another stream)
+            N.check(self.lib.pdlp_pack_tile_items(t.idx.data_ptr(), t.items, t.lw, idx24.data_ptr(), run_base.data_ptr(), flag.data_ptr(),
+                                                  self.stream.cuda_stream), "pdlp_pack_tile_items")
+            self.stream.synchronize()
+            if int(flag.item()) == 0:
+                N.check(self.lib.pdlp_attach_packed_items(self.h, transpose, idx24.data_ptr(), run_base.data_ptr()), "pdlp_attach_packed_items")
+                t._idx24, t._run_base = idx24, run_base       # keep the arrays alive
+                packed = True
+            elif mode == "1":
+                raise N.PdlpError("PDLP_PACKED_ITEMS=1: a run of 64 sorted items spans more than 1023 columns")
+        if not packed:
+            t._idx24 = t._run_base = None
+        nnz = max(int(t.stats.get("tiled", t.items)), 1)
+        extra = int(t._run_base.numel()) * 4 if packed else 0
+        t.stats["packed_items"] = packed
+        t.stats["bytes_per_nnz"] = (t.items * (7 if packed else 8) + extra + int(t.cnt.numel()) * 4) / nnz
+        return packed

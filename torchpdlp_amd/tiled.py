@@ -23,7 +23,8 @@ group of 256 column-sorted items the storage order is interleaved: position ``4*
 ``64*j + lane``.  A lane's 16-byte load then yields items j = 0..3 of four different 64-item runs and gather
 instruction j covers 64 CONSECUTIVE sorted items (about 25 lines at 100 non-zeros per row) instead of 64 items
 spaced four apart (64 lines).  Bytes per non-zero: 8 + 20*512*P/nnz_per_block (the count nibbles): about 8.9 for
-100 non-zeros per row at 10M columns.
+100 non-zeros per row at 10M columns -- and about 7.9 for float32 engines, which read the index words as 24-bit fields (7-byte
+items: ``pack_items24`` below; ``Tiles.idx`` stays for the other precisions).
 
 Limits of the tiles proper: at most ``cap`` items per tile (16384 in float32, 8192 in float64), at most 15 items of one row
 in one tile (4-bit counts) and at most 255 items of 64 consecutive rows in one tile (the kernel scans the lanes' counts in 8-bit
@@ -457,6 +458,80 @@ def emulate_spmv(t: Tiles, x: torch.Tensor) -> torch.Tensor:
         for i, r in enumerate(t.rem_rows.tolist()):
             y[r] += seg[rptr[i]:rptr[i + 1]].sum()
     return y[:t.nrows]
+
+
+# ---- 7-byte items: the index stream of a float32 tile set in 24 bits per item ----------------------------------------------------
+# (``pdlp_pack_tile_items`` / ``pdlp_attach_packed_items``, include/pdlp_hip.h; read by k_tiled_fused<float, float, ..., PACKED>)
+# Derived from ``Tiles.idx``, which stays: per chunk of 256 stored items the four index words of lane ``l`` (positions 4l..4l+3, one
+# item of each 64-item run j = 0..3) become four little-endian 24-bit fields ``(slot << 10) | (local column - run_base[j])`` in 12
+# bytes, so item offset i is byte 3 i.  ``run_base``: per run the smallest local column of its REAL items (0 for a run of padding),
+# four 16-bit numbers per chunk in two words, then P24_TAIL zero entries (the kernel requests a register group's bases
+# unconditionally, up to 31 chunks past the last tile's end).  Padding items keep their slot and get column field 0.
+P24_COL_BITS = 10            # a run of 64 consecutive sorted items may span 1023 columns (the bench LP: about 320)
+P24_SLOT_BITS = 14           # cap <= 16384
+P24_TAIL = 32                # spare run-base entries behind the last chunk (items of one register group / 256)
+
+
+def packed_items_shape_ok(t: Tiles) -> bool:
+    """what the packed stream needs of a tile set apart from narrow runs: float32, slots of 14 bits, run bases of 16 bits and row
+    blocks below 2^30 items (the packed kernel adds 32-bit byte offsets to a row block's base)"""
+    if t.val.dtype != torch.float32 or t.cap > (1 << P24_SLOT_BITS) or t.lw > 16:
+        return False
+    return t.items == 0 or int(t.abi_tile_ptr()[0].max()) < 2 ** 30
+
+
+def pack_items24(t: Tiles):
+    """``(idx24 int32 [3 * items / 4], run_base int32 [2 * (items / 256 + P24_TAIL)], fits)``: the CPU model of the device packer
+    (k_pack_items24), byte for byte; ``fits`` is False when some run spans more than 1023 columns or a slot exceeds 14 bits (the
+    arrays then hold truncated fields and must not be used).  Padding items sit at the end of a tile's sorted order and all carry
+    the same word, so inside a chunk they are the items equal to the chunk's last sorted item when that one has column 0."""
+    if t.lw > 16:
+        raise ValueError("run bases are 16-bit: lw <= 16")
+    dev = t.idx.device
+    w = (t.idx.long() & 0xFFFFFFFF).view(-1, 64, 4)                       # [chunk, lane, run]
+    mask = (1 << t.lw) - 1
+    last = w[:, 63, 3].view(-1, 1, 1)
+    pad = ((last & mask) == 0) & (w == last)
+    col, sl = w & mask, w >> t.lw
+    big = 1 << 32
+    m = torch.where(pad, big, col).amin(dim=1) if w.numel() else col.new_zeros((0, 4))
+    rb = torch.where(m == big, 0, m)                                      # [chunk, run]
+    d = torch.where(pad, 0, col - rb.view(-1, 1, 4))
+    fits = not bool(((d >= (1 << P24_COL_BITS)) | (sl >= (1 << P24_SLOT_BITS))).any())
+    f = ((sl & ((1 << P24_SLOT_BITS) - 1)) << P24_COL_BITS) | (d & ((1 << P24_COL_BITS) - 1))
+    by = torch.stack([f & 255, (f >> 8) & 255, (f >> 16) & 255], dim=-1).to(torch.uint8)      # little-endian 24-bit fields
+    idx24 = by.reshape(-1).view(torch.int32) if by.numel() else torch.zeros(0, dtype=torch.int32, device=dev)
+    rbw = torch.stack([rb[:, 0] | (rb[:, 1] << 16), rb[:, 2] | (rb[:, 3] << 16)], dim=-1)
+    run_base = torch.cat([_wrap_i32(rbw.reshape(-1)), torch.zeros(2 * P24_TAIL, dtype=torch.int32, device=dev)])
+    return idx24, run_base, fits
+
+
+def tile_item_counts(t: Tiles) -> torch.Tensor:
+    """real items of every tile (the sum of its 4-bit counts), int64 [nblk * npanel]"""
+    ntiles = t.nblk * t.npanel
+    n4 = ntiles * t.nt * 4
+    w = torch.cat([t.cnt[:n4].view(ntiles, -1), t.cnt[n4:].view(ntiles, -1)], dim=1).long() & 0xFFFFFFFF
+    shifts = (torch.arange(8, device=w.device) * 4).view(1, 1, 8)
+    return ((w.unsqueeze(-1) >> shifts) & 15).sum((1, 2))
+
+
+def unpack_items24(idx24: torch.Tensor, run_base: torch.Tensor, t: Tiles) -> torch.Tensor:
+    """the 32-bit index words ``(slot << lw) | local column`` (int32, like ``Tiles.idx``) out of the packed stream of tile set
+    ``t`` (its ``lw``, ``tile_ptr`` and counts say which stored items are padding: those get column 0 again)"""
+    by = idx24.view(torch.uint8).long().view(-1, 64, 4, 3)
+    f = by[..., 0] | (by[..., 1] << 8) | (by[..., 2] << 16)                # [chunk, lane, run]
+    nch = f.shape[0]
+    rbw = run_base[:2 * nch].long().view(-1, 2) & 0xFFFFFFFF
+    rb = torch.stack([rbw[:, 0] & 0xFFFF, rbw[:, 0] >> 16, rbw[:, 1] & 0xFFFF, rbw[:, 1] >> 16], dim=-1)
+    # sorted position of every stored item inside its tile against the tile's real items
+    tp = t.tile_ptr.long()
+    tile_of_chunk = torch.repeat_interleave(torch.arange(tp.numel() - 1, device=tp.device), (tp[1:] - tp[:-1]) // GROUP)
+    first = tp[:-1][tile_of_chunk] // GROUP
+    pos = ((torch.arange(nch, device=tp.device) - first) * GROUP).view(-1, 1, 1) + \
+        torch.arange(64, device=tp.device).view(1, 64, 1) + 64 * torch.arange(4, device=tp.device).view(1, 1, 4)
+    real = pos < tile_item_counts(t)[tile_of_chunk].view(-1, 1, 1)
+    col = torch.where(real, rb.view(-1, 1, 4) + (f & ((1 << P24_COL_BITS) - 1)), 0)
+    return _wrap_i32(((f >> P24_COL_BITS) << t.lw) | col).reshape(-1)
 
 
 # ---- column-sorted row blocks: the CSR kernel's format for matrices whose entries cluster ---------------------------------------
