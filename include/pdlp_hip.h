@@ -275,6 +275,29 @@ int pdlp_halpern_iterate(pdlp_handle h, int iters);
  * pdlp_comm_init and pdlp_peer_connect return PDLP_ERR_STATE. */
 int pdlp_set_row_upper(pdlp_handle h, const void* q_upper_local);
 
+/* ---- diagonal quadratic objective -------------------------------------------------------------------------------------------
+ * min c'x + 1/2 sum_j d_j x_j^2 over the same constraints, d >= 0 (no counterpart in the reference).  d_local: this handle's
+ * variables (length n), in the working dtype, device memory the caller keeps alive like c; NULL switches the term off again.
+ * Entries: finite, d_j >= 0; d_j = 0 is a variable without the term.  The library does not inspect the values (they are device
+ * memory): the caller validates them.  With preconditioning (x = D_col x_s) pass d_s = d D_col^2.
+ * The primal half-step (fixed, adaptive and the Halpern candidate) forms v = (x_j - tau (c_j - (K'y)_j)) / (1 + tau d_j) and then
+ * clamps to [l_j, u_j] (the prox of the objective stays closed form; with d_j = 0 the division is by 1 and exact); xbar, the sums
+ * and the Halpern combination follow from v as always.  pdlp_kkt_local and pdlp_report_local take g_j = c_j + d_j x_j - (K'y)_j
+ * (formed from the scaled operands, before `unscaled` divides it) where they take c_j - (K'y)_j: lam, the dual residual, the
+ * bound terms and the reduced costs come from g.  The SIX SUMS KEEP THEIR PLACES (PDLP_NRED is unchanged): with
+ * h_j = 1/2 d_j x_j^2 accumulated in double, PDLP_BUF_RED[3] (c'x) receives c_j x_j + h_j and PDLP_BUF_RED[1] (l_dual'max(lam,0))
+ * receives -h_j besides its own term, so pdlp_kkt_finish returns prim_obj = c'x + 1/2 x'Dx, adjusted_dual = q'y + l'lam+ + u'lam-
+ * - 1/2 x'Dx and their gap with no change.  h is invariant under the scaling, so `unscaled` needs no factor of its own.
+ * The constraint side, two-sided rows (a handle may have both), the restart distance, the averages and the power iteration do
+ * not change.
+ * The call drops the captured graphs (PDLP_OPT_GRAPH captures again with the new functors) and what the handle carries from a KKT
+ * pass: the candidates' products and the kept K'y.
+ * PDLP_ERR_STATE: PDLP_MIXED handles (delta mode or not), a shard of a problem, a handle with a communicator or a peer exchange.
+ * While it is set, pdlp_infeas_reset / pdlp_infeas_begin / pdlp_infeas_local / pdlp_infeas_finish, pdlp_mv_steps / pdlp_mv_gap /
+ * pdlp_mv_product, pdlp_comm_init, pdlp_peer_connect and every pdlp_batch_* call return PDLP_ERR_STATE; so does pdlp_set_delta(on),
+ * because it needs a PDLP_MIXED handle and such a handle never has the term. */
+int pdlp_set_objective_diag(pdlp_handle h, const void* d_local);
+
 /* ---- sharded problems: the exchange inside the library (RCCL over xGMI) ------------------------------------------------
  * One process per GPU; rank r owns block r of the constraints and of the variables (equal, padded blocks -- the layout of
  * torchpdlp_amd/distributed.py).  The reference is single-device, so these have no counterpart there; SURVEY.md 8b sketched

@@ -99,6 +99,7 @@ SIGNATURES = {
     "pdlp_iterate": (_I, [_H, _I, _I]),
     "pdlp_halpern_iterate": (_I, [_H, _I]),
     "pdlp_set_row_upper": (_I, [_H, _P]),
+    "pdlp_set_objective_diag": (_I, [_H, _P]),
     "pdlp_set_exchange_chunks": (_I, [_H, _I]),
     "pdlp_set_option": (_I, [_H, _I, _I64]),
     "pdlp_exchange_plan": (_I, [_H, _I, C.POINTER(C.c_int32), C.POINTER(_I64)]),

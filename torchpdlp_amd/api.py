@@ -69,7 +69,7 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
              fishnet: bool = False, comm=None, infeasibility_detect: bool = False, infeas_tol: float = 1e-4,
              precision: Optional[str] = None, adaptive_retry: bool = False, direct_exchange: bool = False,
              report: bool = True, pock_chambolle: bool = False, halpern: bool = False, q_upper=None,
-             ranged_rows: bool = False) -> LPResult:
+             ranged_rows: bool = False, quad_diag=None) -> LPResult:
     """Solve ``min c'x, K[:m_ineq]x >= q[:m_ineq], K[m_ineq:]x = q[m_ineq:], l <= x <= u`` on the current HIP device.
 
     ``problem`` is an MPS path or ``(c, K, q, m_ineq, l, u)`` with ``K`` dense / COO / scipy-sparse / ``CsrPair``.
@@ -102,6 +102,16 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     ``pock_chambolle``, ``primal_weight_update``, ``adaptive_stepsize``, ``halpern``, ``x_init`` / ``y_init`` and ``report`` in
     float32 and float64; ``ValueError`` (before any device work) for a malformed ``q_upper`` and together with
     ``precision="mixed"``, ``comm``, ``infeasibility_detect``, ``fishnet`` and ``adaptive_retry``.
+    ``quad_diag`` (length n, ``d >= 0``; not in the reference): a separable quadratic term in the objective,
+    ``min c'x + 1/2 sum_j d_j x_j^2`` over the same constraints: ridge-regularised LPs, the proximal term
+    ``rho/2 ||x - xbar||^2`` of an outer loop (``d = rho``, ``c - rho xbar``), diagonal-risk models.  ``objective`` is then the quadratic
+    objective, ``dual_objective`` its dual ``q'y + l'lam+ + u'lam- - 1/2 x'Dx`` and ``reduced_costs`` are
+    ``project_lambda_box(c + Dx - K'y)``.  Works with ``precondition``, ``pock_chambolle``, ``primal_weight_update``,
+    ``adaptive_stepsize``, ``halpern``, ``q_upper`` / ``ranged_rows``, ``x_init`` / ``y_init`` and ``report`` in float32 and float64;
+    ``ValueError`` (before any device work) for a malformed vector and together with ``precision="mixed"``, ``comm``,
+    ``direct_exchange`` (a flag of sharded solves), ``infeasibility_detect``, ``fishnet`` and ``adaptive_retry``.  With an MPS path the
+    vector's length can only be compared with ``n`` after the file is read, which puts the problem on the device; everything else
+    about it is checked first.  MPS ``QUADOBJ`` / ``QMATRIX`` sections are not read.
     """
     _check_pock_chambolle(pock_chambolle, precondition)
     from_file = isinstance(problem, (str, os.PathLike))
@@ -114,6 +124,13 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
             raise ValueError(REFUSED)
         if q_upper is not None:
             check_row_upper(problem[2], q_upper, problem[3])
+    if quad_diag is not None:
+        from .quad import REFUSED as QUAD_REFUSED, check_quad_diag
+        if (is_mixed(precision) or comm not in (None, False) or infeasibility_detect or fishnet or adaptive_retry
+                or direct_exchange):
+            raise ValueError(QUAD_REFUSED)
+        # (an MPS path: shape, sign and finiteness now, the length once the file is read)
+        quad_diag = check_quad_diag(quad_diag, None if from_file else torch.as_tensor(problem[0]).numel())
     if halpern and (adaptive_stepsize or adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False)
                     or direct_exchange):
         from .solver import HALPERN_REFUSED
@@ -141,8 +158,14 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     else:
         c, K, q, m_ineq, l, u = load_problem(problem, device, dtype, verbose, compat)
     time_used, data_precond = 0.0, None
-    Ks, cs, qs, ls, us, qus = K, c, q, l, u, q_upper
-    if precondition and q_upper is not None:
+    if quad_diag is not None:
+        quad_diag = check_quad_diag(quad_diag, c.numel())                # (a problem read from a file: its n is known only now)
+    Ks, cs, qs, ls, us, qus, ds = K, c, q, l, u, q_upper, quad_diag
+    if precondition and quad_diag is not None:
+        Ks, cs, qs, ls, us, *more, data_precond, time_used = ruiz_precondition(c, K, q, l, u, device=device, pock_chambolle=pock_chambolle,
+                                                                               q_upper=q_upper, quad_diag=quad_diag)
+        qus, ds = (more[0], more[1]) if q_upper is not None else (None, more[0])
+    elif precondition and q_upper is not None:
         Ks, cs, qs, ls, us, qus, data_precond, time_used = ruiz_precondition(c, K, q, l, u, device=device, pock_chambolle=pock_chambolle,
                                                                              q_upper=q_upper)
     elif precondition:                                                  # main.py:106-110
@@ -156,7 +179,8 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     rep = {} if report else None
     x, obj, k, n, j, status, total = pdlp_algorithm(
         Ks, m_ineq, cs, qs, ls, us, device, verbose=verbose, data_precond=data_precond, time_used=time_used, x_init=x_init,
-        y_init=y_init, seed=seed, comm=comm, precision=precision, report=rep, **({} if qus is None else dict(q_upper=qus)), **run)
+        y_init=y_init, seed=seed, comm=comm, precision=precision, report=rep, **({} if qus is None else dict(q_upper=qus)),
+        **({} if ds is None else dict(quad_diag=ds)), **run)
     if precondition:        # the reference returns the scaled iterate (quirk Q4); solve_lp un-scales: x = D_col x_s (pdhg.py:161)
         x = Scaling(*data_precond[:2]).unscale_x(x)
     return LPResult(x, obj, k, n, j, status, total, **report_fields(rep))

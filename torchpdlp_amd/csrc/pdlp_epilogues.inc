@@ -48,9 +48,25 @@ template <typename T> struct RowUpper<T, false> {};
 // Written from a < 0 so that with q_upper = +inf (b = +inf) the value is the one-sided `a < 0 ? 0 : a` bit for bit (a = -0 included).
 template <typename T> __device__ __forceinline__ T ranged_dual(T a, T b) { return a < (T)0 ? (b < (T)0 ? b : (T)0) : a; }
 
+// Diagonal quadratic objective (pdlp_set_objective_diag): min c'x + 1/2 sum_j d_j x_j^2, d >= 0.  QUAD = true adds ONE operand to the
+// variable-side functors -- d[j], loaded in pre() beside c[j] -- the division of the primal half-step's prox and the term d_j x_j of
+// the gradient; QUAD = false (the default) has neither the pointer in the kernel arguments nor the value in the operand set (the tiled
+// kernel sizes its epilogue groups by sizeof(Pre)), so those instantiations are what they were before the quadratic term existed.
+// Only PEER = false functors have the QUAD form: a handle with the term is one GPU without an exchange.
+template <typename T, bool QUAD> struct ObjDiag { const T* p = nullptr; };
+template <typename T> struct ObjDiag<T, false> {};
+// the prox of tau (c'x + 1/2 x'Dx) at z = x - tau (c - K'y): z / (1 + tau d), before the clamp; d = 0 divides by 1, which is exact
+template <typename T> __device__ __forceinline__ T quad_prox(T z, T tau, T dj) { return z / ((T)1 + tau * dj); }
+// 1/2 d_j x_j^2 in double: joins c_j x_j in the primal objective's sum and leaves the sum l'max(lam, 0) of the dual objective.  Formed
+// from the SCALED pair (d_s = d D_col^2, x_s = x / D_col), of which it is invariant, so UNSCALE needs no factor of its own.
+template <typename T> __device__ __forceinline__ double quad_half(T dj, T xj) { return 0.5 * (double)dj * ((double)xj * (double)xj); }
+
 // primal half-step over this rank's rows of K' (= its variables).  kty = (K'y)_j.
 // step.py:25-30 (fixed) / :74-82 (adaptive); running sum pdhg.py:107.
-template <typename T, bool ADAPT, bool PEER = false> struct PrimalEpi {
+template <typename T, bool QUAD> struct PrimalPre { T xo, cj, lo, hi, sum, ks; };
+template <typename T> struct PrimalPre<T, true> { T xo, cj, lo, hi, sum, ks, dj; };
+template <typename T, bool ADAPT, bool PEER = false, bool QUAD = false> struct PrimalEpi {
+    static_assert(!(QUAD && PEER), "the quadratic term has no sharded form");
     static constexpr int NA = ADAPT ? 1 : 0;
     const T* x_old; T* x_new; T* xbar; const T* c; const T* l; const T* u; T* x_sum; const double* sc;
     // kty_sum (or null): running sum of w_k K'y_k -- K'y of the averaged iterate without a product at the restart check.  The
@@ -59,6 +75,7 @@ template <typename T, bool ADAPT, bool PEER = false> struct PrimalEpi {
     T* kty_sum = nullptr;
     T tau = 0, theta = 0, w = 0, wk = 0;
     PeerOut<T, PEER> peer{};               // the other ranks' xbar, at this rank's block
+    [[no_unique_address]] ObjDiag<T, QUAD> diag{};          // d of this rank's variables
     __device__ void load()
     {
         tau = (T)sc[S_TAU];
@@ -66,8 +83,12 @@ template <typename T, bool ADAPT, bool PEER = false> struct PrimalEpi {
         w = ADAPT ? (T)sc[S_WPEND] : (T)sc[S_ETA];
         wk = w;
     }
-    struct Pre { T xo, cj, lo, hi, sum, ks; };
-    __device__ Pre pre(int j) const { return Pre{x_old[j], c[j], l[j], u[j], x_sum[j], kty_sum ? kty_sum[j] : (T)0}; }
+    typedef PrimalPre<T, QUAD> Pre;
+    __device__ Pre pre(int j) const
+    {
+        if constexpr (QUAD) return Pre{x_old[j], c[j], l[j], u[j], x_sum[j], kty_sum ? kty_sum[j] : (T)0, diag.p[j]};
+        else return Pre{x_old[j], c[j], l[j], u[j], x_sum[j], kty_sum ? kty_sum[j] : (T)0};
+    }
     __device__ void operator()(int j, T kty, double* acc) const { (*this)(j, kty, pre(j), acc); }
     __device__ void operator()(int j, T kty, const Pre& p, double* acc) const
     {
@@ -75,6 +96,7 @@ template <typename T, bool ADAPT, bool PEER = false> struct PrimalEpi {
         const T grad = p.cj - kty;
         if (kty_sum) kty_sum[j] = p.ks + wk * kty;
         T v = xo - tau * grad;
+        if constexpr (QUAD) v = quad_prox(v, tau, p.dj);
         const T lo = p.lo, hi = p.hi;
         v = v < lo ? lo : v;
         v = v > hi ? hi : v;
@@ -151,20 +173,28 @@ template <typename T, bool ADAPT, bool PEER = false, bool RANGED = false> struct
 // x' and xbar are formed with PrimalEpi's own expressions at theta = 1 (the candidate equals one fixed PDHG step bit for bit);
 // the new iterate is the reflected point xbar = 2x' - x pulled towards the anchor: x+ = a xbar + b x_last, a = (t+1)/(t+2),
 // b = 1/(t+2) rounded once on the host.  No running sums: five operand loads, three stores.
-template <typename T> struct HalpernPrimalEpi {
+template <typename T, bool QUAD> struct HalpernPrimalPre { T xo, xl, cj, lo, hi; };
+template <typename T> struct HalpernPrimalPre<T, true> { T xo, xl, cj, lo, hi, dj; };
+template <typename T, bool QUAD = false> struct HalpernPrimalEpi {
     static constexpr int NA = 0;
     const T* x_old; T* x_new; T* xbar; T* x_cand; const T* x_last; const T* c; const T* l; const T* u; const double* sc;
     T a, b;
     T tau = 0;
+    [[no_unique_address]] ObjDiag<T, QUAD> diag{};
     __device__ void load() { tau = (T)sc[S_TAU]; }
-    struct Pre { T xo, xl, cj, lo, hi; };
-    __device__ Pre pre(int j) const { return Pre{x_old[j], x_last[j], c[j], l[j], u[j]}; }
+    typedef HalpernPrimalPre<T, QUAD> Pre;
+    __device__ Pre pre(int j) const
+    {
+        if constexpr (QUAD) return Pre{x_old[j], x_last[j], c[j], l[j], u[j], diag.p[j]};
+        else return Pre{x_old[j], x_last[j], c[j], l[j], u[j]};
+    }
     __device__ void operator()(int j, T kty, double* acc) const { (*this)(j, kty, pre(j), acc); }
     __device__ void operator()(int j, T kty, const Pre& p, double*) const
     {
         const T xo = p.xo;
         const T grad = p.cj - kty;
         T v = xo - tau * grad;
+        if constexpr (QUAD) v = quad_prox(v, tau, p.dj);
         const T lo = p.lo, hi = p.hi;
         v = v < lo ? lo : v;
         v = v > hi ? hi : v;
@@ -208,18 +238,30 @@ template <typename T, bool RANGED = false> struct HalpernDualEpi {
 };
 
 // KKT, dual side (helpers.py:75-84,94 with project_lambda_box helpers.py:21-37 and pdhg.py:11-17)
-template <typename T, bool UNSCALE> struct KktDualEpi {
+// Quadratic term (QUAD): the gradient is g = c + d x - K'y (formed from the scaled operands, before UNSCALE divides it), the primal
+// objective's sum acc[3] takes c_j x_j + 1/2 d_j x_j^2 and acc[1] takes -1/2 d_j x_j^2 besides l'max(lam, 0): the dual objective of the
+// quadratic problem is q'y + l'lam+ + u'lam- - 1/2 x'Dx, and the six sums keep their places (include/pdlp_hip.h).
+template <typename T, bool QUAD> struct KktDualPre { T cj, lo, hi, xj, d; };
+template <typename T> struct KktDualPre<T, true> { T cj, lo, hi, xj, d, qd; };
+template <typename T, bool UNSCALE, bool QUAD = false> struct KktDualEpi {
     static constexpr int NA = 4;
     const T* x; const T* c; const T* l; const T* u; const T* dcol; T* kty_out;     // kty_out: keeps K'y for the next primal half-step
+    [[no_unique_address]] ObjDiag<T, QUAD> diag{};
     __device__ void load() {}
-    struct Pre { T cj, lo, hi, xj, d; };
-    __device__ Pre pre(int j) const { return Pre{c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1}; }
+    typedef KktDualPre<T, QUAD> Pre;
+    __device__ Pre pre(int j) const
+    {
+        if constexpr (QUAD) return Pre{c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1, diag.p[j]};
+        else return Pre{c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1};
+    }
     __device__ void operator()(int j, T kty, double* acc) const { (*this)(j, kty, pre(j), acc); }
     __device__ void operator()(int j, T kty, const Pre& p, double* acc) const
     {
         if (kty_out) kty_out[j] = kty;
         T cj = p.cj, lo = p.lo, hi = p.hi, xj = p.xj;
         T g = cj - kty;
+        [[maybe_unused]] double hq = 0.0;
+        if constexpr (QUAD) { g = (cj + p.qd * xj) - kty; hq = quad_half(p.qd, xj); }
         if (UNSCALE) {            // K_u'(D_row y) = (K_s'y)/D_col, c_u = c_s/D_col, l_u = l_s D_col, x_u = D_col x
             const T d = p.d;
             g = g / d; cj = cj / d; lo = lo * d; hi = hi * d; xj = xj * d;
@@ -236,6 +278,7 @@ template <typename T, bool UNSCALE> struct KktDualEpi {
         acc[1] += (double)ld * (double)(lam > (T)0 ? lam : (T)0);
         acc[2] += (double)ud * (double)(lam < (T)0 ? lam : (T)0);
         acc[3] += (double)cj * (double)xj;
+        if constexpr (QUAD) { acc[1] -= hq; acc[3] += hq; }     // (own additions: with d = 0 the sums are the linear ones bit for bit)
     }
 };
 
@@ -291,17 +334,24 @@ template <typename T, bool UNSCALE, bool RANGED = false> struct KktPrimalEpi {
 // and leaves the reduced cost lam_j in buf[j] -- UNSCALE: of the un-preconditioned problem, lam_u = lam_s / D_col (pdhg.py:157-161).
 // The product is an operand of pre(), not the kernel's row sum (k_rowsum_epilogue runs with no groups): buf is read and written
 // through this one pointer.
-template <typename T, bool UNSCALE> struct ReportDualEpi {
+template <typename T, bool UNSCALE, bool QUAD = false> struct ReportDualEpi {
     static constexpr int NA = 4;
     T* buf; const T* x; const T* c; const T* l; const T* u; const T* dcol;
+    [[no_unique_address]] ObjDiag<T, QUAD> diag{};
     __device__ void load() {}
-    struct Pre { T kty; typename KktDualEpi<T, UNSCALE>::Pre kp; };
-    __device__ Pre pre(int j) const { return Pre{buf[j], {c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1}}; }
+    struct Pre { T kty; typename KktDualEpi<T, UNSCALE, QUAD>::Pre kp; };
+    __device__ Pre pre(int j) const
+    {
+        if constexpr (QUAD) return Pre{buf[j], {c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1, diag.p[j]}};
+        else return Pre{buf[j], {c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1}};
+    }
     __device__ void operator()(int j, T, double* acc) const { (*this)(j, (T)0, pre(j), acc); }
     __device__ void operator()(int j, T, const Pre& p, double* acc) const
     {
         T cj = p.kp.cj, lo = p.kp.lo, hi = p.kp.hi, xj = p.kp.xj;
         T g = cj - p.kty;
+        [[maybe_unused]] double hq = 0.0;
+        if constexpr (QUAD) { g = (cj + p.kp.qd * xj) - p.kty; hq = quad_half(p.kp.qd, xj); }
         if (UNSCALE) {
             const T d = p.kp.d;
             g = g / d; cj = cj / d; lo = lo * d; hi = hi * d; xj = xj * d;
@@ -319,6 +369,7 @@ template <typename T, bool UNSCALE> struct ReportDualEpi {
         acc[1] += (double)ld * (double)(lam > (T)0 ? lam : (T)0);
         acc[2] += (double)ud * (double)(lam < (T)0 ? lam : (T)0);
         acc[3] += (double)cj * (double)xj;
+        if constexpr (QUAD) { acc[1] -= hq; acc[3] += hq; }     // (own additions: with d = 0 the sums are the linear ones bit for bit)
     }
 };
 

@@ -14,9 +14,16 @@ template <typename T> int halpern_iterate_t(pdlp_handle h, int iters)
         const double t2 = (double)(h->since_reset + 2);
         const T a = (T)((double)(h->since_reset + 1) / t2), b = (T)(1.0 / t2);
         const int cur = h->ix_cur, nxt = h->ix_prev, cand = h->ix_avg;
-        HalpernPrimalEpi<T> ep{xloc<T>(h, cur), xloc<T>(h, nxt), (T*)h->xbar + h->p.col0, xloc<T>(h, cand), (const T*)h->x_last,
-                               (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, h->sc, a, b};
-        if ((rc = launch_csr<T>(h, true, h->yb[cur], ep, h->partA)) != PDLP_OK) return rc;
+        if (h->obj_diag) {         // diagonal quadratic objective (pdlp_set_objective_diag)
+            HalpernPrimalEpi<T, true> ep{xloc<T>(h, cur), xloc<T>(h, nxt), (T*)h->xbar + h->p.col0, xloc<T>(h, cand), (const T*)h->x_last,
+                                         (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, h->sc, a, b};
+            ep.diag.p = (const T*)h->obj_diag;
+            if ((rc = launch_mat<T, T>(h, true, h->yb[cur], ep, h->partA)) != PDLP_OK) return rc;
+        } else {
+            HalpernPrimalEpi<T> ep{xloc<T>(h, cur), xloc<T>(h, nxt), (T*)h->xbar + h->p.col0, xloc<T>(h, cand), (const T*)h->x_last,
+                                   (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, h->sc, a, b};
+            if ((rc = launch_csr<T>(h, true, h->yb[cur], ep, h->partA)) != PDLP_OK) return rc;
+        }
         if (h->q_upper) {          // two-sided rows (pdlp_set_row_upper)
             HalpernDualEpi<T, true> ed{yloc<T>(h, cur), yloc<T>(h, nxt), yloc<T>(h, cand), (const T*)h->y_last, (const T*)h->p.q, h->sc,
                                        h->ineq_end, a, b};

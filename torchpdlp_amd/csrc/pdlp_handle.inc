@@ -90,6 +90,7 @@ struct pdlp_solver {
     float *gdx = nullptr, *gdy = nullptr;   // full-length float32 difference vectors the float32 kernels gather from
     int64_t nl = 0, ml = 0;       // local variable / constraint counts
     int ineq_end = 0;             // local rows below this index are inequalities
+    const void* obj_diag = nullptr;  // diagonal quadratic objective (pdlp_set_objective_diag): c'x + 1/2 x'Dx, d of the variables; the caller's memory
     const void* q_upper = nullptr;   // two-sided rows (pdlp_set_row_upper): q <= K x <= q_upper on the inequality rows; the caller's memory
     Schedule sK, sKT;
     char* xb[3] = {};             // full-length primal buffers; roles via ix_*

@@ -384,6 +384,21 @@ int pdlp_set_row_upper(pdlp_handle h, const void* q_upper_local)
     return PDLP_OK;
 }
 
+int pdlp_set_objective_diag(pdlp_handle h, const void* d_local)
+{
+    if (!h) return PDLP_ERR_INVALID;
+    // forms without the quadratic term: mixed precision / delta mode, a shard of a problem, an exchange of any kind.  (This is also
+    // what keeps pdlp_set_delta(on) away from the term: it asks for a PDLP_MIXED handle, which can never have d set.)
+    if (d_local && (h->mixed || h->delta || h->nl != h->p.n || h->ml != h->p.m || h->comm || h->peer.on)) return PDLP_ERR_STATE;
+    if (h->sK.pending || h->sKT.pending) return PDLP_ERR_STATE;       // not in the middle of a split product
+    drop_graphs(h);               // captured launches hold the functors without (or with the old) d
+    h->obj_diag = d_local;
+    // what a KKT pass left behind belongs to the other objective: the candidates' products and the kept K'y
+    h->cand_valid[0] = h->cand_valid[1] = false;
+    h->kty_cur = -1; h->cur_kx_cached = false;
+    return PDLP_OK;
+}
+
 int pdlp_get_iterate(pdlp_handle h, int which, void* x_local, void* y_local)
 {
     if (!h) return PDLP_ERR_INVALID;
@@ -663,6 +678,7 @@ int pdlp_mark_restart_point(pdlp_handle h)
 int pdlp_infeas_reset(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
+    if (h->obj_diag) return PDLP_ERR_STATE;      // (no call of the detector with a quadratic objective: pdlp_set_objective_diag)
     HIP_TRY(hipMemsetAsync(h->lam_prev, 0, h->nl * h->es, h->stream));          // pdhg.py:39-40
     return PDLP_OK;
 }
@@ -670,20 +686,21 @@ int pdlp_infeas_reset(pdlp_handle h)
 int pdlp_infeas_begin(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->q_upper) return PDLP_ERR_STATE;       // (the detector's tests know one-sided rows only)
+    if (h->q_upper || h->obj_diag) return PDLP_ERR_STATE;       // (the detector's tests know one-sided rows and a linear objective only)
     return DISPATCH(h, infeas_begin_t, h);
 }
 
 int pdlp_infeas_local(pdlp_handle h, double tol)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->q_upper) return PDLP_ERR_STATE;
+    if (h->q_upper || h->obj_diag) return PDLP_ERR_STATE;
     return DISPATCH(h, infeas_local_t, h, tol);
 }
 
 int pdlp_infeas_finish(pdlp_handle h, double tol, int32_t* status, double diag[8])
 {
     if (!h || !status || !diag) return PDLP_ERR_INVALID;
+    if (h->obj_diag) return PDLP_ERR_STATE;
     double r[PDLP_NRED];
     const int rc = pdlp_read_red(h, r);
     if (rc != PDLP_OK) return rc;
@@ -694,21 +711,21 @@ int pdlp_infeas_finish(pdlp_handle h, double tol, int32_t* status, double diag[8
 int pdlp_mv_steps(pdlp_handle h, int nvp, int steps, double eta, double omega, double theta, void* X, void* Y, void* work)
 {
     if (!h || !X || !Y || !work || steps < 0 || (nvp != 8 && nvp != 16 && nvp != 32)) return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper) return PDLP_ERR_STATE;   // (q_upper: one-sided rows only)
+    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper || h->obj_diag) return PDLP_ERR_STATE;   // (one-sided rows, linear objective)
     return DISPATCH(h, mv_steps_t, h, nvp, steps, eta, omega, theta, X, Y, work);
 }
 
 int pdlp_mv_gap(pdlp_handle h, int nvp, const void* X, const void* Y, void* work, double* gaps)
 {
     if (!h || !X || !Y || !work || !gaps || (nvp != 8 && nvp != 16 && nvp != 32)) return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper) return PDLP_ERR_STATE;   // (q_upper: one-sided rows only)
+    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper || h->obj_diag) return PDLP_ERR_STATE;   // (one-sided rows, linear objective)
     return DISPATCH(h, mv_gap_t, h, nvp, X, Y, work, gaps);
 }
 
 int pdlp_mv_product(pdlp_handle h, int nvp, const void* X, void* Y)
 {
     if (!h || !X || !Y || (nvp != 8 && nvp != 16 && nvp != 32)) return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper) return PDLP_ERR_STATE;   // (q_upper: one-sided rows only)
+    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper || h->obj_diag) return PDLP_ERR_STATE;   // (one-sided rows, linear objective)
     return DISPATCH(h, mv_product_t, h, nvp, X, Y);
 }
 

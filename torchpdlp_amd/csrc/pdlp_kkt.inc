@@ -20,7 +20,27 @@ template <typename T, bool RANGED, class Epi> int launch_rows(pdlp_handle h, con
     else return launch_csr<T>(h, false, vin, e, partials);
 }
 
-template <typename T, bool UNSCALE, bool RANGED = false> int kkt_local_u(pdlp_handle h, int which)
+// the variable side's functor of a KKT pass, with d when the handle has a diagonal quadratic objective (QUAD), and its product with
+// K': such a handle is never in mixed precision either
+template <typename T, bool UNSCALE, bool QUAD> KktDualEpi<T, UNSCALE, QUAD> kkt_dual_epi(pdlp_handle h, int ix, const T* dcol, T* kty_out)
+{
+    KktDualEpi<T, UNSCALE, QUAD> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, kty_out};
+    if constexpr (QUAD) ed.diag.p = (const T*)h->obj_diag;
+    return ed;
+}
+template <typename T, bool QUAD, class Epi> int launch_cols(pdlp_handle h, const void* vin, Epi e, double* partials)
+{
+    if constexpr (QUAD) return launch_mat<T, T>(h, true, vin, e, partials);
+    else return launch_csr<T>(h, true, vin, e, partials);
+}
+// f(RANGED, QUAD) with the handle's two problem-class switches as types
+template <class F> int with_ranged_quad(pdlp_handle h, F f)
+{
+    if (h->obj_diag) return h->q_upper ? f(std::true_type{}, std::true_type{}) : f(std::false_type{}, std::true_type{});
+    return h->q_upper ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{});
+}
+
+template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int kkt_local_u(pdlp_handle h, int which)
 {
     const int ix = iterate_index(h, which);
     const T* dcol = UNSCALE ? (const T*)h->p.d_col : nullptr;
@@ -28,7 +48,7 @@ template <typename T, bool UNSCALE, bool RANGED = false> int kkt_local_u(pdlp_ha
     int rc, gridA = grid_of(h->sKT, h->nl), gridB = grid_of(h->sK, h->ml);
     if (which == PDLP_AVG && h->avg_products) {
         // K'y_avg (ktyb[1]) and K x_avg (kxb[2]) were formed from the running sums by pdlp_compute_average: two vector passes
-        KktDualEpi<T, UNSCALE> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, nullptr};
+        const auto ed = kkt_dual_epi<T, UNSCALE, QUAD>(h, ix, dcol, nullptr);
         if ((rc = epilogue_pass<T>(h, h->nl, h->ktyb[1], ed, h->partA)) != PDLP_OK) return rc;
         const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, nullptr);
         if ((rc = epilogue_pass<T>(h, h->ml, h->kxb[2], ep, h->partB)) != PDLP_OK) return rc;
@@ -40,8 +60,8 @@ template <typename T, bool UNSCALE, bool RANGED = false> int kkt_local_u(pdlp_ha
         // sums): keep it.  (A pass at the current iterate after a restart to the average supersedes that restart's copy.)
         T* kty_out = which == PDLP_CUR ? (T*)h->ktyb[0] : (which == PDLP_AVG ? (T*)h->ktyb[1] : nullptr);
         if (which == PDLP_CUR || (which == PDLP_AVG && h->kty_cur == 1)) h->kty_cur = -1;     // (the copy about to be overwritten)
-        KktDualEpi<T, UNSCALE> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, kty_out};
-        if ((rc = launch_csr<T>(h, true, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
+        const auto ed = kkt_dual_epi<T, UNSCALE, QUAD>(h, ix, dcol, kty_out);
+        if ((rc = launch_cols<T, QUAD>(h, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
         if (which == PDLP_CUR && h->kx_valid && !h->no_running) {
             // K x of the current iterate is carried along by the dual half-steps (kxb[0]): no product
             const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, nullptr);
@@ -61,6 +81,11 @@ template <typename T, bool UNSCALE, bool RANGED = false> int kkt_local_u(pdlp_ha
 
 template <typename T> int kkt_local_t(pdlp_handle h, int which, int unscaled)
 {
+    if (h->obj_diag)       // (a handle may have two-sided rows and the quadratic term)
+        return with_ranged_quad(h, [&](auto R, auto Q) {
+            return unscaled ? kkt_local_u<T, true, decltype(R)::value, decltype(Q)::value>(h, which)
+                            : kkt_local_u<T, false, decltype(R)::value, decltype(Q)::value>(h, which);
+        });
     if (h->q_upper) return unscaled ? kkt_local_u<T, true, true>(h, which) : kkt_local_u<T, false, true>(h, which);
     return unscaled ? kkt_local_u<T, true>(h, which) : kkt_local_u<T, false>(h, which);
 }
@@ -71,7 +96,7 @@ template <typename T> int kkt_local_t(pdlp_handle h, int which, int unscaled)
 // then forms the sums and turns K'y into lam in place.  A vector the caller does not want (null) costs nothing extra: that side
 // runs the KKT pass's own fused epilogue without its stores.  Nothing of the solver's state is read except the iterate and
 // nothing is written except scratch (partial sums, row sums, PDLP_BUF_RED).
-template <typename T, bool UNSCALE, bool RANGED = false> int report_local_u(pdlp_handle h, int which, void* rc_local, void* act_local)
+template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int report_local_u(pdlp_handle h, int which, void* rc_local, void* act_local)
 {
     const int ix = iterate_index(h, which);
     const T* dcol = UNSCALE ? (const T*)h->p.d_col : nullptr;
@@ -80,12 +105,13 @@ template <typename T, bool UNSCALE, bool RANGED = false> int report_local_u(pdlp
     if (rc_local) {
         StoreEpi<T> st{(T*)rc_local};
         if ((rc = launch_csr<T>(h, true, h->yb[ix], st, h->partA)) != PDLP_OK) return rc;
-        ReportDualEpi<T, UNSCALE> ed{(T*)rc_local, xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol};
+        ReportDualEpi<T, UNSCALE, QUAD> ed{(T*)rc_local, xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol};
+        if constexpr (QUAD) ed.diag.p = (const T*)h->obj_diag;
         if ((rc = epilogue_pass<T>(h, h->nl, nullptr, ed, h->partA)) != PDLP_OK) return rc;
         gridA = rows_grid(h->nl);
     } else {
-        KktDualEpi<T, UNSCALE> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, nullptr};
-        if ((rc = launch_csr<T>(h, true, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
+        const auto ed = kkt_dual_epi<T, UNSCALE, QUAD>(h, ix, dcol, nullptr);
+        if ((rc = launch_cols<T, QUAD>(h, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
     }
     if (act_local) {
         StoreEpi<T> st{(T*)act_local};
@@ -103,6 +129,11 @@ template <typename T, bool UNSCALE, bool RANGED = false> int report_local_u(pdlp
 
 template <typename T> int report_local_t(pdlp_handle h, int which, int unscaled, void* rc_local, void* act_local)
 {
+    if (h->obj_diag)
+        return with_ranged_quad(h, [&](auto R, auto Q) {
+            return unscaled ? report_local_u<T, true, decltype(R)::value, decltype(Q)::value>(h, which, rc_local, act_local)
+                            : report_local_u<T, false, decltype(R)::value, decltype(Q)::value>(h, which, rc_local, act_local);
+        });
     if (h->q_upper)
         return unscaled ? report_local_u<T, true, true>(h, which, rc_local, act_local) : report_local_u<T, false, true>(h, which, rc_local, act_local);
     return unscaled ? report_local_u<T, true>(h, which, rc_local, act_local) : report_local_u<T, false>(h, which, rc_local, act_local);

@@ -215,18 +215,23 @@ template <class F> int with_adapt_peer(pdlp_handle h, int adaptive, F f)
     return adaptive ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{});
 }
 
-template <typename T, bool ADAPT, bool PEER> int primal_half_e(pdlp_handle h, int src, T* ksum, const PieceCtl& pc)
+// QUAD: the handle has a diagonal quadratic objective (pdlp_set_objective_diag: float32 / float64, one GPU, no exchange -- so never
+// PEER, and the matrix has the working type)
+template <typename T, bool ADAPT, bool PEER, bool QUAD = false> int primal_half_e(pdlp_handle h, int src, T* ksum, const PieceCtl& pc)
 {
-    PrimalEpi<T, ADAPT, PEER> e{xloc<T>(h, h->ix_cur), xloc<T>(h, h->ix_prev), (T*)h->xbar + h->p.col0, (const T*)h->p.c,
-                                (const T*)h->p.l, (const T*)h->p.u, (T*)h->x_sum, h->sc, ksum};
+    PrimalEpi<T, ADAPT, PEER, QUAD> e{xloc<T>(h, h->ix_cur), xloc<T>(h, h->ix_prev), (T*)h->xbar + h->p.col0, (const T*)h->p.c,
+                                      (const T*)h->p.l, (const T*)h->p.u, (T*)h->x_sum, h->sc, ksum};
     peer_targets(h, e.peer, 0);
+    if constexpr (QUAD) e.diag.p = (const T*)h->obj_diag;
     if (src >= 0) {     // the primal update from a K'y that a KKT pass at this very iterate left behind: no product, one vector kernel
         if (ADAPT) h->last_gridA = rows_grid(h->nl);
         return epilogue_pass<T>(h, h->nl, h->ktyb[src], e, h->partA);
     }
     if (ADAPT) h->last_gridA = grid_of(h->sKT, h->nl);
     h->use_split = true;
-    const int rc = launch_csr<T>(h, true, h->yb[h->ix_cur], e, h->partA);
+    int rc;
+    if constexpr (QUAD) rc = launch_mat<T, T>(h, true, h->yb[h->ix_cur], e, h->partA);
+    else rc = launch_csr<T>(h, true, h->yb[h->ix_cur], e, h->partA);
     h->use_split = false;
     if (pc.finish) h->sKT.pending = false;
     return rc;
@@ -243,6 +248,7 @@ template <typename T> int primal_half_t(pdlp_handle h, int adaptive)
     T* ksum = (h->since_reset > 0 && !h->kty_tail_done && !h->sums_broken && !h->no_running && !h->graph_ok) ? (T*)h->kty_sum : nullptr;
     const PieceCtl pc = piece_ctl(h, h->sKT, src < 0);
     if (pc.skip) return PDLP_OK;                             // (all of this half-step went out with piece 0)
+    if (h->obj_diag) return adaptive ? primal_half_e<T, true, false, true>(h, src, ksum, pc) : primal_half_e<T, false, false, true>(h, src, ksum, pc);
     // (inside the direct exchange the epilogue also stores xbar into the peers: its own instantiations)
     return with_adapt_peer(h, adaptive, [&](auto A, auto P) { return primal_half_e<T, decltype(A)::value, decltype(P)::value>(h, src, ksum, pc); });
 }

@@ -86,8 +86,9 @@ class PdlpEngine(KernelChoice, Exchange):
 
     def __init__(self, m: int, n: int, m_ineq: int, K_rows, KT_rows, c, q, l, u, rows: Tuple[int, int] = None,
                  cols: Tuple[int, int] = None, d_col=None, d_row=None, comm: Optional[Comm] = None, vec_dtype=None,
-                 delta: Optional[bool] = None, exact=None, tiles: bool = True, q_upper=None):
+                 delta: Optional[bool] = None, exact=None, tiles: bool = True, q_upper=None, quad_diag=None):
         """``q_upper`` (length row1-row0, or None): two-sided rows ``q <= K x <= q_upper`` on the inequality rows (``set_row_upper``).
+        ``quad_diag`` (length n, or None): the objective ``c'x + 1/2 sum_j d_j x_j^2`` (``set_objective_diag``).
         ``vec_dtype=torch.float64`` over float32 matrix values selects the mixed precision (``PDLP_MIXED``): float64 vectors,
         products and sums on a float32 matrix (12 -> 8 bytes per non-zero); ``delta`` (default: ``PDLP_DELTA`` in the environment,
         else on) then runs the iterations on the float32 kernels over float32 difference vectors added to float64 anchor
@@ -146,6 +147,9 @@ class PdlpEngine(KernelChoice, Exchange):
         self.q_upper = None
         if q_upper is not None:
             self.set_row_upper(q_upper)
+        self.quad_diag = None
+        if quad_diag is not None:
+            self.set_objective_diag(quad_diag)
         # test / tool knobs of the handle (knobs_from_env)
         kn = self.knobs = knobs_from_env()
         if not kn.running_kkt:
@@ -204,6 +208,22 @@ class PdlpEngine(KernelChoice, Exchange):
         N.check(self.lib.pdlp_set_row_upper(self.h, qu.data_ptr()), "pdlp_set_row_upper")
         self.q_upper = qu                      # (kept alive: the library points into it)
 
+    def set_objective_diag(self, d):
+        """Diagonal quadratic objective (``pdlp_set_objective_diag``, include/pdlp_hip.h): ``min c'x + 1/2 sum_j d_j x_j^2`` with
+        ``d >= 0`` of length n, in the engine's scaling when it has one (``Scaling.scale(..., quad_diag=)``: ``d D_col^2``).  ``None``
+        switches the term off.  Validated here (``quad.check_quad_diag``: ``ValueError``); float32 / float64 engines on one GPU --
+        the library refuses the others (``PdlpError``).  While set, ``kkt`` / ``report`` give the quadratic problem's objectives
+        (``p = c'x + 1/2 x'Dx``, ``d_adj`` with ``-1/2 x'Dx``) and reduced costs ``project_lambda_box(c + Dx - K'y)``, and
+        ``detect_infeasibility``, the population calls and the batch calls raise ``PdlpError``."""
+        from .quad import check_quad_diag
+        if d is None:
+            N.check(self.lib.pdlp_set_objective_diag(self.h, None), "pdlp_set_objective_diag")
+            self.quad_diag = None
+            return
+        d = as_vec(check_quad_diag(d, self.nl), self.nl, self.device, self.dtype)
+        N.check(self.lib.pdlp_set_objective_diag(self.h, d.data_ptr()), "pdlp_set_objective_diag")
+        self.quad_diag = d                     # (kept alive: the library points into it)
+
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
         th = getattr(self, "_comm_init_thread", None)
@@ -221,11 +241,11 @@ class PdlpEngine(KernelChoice, Exchange):
 
     @classmethod
     def from_full(cls, K: CsrPair, c, q, l, u, m_ineq: int, d_col=None, d_row=None, vec_dtype=None, delta=None,
-                  exact: Optional[CsrPair] = None, q_upper=None) -> "PdlpEngine":
+                  exact: Optional[CsrPair] = None, q_upper=None, quad_diag=None) -> "PdlpEngine":
         """single-GPU engine over a whole problem (``exact``: the float64 matrix of which ``K`` is the float32 rounding)"""
         ex = None if exact is None else ((exact.rowptr, exact.colidx, exact.val), (exact.t_rowptr, exact.t_colidx, exact.t_val))
         return cls(K.m, K.n, m_ineq, (K.rowptr, K.colidx, K.val), (K.t_rowptr, K.t_colidx, K.t_val), c, q, l, u,
-                   d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, delta=delta, exact=ex, q_upper=q_upper)
+                   d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, delta=delta, exact=ex, q_upper=q_upper, quad_diag=quad_diag)
 
     # ---- buffers ------------------------------------------------------------------------------------
     def buffer(self, which: int) -> torch.Tensor:

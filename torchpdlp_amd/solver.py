@@ -17,6 +17,7 @@ from . import _native as N
 from .engine import Comm, PdlpEngine
 from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, kkt_error, np_type, previous_kkt_matters,   # noqa: F401
                     primal_weight, restart_decision, start_eta, start_omega, terminated)
+from .quad import REFUSED as QUAD_REFUSED, check_quad_diag
 from .ranged import REFUSED as RANGED_REFUSED, check_row_upper, norm_vector as ranged_norm_vector
 from .sparse import CsrPair, as_vec, resolve_device     # noqa: F401  (resolve_device: api.py and callers take it from here)
 
@@ -94,6 +95,10 @@ class PdhgDriver:
         q_upper = getattr(eng, "q_upper", None)
         if q_upper is not None and (adaptive_retry or infeasibility_detect or getattr(eng, "mixed", False) or eng.comm is not None):
             raise ValueError(RANGED_REFUSED)
+        # a diagonal quadratic objective (the engine's quad_diag) changes nothing here: the engine's sums carry the term
+        if getattr(eng, "quad_diag", None) is not None and (adaptive_retry or infeasibility_detect or getattr(eng, "mixed", False)
+                                                             or eng.comm is not None):
+            raise ValueError(QUAD_REFUSED)
         self.q_norm = self.t(_global_norm(ranged_norm_vector(eng.q, q_upper, getattr(eng, "m_ineq", 0)), eng.comm))
         self.c_norm = self.t(_global_norm(eng.c, eng.comm))
         self.n = self.k = self.j = self.tt = 0
@@ -377,7 +382,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
                    precondition=False, primal_update=False, adaptive=False, data_precond=None, infeasibility_detect=False,
                    infeas_tol=1e-4, time_limit=3600, time_used=0, x_init=None, y_init=None, *, b0=None, sigma=None,
                    seed=None, trace=None, comm=None, precision=None, adaptive_retry=False, report=None,
-                   halpern=False, q_upper=None):
+                   halpern=False, q_upper=None, quad_diag=None):
     """Drop-in for the reference's ``pdlp_algorithm`` (primal_dual_hybrid_gradient.py:7) on one MI355X.
 
     ``K`` may be a dense / COO torch tensor (as the reference takes), a scipy sparse matrix or a
@@ -417,6 +422,14 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     ``y_init`` in float32 and float64; ``ValueError`` (before any device work) for a malformed ``q_upper`` and together with
     ``precision="mixed"``, ``comm``, ``infeasibility_detect`` or ``adaptive_retry``.
 
+    ``quad_diag`` (length n, default None; the reference has no counterpart): the objective becomes ``c'x + 1/2 sum_j d_j x_j^2`` with
+    ``d = quad_diag >= 0``: the primal half-step divides by ``1 + tau d_j`` before the clamp, the gradient of the KKT
+    pass is ``c + D x - K'y``, the returned objective is the quadratic one and the report's dual objective carries ``-1/2 x'Dx``;
+    with ``precondition`` pass the scaled diagonal (``Scaling.scale(..., quad_diag=)``: ``d D_col^2``).  Works with ``precondition``,
+    ``primal_update``, ``adaptive``, ``halpern``, ``q_upper`` and ``x_init`` / ``y_init`` in float32 and float64; ``ValueError`` (before
+    any device work) for a malformed vector and together with ``precision="mixed"``, ``comm``, ``infeasibility_detect`` or
+    ``adaptive_retry``.
+
     ``comm`` (a ``Comm``, or ``True`` for the default ``torch.distributed`` group): every rank calls with the SAME
     full problem and the same ``seed``/``b0``; each keeps its row blocks of K and K', the iterations exchange
     ``xbar`` and ``y`` over RCCL, and every rank returns the full solution.
@@ -428,6 +441,10 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
         if adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False):
             raise ValueError(RANGED_REFUSED)
         q_upper = check_row_upper(q, q_upper, m_ineq)
+    if quad_diag is not None:
+        if adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False):
+            raise ValueError(QUAD_REFUSED)
+        quad_diag = check_quad_diag(quad_diag, torch.as_tensor(c).numel())
     device = resolve_device(device)
     Kp = CsrPair.from_any(K, device=device)
     dtype = Kp.dtype
@@ -455,7 +472,8 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
             b0 = eng.part.pad_cols(as_vec(b0, Kp.n, device, torch.float32))
         verbose = verbose and comm.rank == 0
     else:
-        eng = PdlpEngine.from_full(Kp, c, q, l, u, m_ineq, d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, exact=exact_K, q_upper=q_upper)
+        eng = PdlpEngine.from_full(Kp, c, q, l, u, m_ineq, d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, exact=exact_K, q_upper=q_upper,
+                                   **({} if quad_diag is None else dict(quad_diag=quad_diag)))
     x, obj, k, n, j, status, total = run_pdlp(
         eng, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period, precondition=precondition,
         primal_update=primal_update, adaptive=adaptive, time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init,
