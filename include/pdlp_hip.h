@@ -246,8 +246,9 @@ int pdlp_fixed_advance(pdlp_handle h, int iters);
  * as two fused products, like the PDHG step: x', xbar and y' are formed with the expressions of pdlp_primal_half / pdlp_dual_half at
  * theta = 1, so (x', y') equals one fixed PDHG step from z bit for bit.  Afterwards PDLP_CUR is z+ = (x+, y+), PDLP_AVG holds the
  * CANDIDATE (x', y') of the last iteration -- inside the bounds and with y >= 0 on the inequality rows, which z+ need not be -- and
- * PDLP_PREV is not defined.  The candidate is what a restart check evaluates and what a restart adopts, with the calls that serve
- * the average in the PDHG loop: pdlp_kkt_local(PDLP_AVG), pdlp_restart(PDLP_AVG) (t = 0 again), pdlp_restart_distance_local,
+ * PDLP_PREV is z, the iterate BEFORE the last iteration (the point the candidate is one step from: PDLP_AVG = T(PDLP_PREV), which is
+ * what pdlp_halpern_fixed_point reads).  The candidate is what a restart check evaluates and what a restart adopts, with the calls
+ * that serve the average in the PDHG loop: pdlp_kkt_local(PDLP_AVG), pdlp_restart(PDLP_AVG) (t = 0 again), pdlp_restart_distance_local,
  * pdlp_mark_restart_point (the adopted point is the new anchor), pdlp_get_iterate(PDLP_AVG).
  * Everything carried from before is dropped: the K x cache, a K'y kept by a KKT pass, and the running sums (until the next
  * restart), so pdlp_kkt_local(PDLP_AVG) afterwards multiplies.  The K'y that pass keeps is NOT reused by the first Halpern iteration
@@ -256,6 +257,19 @@ int pdlp_fixed_advance(pdlp_handle h, int iters);
  * or a peer exchange, PDLP_OPT_GRAPH switched on.  After Halpern iterations and before the next pdlp_set_iterate,
  * pdlp_flush_average and pdlp_compute_average return PDLP_ERR_STATE (they would overwrite the candidate). */
 int pdlp_halpern_iterate(pdlp_handle h, int iters);
+/* The fixed-point residual of the last Halpern iteration, the quantity the restart rule of the rHPDHG papers looks at: with
+ * z = (x, y) = PDLP_PREV, T(z) = (x', y') = PDLP_AVG, dx = x - x', dy = y - y',
+ *     PDLP_BUF_RED[0..2] = { ||dx||^2, dx'(K'dy), ||dy||^2 }
+ * in double, in a fixed order (no atomics: the same bits on every call); the caller forms
+ *     ||z - T(z)||_P^2 = (omega/eta) ||dx||^2 - 2 dx'(K'dy) + ||dy||^2 / (eta omega)
+ * on the host (pdlp_read_red).  One vector pass (dy, stored into PDLP_BUF_DY, with its sum) and ONE product, K'dy, whose epilogue forms
+ * the other two sums -- against the two products of a KKT pass.  Writes PDLP_BUF_DY, PDLP_BUF_RED and the partial-sum and product
+ * scratch; no iterate, no scalar, no carried product and no flag of the handle changes, so every later result is bit-identical
+ * to a run without the call.  q_upper and the quadratic term do not enter (the pass reads vectors only).
+ * PDLP_ERR_STATE: on the handles pdlp_halpern_iterate refuses; unless pdlp_halpern_iterate (iters >= 1) has run since the last
+ * pdlp_set_iterate / pdlp_restart; and once a call has re-assigned the iterate buffers since then (pdlp_iterate, the half-step
+ * calls, pdlp_adaptive_retry).  KKT, report and distance passes in between are fine. */
+int pdlp_halpern_fixed_point(pdlp_handle h);
 
 /* ---- two-sided constraint rows -------------------------------------------------------------------------------------------
  * q_i <= (K x)_i <= q_upper_i on the inequality rows (i < m_ineq) without entering the row twice (no counterpart in the

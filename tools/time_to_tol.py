@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Time-to-tolerance on the bench LP (BASELINE.json metric, second half): full restarted solve, prints the
 restart log every check.  python tools/time_to_tol.py [n] [nnz_per_row] [tol] [ruiz 0/1] [max_kkt] [f32|f64|mixed] [--pock-chambolle]
-[--halpern | --fixed]
+[--halpern [--halpern-restart kkt|fixed_point] | --fixed]
 (--pock-chambolle, with ruiz 1: the Pock-Chambolle pass after the sweeps, solve_lp's pock_chambolle=True)
 (--halpern: the reflected Halpern iteration, solve_lp's halpern=True -- fixed step, f32 / f64; --fixed: averaged PDHG with the fixed
-step, its like-for-like comparison; neither: the adaptive step)
+step, its like-for-like comparison; neither: the adaptive step; --halpern-restart fixed_point: the Halpern mode's restart checks look at
+the fixed-point residual instead of the candidate's KKT error, solve_lp's halpern_restart)
 (mixed: the generator's matrix entries are float32 numbers, so holding K in float32 under float64 vectors is the same LP
 as the f64 run; PDLP_DELTA=0 switches its delta mode off)"""
 import os, sys, time
@@ -15,6 +16,13 @@ from torchpdlp_amd.solver import run_pdlp
 
 pock = "--pock-chambolle" in sys.argv
 halpern, fixed = "--halpern" in sys.argv, "--fixed" in sys.argv
+halpern_restart = "kkt"
+if "--halpern-restart" in sys.argv:
+    at = sys.argv.index("--halpern-restart")
+    if at + 1 >= len(sys.argv) or not halpern:
+        sys.exit("--halpern-restart kkt|fixed_point goes with --halpern")
+    halpern_restart = sys.argv[at + 1]
+    del sys.argv[at:at + 2]
 sys.argv = [a for a in sys.argv if a not in ("--pock-chambolle", "--halpern", "--fixed")]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 100
@@ -63,9 +71,9 @@ print(f"setup {time.time()-t0:.1f}s (ruiz{' + Pock-Chambolle' if pock else ''} {
 trace = dict(kkt=[], omega=[], restarts=[])
 x, obj, it, nr, j, status, secs = run_pdlp(eng, max_kkt=max_kkt, tol=tol, verbose=True, precondition=ruiz, primal_update=True,
                                            adaptive=not (halpern or fixed), time_limit=time_limit, seed=0, power_iters=100, trace=trace,
-                                           halpern=halpern)
+                                           halpern=halpern, halpern_restart=halpern_restart)
 print(f"RESULT n={n} k={k} tol={tol} ruiz={ruiz} pock_chambolle={pock} precision={prec} "
-      f"method={'halpern' if halpern else 'fixed' if fixed else 'adaptive'}: status={status} obj={obj:.6f} iterations={it} restarts={nr} kkt_passes={j} "
+      f"method={('halpern' if halpern_restart == 'kkt' else 'halpern_' + halpern_restart) if halpern else 'fixed' if fixed else 'adaptive'}: status={status} obj={obj:.6f} iterations={it} restarts={nr} kkt_passes={j} "
       f"solve_time={secs:.2f}s  ({it/secs:.1f} it/s incl. power iteration and checks)", flush=True)
 
 # ---- independent float64 check of the exit point (at 10M the only evaluator of the 1e-8 claim was the library's own

@@ -41,6 +41,9 @@ def parse_args(argv=None):
     p.add_argument("--halpern", action="store_true",
                    help="not in the reference's CLI: the restarted, reflected Halpern iteration instead of averaged PDHG (fixed step; "
                         "not with --adaptive_stepsize, --infeasibility_detect, --dtype mixed or several ranks)")
+    p.add_argument("--halpern_restart", choices=("kkt", "fixed_point"), default="kkt",
+                   help="with --halpern: what its restart checks look at -- the KKT error of the candidate (default) or the fixed-point "
+                        "residual ||z - T(z)|| of the Halpern iterate (the criterion of the rHPDHG papers; one product per check)")
     p.add_argument("--ranged_rows", action="store_true",
                    help="not in the reference's CLI: a RANGES row stays one two-sided row q <= a'x <= q_upper instead of two >= rows "
                         "(one GPU, fp32 / fp64; not with --infeasibility_detect, --fishnet or --adaptive_retry)")
@@ -151,7 +154,8 @@ def main(argv=None) -> int:
                          adaptive_stepsize=args.adaptive_stepsize, adaptive_retry=args.adaptive_retry, max_kkt=args.max_kkt, time_limit=args.time_limit,
                          verbose=args.verbose, dtype=dtype, seed=args.seed, fishnet=args.fishnet, comm=comm,
                          infeasibility_detect=args.infeasibility_detect, precision="mixed" if args.dtype == "mixed" else None,
-                         direct_exchange=args.direct_exchange, report=args.solution_dir is not None, halpern=args.halpern, q_upper=q_upper)
+                         direct_exchange=args.direct_exchange, report=args.solution_dir is not None, halpern=args.halpern, q_upper=q_upper,
+                         halpern_restart=args.halpern_restart)
             print(f"Solver uses {r.time:.4f} seconds.\nStatus: {r.status}")
             if args.solution_dir is not None and rank == 0:
                 print(f"Solution saved to {write_solution(args.solution_dir, name, r)}")

@@ -98,6 +98,7 @@ SIGNATURES = {
     "pdlp_adaptive_update": (_I, [_H]),
     "pdlp_iterate": (_I, [_H, _I, _I]),
     "pdlp_halpern_iterate": (_I, [_H, _I]),
+    "pdlp_halpern_fixed_point": (_I, [_H]),
     "pdlp_set_row_upper": (_I, [_H, _P]),
     "pdlp_set_objective_diag": (_I, [_H, _P]),
     "pdlp_set_exchange_chunks": (_I, [_H, _I]),

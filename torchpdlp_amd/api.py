@@ -69,7 +69,7 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
              fishnet: bool = False, comm=None, infeasibility_detect: bool = False, infeas_tol: float = 1e-4,
              precision: Optional[str] = None, adaptive_retry: bool = False, direct_exchange: bool = False,
              report: bool = True, pock_chambolle: bool = False, halpern: bool = False, q_upper=None,
-             ranged_rows: bool = False, quad_diag=None) -> LPResult:
+             ranged_rows: bool = False, quad_diag=None, halpern_restart: str = "kkt") -> LPResult:
     """Solve ``min c'x, K[:m_ineq]x >= q[:m_ineq], K[m_ineq:]x = q[m_ineq:], l <= x <= u`` on the current HIP device.
 
     ``problem`` is an MPS path or ``(c, K, q, m_ineq, l, u)`` with ``K`` dense / COO / scipy-sparse / ``CsrPair``.
@@ -93,7 +93,10 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     ``halpern`` (not in the reference): the restarted, reflected Halpern iteration instead of averaged PDHG, with the fixed step
     (``pdlp_algorithm``).  Works with ``precondition``, ``pock_chambolle``, ``primal_weight_update``,
     ``x_init`` / ``y_init`` and ``fishnet``; ``ValueError`` with ``adaptive_stepsize``, ``adaptive_retry``, ``infeasibility_detect``,
-    ``precision="mixed"`` and for sharded solves (``comm``).
+    ``precision="mixed"`` and for sharded solves (``comm``).  ``halpern_restart="fixed_point"`` (default "kkt"; needs ``halpern``):
+    its restart checks look at the fixed-point residual ``||z - T(z)||_P`` of the Halpern iterate, the criterion of the rHPDHG papers,
+    instead of the candidate's KKT error -- one product per check and no KKT pass; ``ValueError`` (before any
+    device work) for another value or without ``halpern``.
     ``q_upper`` (length m; not in the reference): two-sided rows, ``q_i <= (K x)_i <= q_upper_i`` on the inequality rows, each
     entered ONCE instead of as two ``>=`` rows.  ``+inf`` is an ordinary row, ``q_upper_i == q_i`` behaves as
     an equality row; on the equality rows the entry must be ``+inf`` or ``q_i`` and is ignored.  In the report ``y_i > 0`` says the
@@ -114,6 +117,8 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     about it is checked first.  MPS ``QUADOBJ`` / ``QMATRIX`` sections are not read.
     """
     _check_pock_chambolle(pock_chambolle, precondition)
+    from .solver import check_halpern_restart
+    check_halpern_restart(halpern_restart, halpern)
     from_file = isinstance(problem, (str, os.PathLike))
     if ranged_rows and (not from_file or q_upper is not None):
         raise ValueError("ranged_rows=True reads the RANGES rows of an MPS path; arrays carry q_upper themselves")
@@ -144,6 +149,8 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
                infeas_tol=infeas_tol, adaptive_retry=adaptive_retry)
     if halpern:
         run["halpern"] = True
+    if halpern_restart != "kkt":
+        run["halpern_restart"] = halpern_restart
     if comm is not None and not fishnet:
         from .engine import Comm
         cm = Comm() if comm is True else comm

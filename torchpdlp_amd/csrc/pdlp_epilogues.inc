@@ -237,6 +237,24 @@ template <typename T, bool RANGED = false> struct HalpernDualEpi {
     }
 };
 
+// Fixed-point residual of the Halpern iteration (pdlp_halpern_fixed_point), over the rows of K' with ktdy = (K'dy)_j, dy = y - y' the
+// gathered vector: dx = x_prev - x_cand, acc[0] = sum dx^2, acc[1] = sum (K'dy)_j dx_j.  Two operand loads, no store.
+template <typename T> struct FixedPointPre { T xp, xc; };
+template <typename T> struct FixedPointEpi {
+    static constexpr int NA = 2;
+    const T* x_prev; const T* x_cand;
+    typedef FixedPointPre<T> Pre;
+    __device__ void load() {}
+    __device__ Pre pre(int j) const { return Pre{x_prev[j], x_cand[j]}; }
+    __device__ void operator()(int j, T ktdy, double* acc) const { (*this)(j, ktdy, pre(j), acc); }
+    __device__ void operator()(int, T ktdy, const Pre& p, double* acc) const
+    {
+        const T dx = p.xp - p.xc;
+        acc[0] += (double)dx * (double)dx;
+        acc[1] += (double)ktdy * (double)dx;
+    }
+};
+
 // KKT, dual side (helpers.py:75-84,94 with project_lambda_box helpers.py:21-37 and pdhg.py:11-17)
 // Quadratic term (QUAD): the gradient is g = c + d x - K'y (formed from the scaled operands, before UNSCALE divides it), the primal
 // objective's sum acc[3] takes c_j x_j + 1/2 d_j x_j^2 and acc[1] takes -1/2 d_j x_j^2 besides l'max(lam, 0): the dual objective of the

@@ -1,7 +1,9 @@
 // pdlp_halpern.inc -- the restarted, reflected Halpern iteration (pdlp_halpern_iterate, include/pdlp_hip.h): two fused products
 // per iteration like the PDHG step, with HalpernPrimalEpi / HalpernDualEpi as their epilogues.  The iterate z lives in the PDLP_CUR
 // buffers, the candidate T(z) -- one fixed PDHG step from z -- in the PDLP_AVG buffers, the anchor is the restart point (x_last,
-// y_last) and t is the handle's count of iterations since the last restart.  The reference has no counterpart.
+// y_last) and t is the handle's count of iterations since the last restart.  The old z stays behind in the PDLP_PREV buffers, so the
+// fixed-point residual z - T(z) of the last iteration (pdlp_halpern_fixed_point) is one vector pass and one product.  The reference
+// has no counterpart.
 // Part of pdlp_hip.hip (included at file scope; not a translation unit of its own).  Needs: pdlp_products.inc and what is before it.
 // ------------------------------------------------------------------------------------------------
 namespace {
@@ -41,6 +43,29 @@ template <typename T> int halpern_iterate_t(pdlp_handle h, int iters)
     return PDLP_OK;
 }
 
+// The fixed-point residual of the last iteration: z = PDLP_PREV, T(z) = PDLP_AVG.  One vector pass (dy into the detector's full-length
+// buffer, which this mode never uses otherwise, with ||dy||^2), one product K'dy with FixedPointEpi, two finishes.
+template <typename T> int halpern_fixed_point_t(pdlp_handle h)
+{
+    const int prev = h->ix_prev, cand = h->ix_avg;
+    const int gb = grid_for(h->ml);
+    hipLaunchKernelGGL(k_sub_sq<T>, dim3(gb), dim3(BLOCK), 0, h->stream, h->ml, (T*)h->dyf + h->p.row0, (const T*)yloc<T>(h, prev),
+                       (const T*)yloc<T>(h, cand), h->partB);
+    FixedPointEpi<T> ep{xloc<T>(h, prev), xloc<T>(h, cand)};
+    int rc;
+    if ((rc = launch_csr<T>(h, true, h->dyf, ep, h->partA)) != PDLP_OK) return rc;
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partA, grid_of(h->sKT, h->nl), 2, h->red, 0);
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partB, gb, 1, h->red, 2);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+// the forms the Halpern mode does not have: mixed precision / delta mode, a shard of a problem, an exchange of any kind, graph replay
+inline bool halpern_refused(pdlp_handle h)
+{
+    return h->mixed || h->delta || h->nl != h->p.n || h->ml != h->p.m || h->comm || h->peer.on || h->graph_ok;
+}
+
 }  // namespace
 
 extern "C" {
@@ -48,8 +73,7 @@ extern "C" {
 int pdlp_halpern_iterate(pdlp_handle h, int iters)
 {
     if (!h || iters < 0) return PDLP_ERR_INVALID;
-    // forms this mode does not have: mixed precision / delta mode, a shard of a problem, an exchange of any kind, graph replay
-    if (h->mixed || h->delta || h->nl != h->p.n || h->ml != h->p.m || h->comm || h->peer.on || h->graph_ok) return PDLP_ERR_STATE;
+    if (halpern_refused(h)) return PDLP_ERR_STATE;
     if (iters == 0) return PDLP_OK;
     char rname[64];
     if (g_roctx.level > 0) std::snprintf(rname, sizeof rname, "pdlp: %d Halpern iterations", iters);
@@ -61,7 +85,16 @@ int pdlp_halpern_iterate(pdlp_handle h, int iters)
     h->kty_cur = -1; h->kty_tail_done = false; h->avg_products = false;
     h->sums_broken = true;
     h->halpern = true;             // PDLP_AVG holds the candidate now: pdlp_flush_average / pdlp_compute_average are refused
+    h->halpern_pair = true;        // PDLP_PREV and PDLP_AVG are z and T(z) of the last iteration (pdlp_halpern_fixed_point)
     return DISPATCH(h, halpern_iterate_t, h, iters);
+}
+
+int pdlp_halpern_fixed_point(pdlp_handle h)
+{
+    if (!h) return PDLP_ERR_INVALID;
+    if (halpern_refused(h) || !h->halpern_pair) return PDLP_ERR_STATE;
+    Range range("pdlp: Halpern fixed-point residual", h->stream);
+    return DISPATCH(h, halpern_fixed_point_t, h);
 }
 
 }  // extern "C"

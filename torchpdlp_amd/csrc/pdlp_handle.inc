@@ -146,6 +146,7 @@ struct pdlp_solver {
     bool cur_kx_cached = false;   // the KKT pass of the current iterate took K x from the cache (nothing to swap on restart)
     bool no_running = false;      // PDLP_OPT_RUNNING_KKT = 0: every KKT pass multiplies (round-1 behaviour)
     bool halpern = false;         // pdlp_halpern_iterate has run since the last pdlp_set_iterate: PDLP_AVG holds its candidate, not an average
+    bool halpern_pair = false;    // PDLP_PREV / PDLP_AVG are still z / T(z) of the last Halpern iteration: no call has re-assigned the iterate buffers since
     double *partA = nullptr, *partB = nullptr, *red = nullptr, *sc = nullptr;
     void* rowsum = nullptr;       // row sums of the tiled kernel on their way to the epilogue: [groups][rs_stride]
     int64_t rs_stride = 0;        // rows + one row block                        (these three: copied from the Layout)

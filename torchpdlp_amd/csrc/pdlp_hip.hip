@@ -19,7 +19,7 @@
 //     pdlp_kkt.inc            KKT pass, report, flush / average / distance / infeasibility / power iteration; pdlp_restart
 //     pdlp_population.inc     the mv_* launchers; pdlp_mv_combine
 //     pdlp_driver.inc         the library's iteration driver: direct, graph replay, sharded over RCCL; pdlp_comm_*
-//     pdlp_halpern.inc        the reflected Halpern iteration (opt-in solve mode); pdlp_halpern_iterate
+//     pdlp_halpern.inc        the reflected Halpern iteration (opt-in solve mode); pdlp_halpern_iterate, pdlp_halpern_fixed_point
 //     pdlp_peer.inc           the direct exchange over HIP IPC: iterate_peer; pdlp_peer_*
 //     pdlp_ruiz.inc           entry points that take no handle: Ruiz blocks, pdlp_vec_*, the bandwidth probes
 //     pdlp_batch_host.inc     batched solves: launch shapes and pdlp_batch_*
@@ -150,9 +150,9 @@ inline int rows_grid(int64_t rows) { return rows > 0 ? grid_for(rows) : 0; }    
 // ================================================================================================
 extern "C" {
 
-// 18: pdlp_batch_* (batched solves over one matrix); pdlp_batch_attach_matrices, pdlp_batch_product, pdlp_halpern_iterate and then
-//     pdlp_pack_tile_items / pdlp_attach_packed_items (7-byte items on the float32 path; struct pdlp_tiles is unchanged) joined
-//     them without a change to any existing signature or struct, so the number stands
+// 18: pdlp_batch_* (batched solves over one matrix); pdlp_batch_attach_matrices, pdlp_batch_product, pdlp_halpern_iterate, then
+//     pdlp_pack_tile_items / pdlp_attach_packed_items (7-byte items on the float32 path; struct pdlp_tiles is unchanged) and
+//     pdlp_halpern_fixed_point joined them without a change to any existing signature or struct, so the number stands
 // 17: pdlp_peer_* (direct exchange over HIP IPC), PDLP_OPT_BEGIN_INLINE
 // 16: pdlp_set_option (the library reads no environment variables), pdlp_mv_product, pdlp_mv_combine, pdlp_vec_sqdist,
 //     pdlp_probe_gather, pdlp_tile_limits reports the threads per workgroup, pdlp_primal_half_piece / pdlp_dual_half_piece (results
@@ -366,7 +366,7 @@ int pdlp_set_iterate(pdlp_handle h, const void* x_local, const void* y_local)
     HIP_TRY(hipMemsetAsync(h->kx_sum, 0, h->ml * h->es, h->stream));
     HIP_TRY(hipMemsetAsync(h->kty_sum, 0, h->nl * h->es, h->stream));
     h->since_reset = 0; h->kty_tail_done = false; h->avg_products = false; h->sums_broken = false; h->cur_kx_cached = false;
-    h->halpern = false;
+    h->halpern = false; h->halpern_pair = false;
     return PDLP_OK;
 }
 
@@ -440,6 +440,7 @@ int pdlp_get_scalars(pdlp_handle h, double out[PDLP_NSCAL])
 int pdlp_primal_half(pdlp_handle h, int adaptive)
 {
     if (!h) return PDLP_ERR_INVALID;
+    h->halpern_pair = false;       // (a half-step re-assigns the iterate buffers)
     if (h->delta) return delta_primal_half(h, adaptive);
     return DISPATCH(h, primal_half_t, h, adaptive);
 }
@@ -447,6 +448,7 @@ int pdlp_primal_half(pdlp_handle h, int adaptive)
 int pdlp_dual_half(pdlp_handle h, int adaptive)
 {
     if (!h) return PDLP_ERR_INVALID;
+    h->halpern_pair = false;
     if (h->delta) return delta_dual_half(h, adaptive);
     return DISPATCH(h, dual_half_t, h, adaptive);
 }
@@ -557,6 +559,7 @@ int pdlp_adaptive_retry(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
     if (h->delta || h->sK.pending || h->sKT.pending || h->graph_ok) return PDLP_ERR_STATE;   // (float32 / float64 handles, between iterations)
+    h->halpern_pair = false;
     // the scalars: the rejected trial's weight leaves eta_total again, nothing is pending (the trial's epilogues have folded the
     // previous iterate's weight into the sums: the repeated half-steps must add nothing), k goes back; eta keeps the rule's eta'
     hipLaunchKernelGGL(k_retry_scalars, dim3(1), dim3(1), 0, h->stream, h->sc);
@@ -594,6 +597,7 @@ int pdlp_iterate(pdlp_handle h, int iters, int adaptive)
 {
     if (!h || iters < 0) return PDLP_ERR_INVALID;
     adaptive = adaptive ? 1 : 0;
+    h->halpern_pair = false;       // (PDHG iterations re-assign the iterate buffers)
     char rname[64];
     if (g_roctx.level > 0) std::snprintf(rname, sizeof rname, "pdlp: %d %s iterations", iters, adaptive ? "adaptive" : "fixed-step");
     Range range(rname, h->stream);

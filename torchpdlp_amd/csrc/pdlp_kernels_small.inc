@@ -306,6 +306,23 @@ __global__ __launch_bounds__(BLOCK) void k_sub(int64_t n, T* __restrict__ out, c
     for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) out[i] = a[i] - b[i];
 }
 
+// out = a - b and partials[blk][0] = sum (a - b)^2 in double over the workgroup's elements: k_sub and k_sqdiff in one pass (a thread
+// adds its elements in index order, then block_sum; no atomics, so the sums depend on n alone)
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_sub_sq(int64_t n, T* __restrict__ out, const T* __restrict__ a, const T* __restrict__ b,
+                                                  double* __restrict__ partials)
+{
+    __shared__ double dred[4];
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+        const T d = a[i] - b[i];
+        out[i] = d;
+        s += (double)d * (double)d;
+    }
+    s = block_sum(s, dred);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * NACC] = s;
+}
+
 // out = float(a - b): the float32 difference vector a delta-mode product gathers from
 __global__ __launch_bounds__(BLOCK) void k_diff_f32(int64_t n, float* __restrict__ out, const double* __restrict__ a,
                                                     const double* __restrict__ b)

@@ -285,6 +285,7 @@ int pdlp_restart(pdlp_handle h, int which)
 {
     if (!h || (which != PDLP_CUR && which != PDLP_AVG)) return PDLP_ERR_INVALID;
     const int cand = which == PDLP_CUR ? 0 : 1;
+    h->halpern_pair = false;       // (t = 0 again: the next fixed-point residual belongs to the next Halpern iteration)
     if (which == PDLP_AVG) {       // the averaged iterate becomes current (pdhg.py:133,137,141)
         const int t = h->ix_cur;
         h->ix_cur = h->ix_avg;

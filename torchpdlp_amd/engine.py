@@ -370,6 +370,15 @@ class PdlpEngine(KernelChoice, Exchange):
         on one GPU without graph replay (``PdlpError`` otherwise)."""
         N.check(self.lib.pdlp_halpern_iterate(self.h, int(iters)), "pdlp_halpern_iterate")
 
+    def halpern_fixed_point(self) -> Tuple[float, float, float]:
+        """``(||dx||^2, dx'K'dy, ||dy||^2)`` of the last Halpern iteration (``pdlp_halpern_fixed_point``, include/pdlp_hip.h):
+        ``dx, dy`` = the iterate before that iteration (``N.PREV``) minus its candidate (``N.AVG``).  One vector pass and one product;
+        ``rules.fixed_point_error`` forms the residual from them.  Synchronises (it reads the three sums)."""
+        N.check(self.lib.pdlp_halpern_fixed_point(self.h), "pdlp_halpern_fixed_point")
+        out = (C.c_double * N.NRED)()
+        N.check(self.lib.pdlp_read_red(self.h, out), "pdlp_read_red")
+        return out[0], out[1], out[2]
+
     def adaptive_retry(self):
         """discard the adaptive iteration just taken (its trial was rejected: ``scalars()["accepted"] == 0``) so that it can be
         issued again with the shrunk step size -- ``pdlp_adaptive_retry`` (include/pdlp_hip.h), SURVEY quirk Q1's optional flag"""

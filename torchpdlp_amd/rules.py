@@ -80,6 +80,38 @@ def restart_decision(kkt_cur, kkt_avg, kkt_prev, kkt_first, tt, k, j, live=True,
     return dict(crit=crit[()], use_avg=use_avg[()], capped=capped[()], action=action[()])
 
 
+def fixed_point_error(dx2, cross, dy2, eta, omega):
+    """The fixed-point residual ``||z - T(z)||_P`` of a Halpern iterate from the three sums of ``pdlp_halpern_fixed_point``
+    (``||dx||^2``, ``dx'K'dy``, ``||dy||^2`` with ``dz = z - T(z)``) under the step's metric ``P = [[1/tau, -K'], [-K, 1/sigma]]``,
+    ``tau = eta/omega``, ``sigma = eta omega``:  ``r^2 = (omega/eta) ||dx||^2 - 2 dx'K'dy + ||dy||^2 / (eta omega)``.
+    Formed in float64 whatever the working precision (the sums are float64); a negative ``r^2`` -- rounding, when the three terms
+    cancel -- is clipped at 0."""
+    dx2, cross, dy2, eta, omega = (np.asarray(v, dtype=np.float64) for v in (dx2, cross, dy2, eta, omega))
+    r2 = (omega / eta) * dx2 - 2.0 * cross + dy2 / (eta * omega)
+    return np.sqrt(np.maximum(r2, 0.0))[()]
+
+
+def fixed_point_restart_decision(r, r_prev, r0, tt, k, j=0, live=True, max_kkt=np.inf, t=np.float32) -> dict:
+    """The restart decision of one check of the Halpern mode under ``halpern_restart="fixed_point"``: ``restart_decision``'s three
+    criteria with the fixed-point residual in the place of the KKT error.
+
+    ``r`` is the residual of the last iteration (``fixed_point_error``), ``r_prev`` the one at the previous check of this restart
+    period (``inf`` at the first check), ``r0`` the one at the restart point (of the first iteration after the restart), ``tt`` the
+    iterations since the last restart, ``k`` the iteration count.  Sufficient: ``r <= BETA[0] r0``; necessary: ``r <= BETA[1] r0``
+    and ``r > r_prev``; artificial: ``tt >= BETA[2] k``; in that order.  Returns the dict of ``restart_decision``: a restart always
+    adopts the candidate, so ``use_avg`` is true and ``action`` is 2 whenever ``crit >= 0``."""
+    rc, rp, rf = t(r), t(r_prev), t(r0)
+    live = np.asarray(live, dtype=bool)
+    suff = rc <= t(BETA[0]) * rf
+    nec = (rc <= t(BETA[1]) * rf) & (rc > rp)
+    art = np.asarray(tt, dtype=np.float64) >= BETA[2] * np.asarray(k, dtype=np.float64)
+    crit = np.where(live, np.where(suff, 0, np.where(nec, 1, np.where(art, 2, -1))), -1)
+    restart = crit >= 0
+    capped = live & ~restart & (np.asarray(j) >= max_kkt)
+    action = np.where(restart, 2, np.where(capped, 1, 0)).astype(np.int32)
+    return dict(crit=crit[()], use_avg=restart[()], capped=capped[()], action=action[()])
+
+
 def start_eta(sigma, t=np.float32):
     """pdhg.py:22: the first step size from the estimate of ||K||_2"""
     return t(0.9) / t(sigma)

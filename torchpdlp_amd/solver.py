@@ -15,8 +15,8 @@ import torch
 
 from . import _native as N
 from .engine import Comm, PdlpEngine
-from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, kkt_error, np_type, previous_kkt_matters,   # noqa: F401
-                    primal_weight, restart_decision, start_eta, start_omega, terminated)
+from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, fixed_point_error, fixed_point_restart_decision,   # noqa: F401
+                    kkt_error, np_type, previous_kkt_matters, primal_weight, restart_decision, start_eta, start_omega, terminated)
 from .quad import REFUSED as QUAD_REFUSED, check_quad_diag
 from .ranged import REFUSED as RANGED_REFUSED, check_row_upper, norm_vector as ranged_norm_vector
 from .sparse import CsrPair, as_vec, resolve_device     # noqa: F401  (resolve_device: api.py and callers take it from here)
@@ -31,7 +31,18 @@ def check_termination(primal_residual, dual_residual, duality_gap, prim_obj, adj
 kkt_from_residuals = kkt_error
 HALPERN_REFUSED = ("halpern=True runs the fixed step on one GPU in float32 or float64: not with adaptive, adaptive_retry, "
                    "infeasibility_detect, mixed precision or a communicator")
+HALPERN_RESTARTS = ("kkt", "fixed_point")
 primal_weight_from_distances = primal_weight
+
+
+def check_halpern_restart(halpern_restart, halpern) -> str:
+    """``halpern_restart`` as given to a solve: one of ``HALPERN_RESTARTS``, and anything but "kkt" only with ``halpern=True``
+    (``ValueError`` otherwise: the callers check before any device work)"""
+    if halpern_restart not in HALPERN_RESTARTS:
+        raise ValueError(f"unknown halpern_restart {halpern_restart!r}: one of {', '.join(map(repr, HALPERN_RESTARTS))}")
+    if halpern_restart != "kkt" and not halpern:
+        raise ValueError(f"halpern_restart={halpern_restart!r} is a restart rule of the Halpern mode: it needs halpern=True")
+    return halpern_restart
 
 
 def precond_factors(precondition, data_precond):
@@ -71,13 +82,23 @@ class PdhgDriver:
     candidate's error at the previous check of this restart period (``inf`` at the first) -- so the decision is "restart at the
     candidate" or "keep"; ``after_restart`` runs as it is.  KKT-pass accounting: ``j += iters`` per segment, ``j += 1`` per check,
     and the two of ``after_restart``.
+
+    ``halpern_restart="fixed_point"`` (with ``halpern``; default "kkt" = the paragraph above): the restart decision looks at the
+    fixed-point residual ``r = ||z - T(z)||_P`` of the last iteration instead (``eng.halpern_fixed_point``, one product and no KKT
+    pass; ``rules.fixed_point_error`` / ``fixed_point_restart_decision``).  ``r0``, the residual at the restart point, is evaluated
+    after the first iteration of every restart period -- a segment that starts a period is ``halpern_iterate(1)``, the evaluation,
+    ``halpern_iterate(rest)``; the checks stay on the multiples of the period.  ``j += 1`` per evaluation, ``r0`` included.
+    ``after_restart`` runs as it is: it adopts the candidate, and its KKT pass at the restart point is the termination test.
     """
 
     def __init__(self, eng: PdlpEngine, restart_period=40, primal_update=False, adaptive=False, precondition=False,
                  tol=1e-4, verbose=False, trace=None, infeasibility_detect=False, infeas_tol=1e-4, adaptive_retry=False,
-                 halpern=False):
+                 halpern=False, halpern_restart="kkt"):
         self.eng, self.period = eng, int(restart_period)
         self.halpern = bool(halpern)
+        self.fixed_point = check_halpern_restart(halpern_restart, self.halpern) == "fixed_point"
+        self.eta = None                                                     # the fixed step of the run (start)
+        self.r0 = self.r_prev = None                                        # fixed-point rule: the residual at the restart point / at the previous check
         if self.halpern and (adaptive or adaptive_retry or infeasibility_detect or getattr(eng, "mixed", False) or eng.comm is not None):
             raise ValueError(HALPERN_REFUSED)
         self.kkt_prev_cand = None                                           # Halpern: the candidate's KKT error at the previous check
@@ -119,6 +140,8 @@ class PdhgDriver:
         else:
             eng.set_iterate(zeros(eng.nl), zeros(eng.ml))
         eng.set_step(eta, self.omega, theta, 0)
+        self.eta = eta
+        self.r0 = self.r_prev = None
         if self.infeasibility_detect:
             eng.infeas_reset()                                              # pdhg.py:39-40
         self.n = self.k = self.j = self.tt = 0
@@ -159,7 +182,14 @@ class PdhgDriver:
         iters = min(self.period - self.tt % self.period, max_iters)
         if iters <= 0:
             return 0, False
-        if self.halpern:
+        if self.halpern and self.fixed_point and self.tt == 0:
+            # the first iteration of a restart period starts at the anchor: its residual is r0 (with the omega of this period)
+            eng.halpern_iterate(1)
+            self.r0, self.r_prev = fixed_point_error(*eng.halpern_fixed_point(), self.eta, self.omega), None
+            self.j += iters + 1
+            if iters > 1:
+                eng.halpern_iterate(iters - 1)
+        elif self.halpern:
             eng.halpern_iterate(iters)
             self.j += iters
         elif self.adaptive_retry:                    # every iteration is tried until a step is accepted, one KKT-pass count per trial
@@ -211,10 +241,40 @@ class PdhgDriver:
             eng.synchronize()
             self.check_seconds += time.perf_counter() - t_check
 
+    def _halpern_fixed_point_check(self):
+        """the restart check under ``halpern_restart="fixed_point"``: one evaluation of the fixed-point residual, no KKT pass"""
+        eng, t = self.eng, self.t
+        timed = self.check_seconds is not None
+        if timed:
+            eng.synchronize()
+            t_check = time.perf_counter()
+        self.checks += 1
+        with N.trace_range("pdlp: restart check (Halpern fixed-point residual)", getattr(eng, "stream", None)):
+            r = fixed_point_error(*eng.halpern_fixed_point(), self.eta, self.omega)
+            r_prev = np.inf if self.r_prev is None else self.r_prev
+            self.r_prev = r
+            self.j += 1
+            if self.trace is not None:
+                self.trace["kkt"] += [float(np.inf), float(r), float(r_prev)]
+            dec = fixed_point_restart_decision(r, r_prev, self.r0, self.tt, self.k, self.j, live=True, t=t)
+        crit = int(dec["crit"])
+        if crit >= 0:
+            if self.verbose:
+                print(f"{('Sufficient', 'Necessary', 'Artificial')[crit]} restart at iteration {self.tt} using the Halpern candidate.")
+            if self.trace is not None:
+                self.trace["restarts"].append((crit, self.tt, 1))
+            with N.trace_range("pdlp: restart work (restart, primal weight, termination test)", getattr(eng, "stream", None)):
+                # no KKT pass was made at the candidate: after_restart adopts it (eng.restart(N.AVG), as it does when the KKT-pass cap
+                # ends a period) and evaluates it as the new current iterate
+                self.after_restart(None)
+        if timed:
+            eng.synchronize()
+            self.check_seconds += time.perf_counter() - t_check
+
     def _restart_check(self):
         """pdhg.py:115-146: the three KKT errors, the decision and, when it says so, the restart with its work"""
         if self.halpern:
-            return self._halpern_check()
+            return self._halpern_fixed_point_check() if self.fixed_point else self._halpern_check()
         eng, t = self.eng, self.t
         timed = self.check_seconds is not None
         if timed:
@@ -317,18 +377,20 @@ def estimate_sigma(eng: PdlpEngine, b0=None, power_iters=100, seed=None) -> floa
 def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_period=40, precondition=False,
              primal_update=False, adaptive=False, time_limit=3600, time_used=0, x_init=None, y_init=None,
              b0=None, sigma=None, power_iters=100, seed=None, trace=None, infeasibility_detect=False, infeas_tol=1e-4,
-             adaptive_retry=False, *, report=None, halpern=False):
+             adaptive_retry=False, *, report=None, halpern=False, halpern_restart="kkt"):
     """The outer loop over an existing engine.  Returns (x_local, prim_obj, k, n, j, status, total_time).
     ``report``: a dict that receives ``PdlpEngine.report`` of the returned iterate (this rank's blocks; of the un-preconditioned
     problem when ``precondition``) whatever the status, and ``q_norm`` / ``c_norm`` as the termination test used them -- in the
     style of ``trace``.  ``halpern``: the restarted, reflected Halpern iteration (``PdhgDriver``); the returned iterate is then the
-    candidate of the last restart or, when the run ends between restarts, of the last iteration."""
+    candidate of the last restart or, when the run ends between restarts, of the last iteration.  ``halpern_restart``: "kkt" or
+    "fixed_point", the quantity its restart checks look at (``PdhgDriver``)."""
     t0 = time.time()
+    check_halpern_restart(halpern_restart, halpern)
     if adaptive_retry and (getattr(eng, "delta", False) or infeasibility_detect):
         raise ValueError("adaptive_retry works on float32 / float64 engines without the infeasibility detector")
     drv = PdhgDriver(eng, restart_period, primal_update=primal_update, adaptive=adaptive, precondition=precondition, tol=tol,
                      verbose=verbose, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
-                     adaptive_retry=adaptive_retry, halpern=halpern)
+                     adaptive_retry=adaptive_retry, halpern=halpern, halpern_restart=halpern_restart)
     if sigma is None:                                                       # pdhg.py:22
         sigma = estimate_sigma(eng, b0, power_iters, seed)
     drv.start(sigma, x_init, y_init)
@@ -382,7 +444,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
                    precondition=False, primal_update=False, adaptive=False, data_precond=None, infeasibility_detect=False,
                    infeas_tol=1e-4, time_limit=3600, time_used=0, x_init=None, y_init=None, *, b0=None, sigma=None,
                    seed=None, trace=None, comm=None, precision=None, adaptive_retry=False, report=None,
-                   halpern=False, q_upper=None, quad_diag=None):
+                   halpern=False, q_upper=None, quad_diag=None, halpern_restart="kkt"):
     """Drop-in for the reference's ``pdlp_algorithm`` (primal_dual_hybrid_gradient.py:7) on one MI355X.
 
     ``K`` may be a dense / COO torch tensor (as the reference takes), a scipy sparse matrix or a
@@ -413,7 +475,10 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     PDHG -- fixed step, the restart rules and the primal weight unchanged, evaluated at the candidate (one PDHG step from the
     Halpern iterate); see ``PdhgDriver`` and DESIGN.md 4.2.  Works with ``precondition``, ``primal_update`` and ``x_init`` /
     ``y_init``; ``ValueError`` together with ``adaptive``, ``adaptive_retry``, ``infeasibility_detect``, ``precision="mixed"`` or
-    ``comm``.
+    ``comm``.  ``halpern_restart`` (default "kkt": the sentence above): "fixed_point" restarts on the fixed-point residual
+    ``||z - T(z)||_P`` of the Halpern iterate instead of the candidate's KKT error -- the criterion of the rHPDHG papers; a check then
+    costs one product and no KKT pass (``PdhgDriver``).  ``ValueError`` (before any device work) for another value
+    and for "fixed_point" without ``halpern``.
 
     ``q_upper`` (length m, default None): two-sided rows ``q_i <= (K x)_i <= q_upper_i`` on the inequality rows, entered once
     (``+inf``: a one-sided row; ``== q_i``: behaves as an equality row; on equality rows ``+inf`` or ``q_i``, ignored); the sign
@@ -435,6 +500,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     ``xbar`` and ``y`` over RCCL, and every rank returns the full solution.
     """
     from .distributed import gather_report, gather_solution, shard_engine, start_blocks
+    check_halpern_restart(halpern_restart, halpern)
     if halpern and (adaptive or adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False)):
         raise ValueError(HALPERN_REFUSED)
     if q_upper is not None:
@@ -478,7 +544,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
         eng, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period, precondition=precondition,
         primal_update=primal_update, adaptive=adaptive, time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init,
         b0=b0, sigma=sigma, seed=seed, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
-        adaptive_retry=adaptive_retry, report=report, halpern=halpern)
+        adaptive_retry=adaptive_retry, report=report, halpern=halpern, halpern_restart=halpern_restart)
     if report is not None:
         report.update(gather_report(eng, report, Kp.n, Kp.m))
     return gather_solution(eng, x, Kp.n).view(-1, 1), obj, k, n, j, status, total
