@@ -12,7 +12,7 @@ import torch
 
 from .mps import mps_to_ranged_form, mps_to_standard_form
 from .precondition import Scaling, equilibrate_matrix, ruiz_precondition, ruiz_precondition_batch
-from .solver import is_mixed, pdlp_algorithm, resolve_device
+from .solver import check_composition, check_quad_diag, check_row_upper, is_mixed, pdlp_algorithm, resolve_device
 from .sparse import CsrPair
 
 
@@ -122,24 +122,15 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     from_file = isinstance(problem, (str, os.PathLike))
     if ranged_rows and (not from_file or q_upper is not None):
         raise ValueError("ranged_rows=True reads the RANGES rows of an MPS path; arrays carry q_upper themselves")
-    if q_upper is not None or ranged_rows:
-        from .ranged import REFUSED, check_row_upper
-        if (is_mixed(precision) or comm not in (None, False) or infeasibility_detect or fishnet or adaptive_retry
-                or direct_exchange):
-            raise ValueError(REFUSED)
-        if q_upper is not None:
-            check_row_upper(problem[2], q_upper, problem[3])
-    if quad_diag is not None:
-        from .quad import REFUSED as QUAD_REFUSED, check_quad_diag
-        if (is_mixed(precision) or comm not in (None, False) or infeasibility_detect or fishnet or adaptive_retry
-                or direct_exchange):
-            raise ValueError(QUAD_REFUSED)
-        # (an MPS path: shape, sign and finiteness now, the length once the file is read)
-        quad_diag = check_quad_diag(quad_diag, None if from_file else torch.as_tensor(problem[0]).numel())
-    if halpern and (adaptive_stepsize or adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False)
-                    or direct_exchange):
-        from .solver import HALPERN_REFUSED
-        raise ValueError(HALPERN_REFUSED)
+    if q_upper is not None or ranged_rows or quad_diag is not None:
+        is_mixed(precision)                     # (an unknown precision is its own error)
+    check_composition(halpern=halpern, q_upper=q_upper is not None or ranged_rows, quad_diag=quad_diag is not None,
+                      adaptive=adaptive_stepsize, adaptive_retry=adaptive_retry, infeasibility_detect=infeasibility_detect,
+                      mixed=precision is not None, comm=comm not in (None, False), fishnet=fishnet, direct_exchange=direct_exchange)
+    if q_upper is not None:
+        check_row_upper(problem[2], q_upper, problem[3])
+    # (an MPS path: shape, sign and finiteness now, the length once the file is read)
+    quad_diag = check_quad_diag(quad_diag, None if from_file or quad_diag is None else torch.as_tensor(problem[0]).numel())
     device = resolve_device(device)
     if is_mixed(precision):
         dtype = torch.float64

@@ -17,7 +17,7 @@ int batch_check(pdlp_handle h, const pdlp_batch* b)
         !b->y_prev || !b->y_sum || !b->y_avg || !b->y_last || !b->dy || !b->eta || !b->omega || !b->eta_sum || !b->wpend ||
         !b->live || !b->action || !b->part || !b->out)
         return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->delta) return PDLP_ERR_STATE;     // single GPU, one precision
+    if (!whole_problem(h) || h->mixed || h->delta) return PDLP_ERR_STATE;     // single GPU, one precision
     if (h->obj_diag) return PDLP_ERR_STATE;      // (the batch kernels know the linear objective only: pdlp_set_objective_diag)
     if (h->p.n < 1 || h->p.m < 1) return PDLP_ERR_INVALID;
     if (h->bm.K_val && h->bm.Bp != b->Bp) return PDLP_ERR_INVALID;      // the attached populations have another width
@@ -330,7 +330,7 @@ int pdlp_batch_attach_matrices(pdlp_handle h, int Bp, const void* K_valB, const 
         return PDLP_OK;
     }
     if (!K_valB || !KT_valB || Bp < 8 || Bp % 8 != 0 || (d_colB == nullptr) != (d_rowB == nullptr)) return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->delta || h->obj_diag) return PDLP_ERR_STATE;     // single GPU, one precision, linear objective
+    if (!whole_problem(h) || h->mixed || h->delta || h->obj_diag) return PDLP_ERR_STATE;     // single GPU, one precision, linear objective
     h->bm.Bp = Bp;
     h->bm.K_val = K_valB; h->bm.KT_val = KT_valB;
     h->bm.d_col = d_colB; h->bm.d_row = d_rowB;

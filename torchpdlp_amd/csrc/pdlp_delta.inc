@@ -72,11 +72,11 @@ template <bool ADAPT, bool PEER> int delta_dual_half_a(pdlp_handle h)
 
 int delta_primal_half(pdlp_handle h, int adaptive)
 {
-    return with_adapt_peer(h, adaptive, [&](auto A, auto P) { return delta_primal_half_a<decltype(A)::value, decltype(P)::value>(h); });
+    return with_flags([&](auto A, auto P) { return delta_primal_half_a<A.value, P.value>(h); }, adaptive, h->peer.active);
 }
 int delta_dual_half(pdlp_handle h, int adaptive)
 {
-    return with_adapt_peer(h, adaptive, [&](auto A, auto P) { return delta_dual_half_a<decltype(A)::value, decltype(P)::value>(h); });
+    return with_flags([&](auto A, auto P) { return delta_dual_half_a<A.value, P.value>(h); }, adaptive, h->peer.active);
 }
 
 // KKT sums of a candidate from the anchors: the current iterate needs at most the pending K'dy; the averaged / previous

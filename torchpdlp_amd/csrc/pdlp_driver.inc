@@ -277,7 +277,7 @@ int pdlp_comm_init(pdlp_handle h, const char* rccl_path, const void* id128, int 
     // equal blocks, this rank's at rank * block (the padded layout of torchpdlp_amd/distributed.py)
     if (h->nl * nranks != h->p.n || h->ml * nranks != h->p.m || h->p.col0 != (int64_t)rank * h->nl || h->p.row0 != (int64_t)rank * h->ml)
         return PDLP_ERR_INVALID;
-    if (h->q_upper || h->obj_diag) return PDLP_ERR_STATE;      // (two-sided rows and the quadratic term have no sharded form)
+    if (has_extension(h)) return PDLP_ERR_STATE;      // (two-sided rows and the quadratic term have no sharded form)
     const int rc = rccl_load(rccl_path);
     if (rc != PDLP_OK) return rc;
     if (h->comm) { (void)g_rccl.CommDestroy(h->comm); h->comm = nullptr; }

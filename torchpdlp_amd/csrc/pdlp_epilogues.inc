@@ -41,8 +41,17 @@ template <typename T> struct StoreEpi {
 // constraint-side functors -- q_upper[i], loaded in pre() beside q[i] -- and the upper side's arithmetic; RANGED = false (the default)
 // has neither the pointer in the kernel arguments nor the value in the operand set (the tiled kernel sizes its epilogue groups by
 // sizeof(Pre)), so those instantiations are what they were before two-sided rows existed.
-template <typename T, bool RANGED> struct RowUpper { const T* p = nullptr; };
-template <typename T> struct RowUpper<T, false> {};
+// An operand that only the RANGED / QUAD form of a functor has: a T, or an empty member ([[no_unique_address]], last in the operand
+// struct, so sizeof(Pre) is that of the members before it -- pinned by a static_assert beside each struct).
+struct Absent {};
+template <typename T, bool ON> using Opt = std::conditional_t<ON, T, Absent>;
+template <typename T, bool RANGED> struct RowUpper {
+    const T* p = nullptr;
+    __device__ __forceinline__ T at(int i) const { return p[i]; }
+};
+template <typename T> struct RowUpper<T, false> {
+    __device__ __forceinline__ Absent at(int) const { return {}; }
+};
 // y' of an inequality row from a = y + sigma (q - k) and b = y + sigma (q_upper - k): a above zero (the lower side pushes), b below
 // zero (the upper side pushes), else 0.  Every operation is monotone, so a <= b after rounding too and at most one side is active.
 // Written from a < 0 so that with q_upper = +inf (b = +inf) the value is the one-sided `a < 0 ? 0 : a` bit for bit (a = -0 included).
@@ -53,18 +62,65 @@ template <typename T> __device__ __forceinline__ T ranged_dual(T a, T b) { retur
 // the gradient; QUAD = false (the default) has neither the pointer in the kernel arguments nor the value in the operand set (the tiled
 // kernel sizes its epilogue groups by sizeof(Pre)), so those instantiations are what they were before the quadratic term existed.
 // Only PEER = false functors have the QUAD form: a handle with the term is one GPU without an exchange.
-template <typename T, bool QUAD> struct ObjDiag { const T* p = nullptr; };
-template <typename T> struct ObjDiag<T, false> {};
+template <typename T, bool QUAD> struct ObjDiag {
+    const T* p = nullptr;
+    __device__ __forceinline__ T at(int j) const { return p[j]; }
+};
+template <typename T> struct ObjDiag<T, false> {
+    __device__ __forceinline__ Absent at(int) const { return {}; }
+};
 // the prox of tau (c'x + 1/2 x'Dx) at z = x - tau (c - K'y): z / (1 + tau d), before the clamp; d = 0 divides by 1, which is exact
 template <typename T> __device__ __forceinline__ T quad_prox(T z, T tau, T dj) { return z / ((T)1 + tau * dj); }
 // 1/2 d_j x_j^2 in double: joins c_j x_j in the primal objective's sum and leaves the sum l'max(lam, 0) of the dual objective.  Formed
 // from the SCALED pair (d_s = d D_col^2, x_s = x / D_col), of which it is invariant, so UNSCALE needs no factor of its own.
 template <typename T> __device__ __forceinline__ double quad_half(T dj, T xj) { return 0.5 * (double)dj * ((double)xj * (double)xj); }
 
+// ---- the arithmetic every kernel file shares (this file is included before all of them) --------------------------------------
+// lam = project_lambda_box(g) (helpers.py:21-37) with the bound classes read off l, u: a variable without a lower bound takes
+// min(g, 0), one without an upper bound max(g, 0), a free one 0, a boxed one g.  ninf / pinf: the classes, for the callers' own use.
+// (Operands by reference here and in primal_step: handed over by value the compiler knows them to be defined and folds the `&&`
+// otherwise than in a body written out; by reference the kernels are what they were, instruction for instruction.)
+template <typename T> __device__ __forceinline__ T project_lambda(const T& g, const bool& ninf, const bool& pinf)
+{
+    T lam;
+    if (ninf && pinf) lam = (T)0;
+    else if (ninf) lam = g < (T)0 ? g : (T)0;
+    else if (pinf) lam = g > (T)0 ? g : (T)0;
+    else lam = g;
+    return lam;
+}
+template <typename T> struct BoxLam { T lam; bool ninf, pinf; };
+template <typename T> __device__ __forceinline__ BoxLam<T> project_lambda(const T& g, const T& lo, const T& hi)
+{
+    const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
+    return {project_lambda(g, ninf, pinf), ninf, pinf};
+}
+// x' = clamp(x - tau (c - K'y), l, u) (step.py:25-30 / :74-82; PDHG_step spectral_casting.py:277-284), with the prox of the
+// quadratic term ahead of the clamp when there is a d_j
+template <typename T, bool QUAD = false>
+__device__ __forceinline__ T primal_step(const T& xo, const T& tau, const T& cj, const T& kty, const T& lo, const T& hi, const Opt<T, QUAD>& dj = {})
+{
+    const T grad = cj - kty;
+    T v = xo - tau * grad;
+    if constexpr (QUAD) v = quad_prox(v, tau, dj);
+    v = v < lo ? lo : v;
+    v = v > hi ? hi : v;
+    return v;
+}
+// y' = y + sigma (q - K xbar), an inequality row (i < ineq_end) projected onto y >= 0 (step.py:33-38 / :85-90; PDHG_step
+// spectral_casting.py:287-292).  The RANGED form of DualEpi and HalpernDualEpi projects with ranged_dual in the functor's own body:
+// through this function the tiled kernel of those two comes out with selects where it has branches.
+template <typename T> __device__ __forceinline__ T dual_step(int i, int ineq_end, T yo, T sigma, T qi, T k)
+{
+    T v = yo + sigma * (qi - k);
+    if (i < ineq_end && v < (T)0) v = (T)0;
+    return v;
+}
+
 // primal half-step over this rank's rows of K' (= its variables).  kty = (K'y)_j.
 // step.py:25-30 (fixed) / :74-82 (adaptive); running sum pdhg.py:107.
-template <typename T, bool QUAD> struct PrimalPre { T xo, cj, lo, hi, sum, ks; };
-template <typename T> struct PrimalPre<T, true> { T xo, cj, lo, hi, sum, ks, dj; };
+template <typename T, bool QUAD> struct PrimalPre { T xo, cj, lo, hi, sum, ks; [[no_unique_address]] Opt<T, QUAD> dj; };
+static_assert(sizeof(PrimalPre<float, false>) == 6 * 4 && sizeof(PrimalPre<double, true>) == 7 * 8, "operands only");
 template <typename T, bool ADAPT, bool PEER = false, bool QUAD = false> struct PrimalEpi {
     static_assert(!(QUAD && PEER), "the quadratic term has no sharded form");
     static constexpr int NA = ADAPT ? 1 : 0;
@@ -76,6 +132,7 @@ template <typename T, bool ADAPT, bool PEER = false, bool QUAD = false> struct P
     T tau = 0, theta = 0, w = 0, wk = 0;
     PeerOut<T, PEER> peer{};               // the other ranks' xbar, at this rank's block
     [[no_unique_address]] ObjDiag<T, QUAD> diag{};          // d of this rank's variables
+    static constexpr bool working_matrix_only = QUAD;      // (launch_csr)
     __device__ void load()
     {
         tau = (T)sc[S_TAU];
@@ -86,20 +143,14 @@ template <typename T, bool ADAPT, bool PEER = false, bool QUAD = false> struct P
     typedef PrimalPre<T, QUAD> Pre;
     __device__ Pre pre(int j) const
     {
-        if constexpr (QUAD) return Pre{x_old[j], c[j], l[j], u[j], x_sum[j], kty_sum ? kty_sum[j] : (T)0, diag.p[j]};
-        else return Pre{x_old[j], c[j], l[j], u[j], x_sum[j], kty_sum ? kty_sum[j] : (T)0};
+        return Pre{x_old[j], c[j], l[j], u[j], x_sum[j], kty_sum ? kty_sum[j] : (T)0, diag.at(j)};
     }
     __device__ void operator()(int j, T kty, double* acc) const { (*this)(j, kty, pre(j), acc); }
     __device__ void operator()(int j, T kty, const Pre& p, double* acc) const
     {
         const T xo = p.xo;
-        const T grad = p.cj - kty;
         if (kty_sum) kty_sum[j] = p.ks + wk * kty;
-        T v = xo - tau * grad;
-        if constexpr (QUAD) v = quad_prox(v, tau, p.dj);
-        const T lo = p.lo, hi = p.hi;
-        v = v < lo ? lo : v;
-        v = v > hi ? hi : v;
+        const T v = primal_step<T, QUAD>(xo, tau, p.cj, kty, p.lo, p.hi, p.dj);
         const T d = v - xo;
         x_new[j] = v;
         const T xb = v + theta * d;
@@ -116,8 +167,8 @@ template <typename T, bool ADAPT, bool PEER = false, bool QUAD = false> struct P
 
 // dual half-step over this rank's rows of K (= its constraints).  kxbar = (K xbar)_i.
 // step.py:33-38 / :85-96; running sum pdhg.py:108.
-template <typename T, bool RANGED> struct DualPre { T yo, qi, sum, kxo, kxs; };
-template <typename T> struct DualPre<T, true> { T yo, qi, sum, kxo, kxs, qu; };
+template <typename T, bool RANGED> struct DualPre { T yo, qi, sum, kxo, kxs; [[no_unique_address]] Opt<T, RANGED> qu; };
+static_assert(sizeof(DualPre<float, false>) == 5 * 4 && sizeof(DualPre<double, true>) == 6 * 8, "operands only");
 template <typename T, bool ADAPT, bool PEER = false, bool RANGED = false> struct DualEpi {
     static constexpr int NA = ADAPT ? 2 : 0;
     const T* y_old; T* y_new; const T* q; T* y_sum; T* kx; const double* sc; int ineq_end;
@@ -127,6 +178,7 @@ template <typename T, bool ADAPT, bool PEER = false, bool RANGED = false> struct
     T sigma = 0, w = 0, inv1pt = 0;
     PeerOut<T, PEER> peer{};               // the other ranks' copy of the y buffer being written, at this rank's block
     [[no_unique_address]] RowUpper<T, RANGED> upper{};      // q_upper of this rank's rows
+    static constexpr bool working_matrix_only = RANGED;
     __device__ void load()
     {
         sigma = (T)sc[S_SIGMA];
@@ -136,18 +188,18 @@ template <typename T, bool ADAPT, bool PEER = false, bool RANGED = false> struct
     typedef DualPre<T, RANGED> Pre;
     __device__ Pre pre(int i) const
     {
-        if constexpr (RANGED) return Pre{y_old[i], q[i], y_sum[i], kx[i], kx_sum ? kx_sum[i] : (T)0, upper.p[i]};
-        else return Pre{y_old[i], q[i], y_sum[i], kx[i], kx_sum ? kx_sum[i] : (T)0};
+        return Pre{y_old[i], q[i], y_sum[i], kx[i], kx_sum ? kx_sum[i] : (T)0, upper.at(i)};
     }
     __device__ void operator()(int i, T kxbar, double* acc) const { (*this)(i, kxbar, pre(i), acc); }
     __device__ void operator()(int i, T kxbar, const Pre& p, double* acc) const
     {
         const T yo = p.yo;
-        T v = yo + sigma * (p.qi - kxbar);
+        T v;
         if constexpr (RANGED) {
+            v = yo + sigma * (p.qi - kxbar);
             if (i < ineq_end) v = ranged_dual(v, yo + sigma * (p.qu - kxbar));
         } else {
-            if (i < ineq_end && v < (T)0) v = (T)0;
+            v = dual_step(i, ineq_end, yo, sigma, p.qi, kxbar);
         }
         y_new[i] = v;
         peer(i, v);
@@ -173,31 +225,26 @@ template <typename T, bool ADAPT, bool PEER = false, bool RANGED = false> struct
 // x' and xbar are formed with PrimalEpi's own expressions at theta = 1 (the candidate equals one fixed PDHG step bit for bit);
 // the new iterate is the reflected point xbar = 2x' - x pulled towards the anchor: x+ = a xbar + b x_last, a = (t+1)/(t+2),
 // b = 1/(t+2) rounded once on the host.  No running sums: five operand loads, three stores.
-template <typename T, bool QUAD> struct HalpernPrimalPre { T xo, xl, cj, lo, hi; };
-template <typename T> struct HalpernPrimalPre<T, true> { T xo, xl, cj, lo, hi, dj; };
+template <typename T, bool QUAD> struct HalpernPrimalPre { T xo, xl, cj, lo, hi; [[no_unique_address]] Opt<T, QUAD> dj; };
+static_assert(sizeof(HalpernPrimalPre<float, false>) == 5 * 4 && sizeof(HalpernPrimalPre<double, true>) == 6 * 8, "operands only");
 template <typename T, bool QUAD = false> struct HalpernPrimalEpi {
     static constexpr int NA = 0;
     const T* x_old; T* x_new; T* xbar; T* x_cand; const T* x_last; const T* c; const T* l; const T* u; const double* sc;
     T a, b;
     T tau = 0;
     [[no_unique_address]] ObjDiag<T, QUAD> diag{};
+    static constexpr bool working_matrix_only = QUAD;
     __device__ void load() { tau = (T)sc[S_TAU]; }
     typedef HalpernPrimalPre<T, QUAD> Pre;
     __device__ Pre pre(int j) const
     {
-        if constexpr (QUAD) return Pre{x_old[j], x_last[j], c[j], l[j], u[j], diag.p[j]};
-        else return Pre{x_old[j], x_last[j], c[j], l[j], u[j]};
+        return Pre{x_old[j], x_last[j], c[j], l[j], u[j], diag.at(j)};
     }
     __device__ void operator()(int j, T kty, double* acc) const { (*this)(j, kty, pre(j), acc); }
     __device__ void operator()(int j, T kty, const Pre& p, double*) const
     {
         const T xo = p.xo;
-        const T grad = p.cj - kty;
-        T v = xo - tau * grad;
-        if constexpr (QUAD) v = quad_prox(v, tau, p.dj);
-        const T lo = p.lo, hi = p.hi;
-        v = v < lo ? lo : v;
-        v = v > hi ? hi : v;
+        const T v = primal_step<T, QUAD>(xo, tau, p.cj, kty, p.lo, p.hi, p.dj);
         const T d = v - xo;
         x_cand[j] = v;
         const T xb = v + d;                // (PrimalEpi's v + theta * d at theta = 1: the product with 1 is exact)
@@ -207,30 +254,31 @@ template <typename T, bool QUAD = false> struct HalpernPrimalEpi {
 };
 
 // Reflected Halpern iteration, dual half over the rows of K: y' as DualEpi forms it; y+ = a (2y' - y) + b y_last.
-template <typename T, bool RANGED> struct HalpernDualPre { T yo, yl, qi; };
-template <typename T> struct HalpernDualPre<T, true> { T yo, yl, qi, qu; };
+template <typename T, bool RANGED> struct HalpernDualPre { T yo, yl, qi; [[no_unique_address]] Opt<T, RANGED> qu; };
+static_assert(sizeof(HalpernDualPre<float, false>) == 3 * 4 && sizeof(HalpernDualPre<double, true>) == 4 * 8, "operands only");
 template <typename T, bool RANGED = false> struct HalpernDualEpi {
     static constexpr int NA = 0;
     const T* y_old; T* y_new; T* y_cand; const T* y_last; const T* q; const double* sc; int ineq_end;
     T a, b;
     T sigma = 0;
     [[no_unique_address]] RowUpper<T, RANGED> upper{};
+    static constexpr bool working_matrix_only = RANGED;
     __device__ void load() { sigma = (T)sc[S_SIGMA]; }
     typedef HalpernDualPre<T, RANGED> Pre;
     __device__ Pre pre(int i) const
     {
-        if constexpr (RANGED) return Pre{y_old[i], y_last[i], q[i], upper.p[i]};
-        else return Pre{y_old[i], y_last[i], q[i]};
+        return Pre{y_old[i], y_last[i], q[i], upper.at(i)};
     }
     __device__ void operator()(int i, T kxbar, double* acc) const { (*this)(i, kxbar, pre(i), acc); }
     __device__ void operator()(int i, T kxbar, const Pre& p, double*) const
     {
         const T yo = p.yo;
-        T v = yo + sigma * (p.qi - kxbar);
+        T v;
         if constexpr (RANGED) {
+            v = yo + sigma * (p.qi - kxbar);
             if (i < ineq_end) v = ranged_dual(v, yo + sigma * (p.qu - kxbar));
         } else {
-            if (i < ineq_end && v < (T)0) v = (T)0;
+            v = dual_step(i, ineq_end, yo, sigma, p.qi, kxbar);
         }
         y_cand[i] = v;
         y_new[i] = a * ((T)2 * v - yo) + b * p.yl;
@@ -259,52 +307,54 @@ template <typename T> struct FixedPointEpi {
 // Quadratic term (QUAD): the gradient is g = c + d x - K'y (formed from the scaled operands, before UNSCALE divides it), the primal
 // objective's sum acc[3] takes c_j x_j + 1/2 d_j x_j^2 and acc[1] takes -1/2 d_j x_j^2 besides l'max(lam, 0): the dual objective of the
 // quadratic problem is q'y + l'lam+ + u'lam- - 1/2 x'Dx, and the six sums keep their places (include/pdlp_hip.h).
-template <typename T, bool QUAD> struct KktDualPre { T cj, lo, hi, xj, d; };
-template <typename T> struct KktDualPre<T, true> { T cj, lo, hi, xj, d, qd; };
+template <typename T, bool QUAD> struct KktDualPre { T cj, lo, hi, xj, d; [[no_unique_address]] Opt<T, QUAD> qd; };
+static_assert(sizeof(KktDualPre<float, false>) == 5 * 4 && sizeof(KktDualPre<double, true>) == 6 * 8, "operands only");
+// the four sums of a variable from (K'y)_j and its operands -- the counterpart of row_sums, shared by the KKT pass and the report;
+// KEEP: lam_j goes to lam_out[j] (UNSCALE: of the un-preconditioned problem)
+template <typename T, bool UNSCALE, bool QUAD, bool KEEP = false>
+__device__ __forceinline__ void col_sums(T kty, const KktDualPre<T, QUAD>& p, double* acc, T* lam_out = nullptr, int j = 0)
+{
+    T cj = p.cj, lo = p.lo, hi = p.hi, xj = p.xj;
+    T g = cj - kty;
+    [[maybe_unused]] double hq = 0.0;
+    if constexpr (QUAD) g = (cj + p.qd * xj) - kty;
+    if (UNSCALE) {            // K_u'(D_row y) = (K_s'y)/D_col, c_u = c_s/D_col, l_u = l_s D_col, x_u = D_col x
+        const T d = p.d;
+        g = g / d; cj = cj / d; lo = lo * d; hi = hi * d; xj = xj * d;
+    }
+    if constexpr (QUAD) hq = quad_half(p.qd, p.xj);         // (of the scaled pair)
+    const BoxLam<T> b = project_lambda(g, lo, hi);
+    const T lam = b.lam;
+    if constexpr (KEEP) lam_out[j] = lam;
+    const T ld = b.ninf ? (T)0 : lo, ud = b.pinf ? (T)0 : hi;
+    const T r = g - lam;
+    acc[0] += (double)r * (double)r;
+    acc[1] += (double)ld * (double)(lam > (T)0 ? lam : (T)0);
+    acc[2] += (double)ud * (double)(lam < (T)0 ? lam : (T)0);
+    acc[3] += (double)cj * (double)xj;
+    if constexpr (QUAD) { acc[1] -= hq; acc[3] += hq; }     // (own additions: with d = 0 the sums are the linear ones bit for bit)
+}
 template <typename T, bool UNSCALE, bool QUAD = false> struct KktDualEpi {
     static constexpr int NA = 4;
     const T* x; const T* c; const T* l; const T* u; const T* dcol; T* kty_out;     // kty_out: keeps K'y for the next primal half-step
     [[no_unique_address]] ObjDiag<T, QUAD> diag{};
+    static constexpr bool working_matrix_only = QUAD;
     __device__ void load() {}
     typedef KktDualPre<T, QUAD> Pre;
-    __device__ Pre pre(int j) const
-    {
-        if constexpr (QUAD) return Pre{c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1, diag.p[j]};
-        else return Pre{c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1};
-    }
+    __device__ Pre pre(int j) const { return Pre{c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1, diag.at(j)}; }
     __device__ void operator()(int j, T kty, double* acc) const { (*this)(j, kty, pre(j), acc); }
     __device__ void operator()(int j, T kty, const Pre& p, double* acc) const
     {
         if (kty_out) kty_out[j] = kty;
-        T cj = p.cj, lo = p.lo, hi = p.hi, xj = p.xj;
-        T g = cj - kty;
-        [[maybe_unused]] double hq = 0.0;
-        if constexpr (QUAD) { g = (cj + p.qd * xj) - kty; hq = quad_half(p.qd, xj); }
-        if (UNSCALE) {            // K_u'(D_row y) = (K_s'y)/D_col, c_u = c_s/D_col, l_u = l_s D_col, x_u = D_col x
-            const T d = p.d;
-            g = g / d; cj = cj / d; lo = lo * d; hi = hi * d; xj = xj * d;
-        }
-        const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
-        T lam;
-        if (ninf && pinf) lam = (T)0;
-        else if (ninf) lam = g < (T)0 ? g : (T)0;
-        else if (pinf) lam = g > (T)0 ? g : (T)0;
-        else lam = g;
-        const T ld = ninf ? (T)0 : lo, ud = pinf ? (T)0 : hi;
-        const T r = g - lam;
-        acc[0] += (double)r * (double)r;
-        acc[1] += (double)ld * (double)(lam > (T)0 ? lam : (T)0);
-        acc[2] += (double)ud * (double)(lam < (T)0 ? lam : (T)0);
-        acc[3] += (double)cj * (double)xj;
-        if constexpr (QUAD) { acc[1] -= hq; acc[3] += hq; }     // (own additions: with d = 0 the sums are the linear ones bit for bit)
+        col_sums<T, UNSCALE, QUAD>(kty, p, acc);
     }
 };
 
 // KKT, primal side (helpers.py:77,87-91).  Optionally keeps K x for the adaptive step's cache.
 // Two-sided rows (RANGED): the upper violation max(k - q_upper, 0) joins the lower one min(k - q, 0) in acc[0] (0 for +inf), and the
 // dual objective takes q_upper_i y_i where y_i < 0 on a row with a finite q_upper (the upper side is the active one).
-template <typename T, bool RANGED> struct KktPrimalPre { T qi, yi, d; };
-template <typename T> struct KktPrimalPre<T, true> { T qi, yi, d, qu; };
+template <typename T, bool RANGED> struct KktPrimalPre { T qi, yi, d; [[no_unique_address]] Opt<T, RANGED> qu; };
+static_assert(sizeof(KktPrimalPre<float, false>) == 3 * 4 && sizeof(KktPrimalPre<double, true>) == 4 * 8, "operands only");
 // the two sums of a constraint row from r = k - q and ru = k - q_upper (RANGED), after UNSCALE has divided them
 template <typename T, bool RANGED>
 __device__ __forceinline__ void row_sums(int i, int ineq_end, T r, T ru, T qi, T qu, T yi, double* acc)
@@ -324,12 +374,12 @@ template <typename T, bool UNSCALE, bool RANGED = false> struct KktPrimalEpi {
     static constexpr int NA = 2;
     const T* y; const T* q; const T* drow; T* kx_out; int ineq_end;
     [[no_unique_address]] RowUpper<T, RANGED> upper{};
+    static constexpr bool working_matrix_only = RANGED;
     __device__ void load() {}
     typedef KktPrimalPre<T, RANGED> Pre;
     __device__ Pre pre(int i) const
     {
-        if constexpr (RANGED) return Pre{q[i], y[i], UNSCALE ? drow[i] : (T)1, upper.p[i]};
-        else return Pre{q[i], y[i], UNSCALE ? drow[i] : (T)1};
+        return Pre{q[i], y[i], UNSCALE ? drow[i] : (T)1, upper.at(i)};
     }
     __device__ void operator()(int i, T kx, double* acc) const { (*this)(i, kx, pre(i), acc); }
     __device__ void operator()(int i, T kx, const Pre& p, double* acc) const
@@ -357,44 +407,16 @@ template <typename T, bool UNSCALE, bool QUAD = false> struct ReportDualEpi {
     T* buf; const T* x; const T* c; const T* l; const T* u; const T* dcol;
     [[no_unique_address]] ObjDiag<T, QUAD> diag{};
     __device__ void load() {}
-    struct Pre { T kty; typename KktDualEpi<T, UNSCALE, QUAD>::Pre kp; };
-    __device__ Pre pre(int j) const
-    {
-        if constexpr (QUAD) return Pre{buf[j], {c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1, diag.p[j]}};
-        else return Pre{buf[j], {c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1}};
-    }
+    struct Pre { T kty; KktDualPre<T, QUAD> kp; };
+    __device__ Pre pre(int j) const { return Pre{buf[j], {c[j], l[j], u[j], x[j], UNSCALE ? dcol[j] : (T)1, diag.at(j)}}; }
     __device__ void operator()(int j, T, double* acc) const { (*this)(j, (T)0, pre(j), acc); }
-    __device__ void operator()(int j, T, const Pre& p, double* acc) const
-    {
-        T cj = p.kp.cj, lo = p.kp.lo, hi = p.kp.hi, xj = p.kp.xj;
-        T g = cj - p.kty;
-        [[maybe_unused]] double hq = 0.0;
-        if constexpr (QUAD) { g = (cj + p.kp.qd * xj) - p.kty; hq = quad_half(p.kp.qd, xj); }
-        if (UNSCALE) {
-            const T d = p.kp.d;
-            g = g / d; cj = cj / d; lo = lo * d; hi = hi * d; xj = xj * d;
-        }
-        const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
-        T lam;
-        if (ninf && pinf) lam = (T)0;
-        else if (ninf) lam = g < (T)0 ? g : (T)0;
-        else if (pinf) lam = g > (T)0 ? g : (T)0;
-        else lam = g;
-        buf[j] = lam;
-        const T ld = ninf ? (T)0 : lo, ud = pinf ? (T)0 : hi;
-        const T r = g - lam;
-        acc[0] += (double)r * (double)r;
-        acc[1] += (double)ld * (double)(lam > (T)0 ? lam : (T)0);
-        acc[2] += (double)ud * (double)(lam < (T)0 ? lam : (T)0);
-        acc[3] += (double)cj * (double)xj;
-        if constexpr (QUAD) { acc[1] -= hq; acc[3] += hq; }     // (own additions: with d = 0 the sums are the linear ones bit for bit)
-    }
+    __device__ void operator()(int j, T, const Pre& p, double* acc) const { col_sums<T, UNSCALE, QUAD, true>(p.kty, p.kp, acc, buf, j); }
 };
 
 // Solution report, constraint side: the same after K x stored into `buf`.  The sums of KktPrimalEpi (helpers.py:77,87-91); buf[i]
 // keeps the row activity (K x)_i -- UNSCALE: act_u = (K_s x_s) / D_row.
-template <typename T, bool RANGED> struct ReportPrimalPre { T kx, qi, yi, d; };
-template <typename T> struct ReportPrimalPre<T, true> { T kx, qi, yi, d, qu; };
+template <typename T, bool RANGED> struct ReportPrimalPre { T kx, qi, yi, d; [[no_unique_address]] Opt<T, RANGED> qu; };
+static_assert(sizeof(ReportPrimalPre<float, false>) == 4 * 4 && sizeof(ReportPrimalPre<double, true>) == 5 * 8, "operands only");
 template <typename T, bool UNSCALE, bool RANGED = false> struct ReportPrimalEpi {
     static constexpr int NA = 2;
     T* buf; const T* y; const T* q; const T* drow; int ineq_end;
@@ -403,8 +425,7 @@ template <typename T, bool UNSCALE, bool RANGED = false> struct ReportPrimalEpi 
     typedef ReportPrimalPre<T, RANGED> Pre;
     __device__ Pre pre(int i) const
     {
-        if constexpr (RANGED) return Pre{buf[i], q[i], y[i], UNSCALE ? drow[i] : (T)1, upper.p[i]};
-        else return Pre{buf[i], q[i], y[i], UNSCALE ? drow[i] : (T)1};
+        return Pre{buf[i], q[i], y[i], UNSCALE ? drow[i] : (T)1, upper.at(i)};
     }
     __device__ void operator()(int i, T, double* acc) const { (*this)(i, (T)0, pre(i), acc); }
     __device__ void operator()(int i, T, const Pre& p, double* acc) const
@@ -436,12 +457,10 @@ template <typename T> struct InfeasDualEpi {
     {
         const T cj = c[j], lo = l[j], hi = u[j];
         const T g = cj - kty;
+        // (the classes formed here and not by project_lambda(g, lo, hi): isinf(lo) and isinf(hi) are read again below, and with the
+        // classes folded inside the shared function this functor's kernels come out with other instructions)
         const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
-        T lam;
-        if (ninf && pinf) lam = (T)0;
-        else if (ninf) lam = g < (T)0 ? g : (T)0;
-        else if (pinf) lam = g > (T)0 ? g : (T)0;
-        else lam = g;
+        const T lam = project_lambda(g, ninf, pinf);
         const T dlam = lam - lam_prev[j];                                    // :110
         lam_prev[j] = lam;                                                   // pdhg.py:101
         const T r = ktdy[j] - dlam;                                          // :146
@@ -509,9 +528,7 @@ template <bool ADAPT, bool PEER = false> struct DeltaPrimalEpi {
         const double ky = p.ky + (double)s;
         kty[j] = ky;
         const double xo = p.xo;
-        double v = xo - tau * (p.cj - ky);
-        v = v < p.lo ? p.lo : v;
-        v = v > p.hi ? p.hi : v;
+        const double v = primal_step(xo, tau, p.cj, ky, p.lo, p.hi);
         const double d = v - xo;
         x_new[j] = v;
         gdx[j] = (float)d;
@@ -545,8 +562,7 @@ template <bool ADAPT, bool PEER = false> struct DeltaDualEpi {
     {
         const double kdx = (double)s;
         const double yo = p.yo;
-        double v = yo + sigma * (p.qi - (p.kxo + onept * kdx));
-        if (i < ineq_end && v < 0.0) v = 0.0;
+        const double v = dual_step(i, ineq_end, yo, sigma, p.qi, p.kxo + onept * kdx);
         y_new[i] = v;
         const double dy = v - yo;
         gdy[i] = (float)dy;

@@ -8,7 +8,7 @@
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-template <typename T> int halpern_iterate_t(pdlp_handle h, int iters)
+template <typename T, bool RANGED, bool QUAD> int halpern_iterate_e(pdlp_handle h, int iters)
 {
     int rc;
     for (int it = 0; it < iters; ++it) {
@@ -16,31 +16,26 @@ template <typename T> int halpern_iterate_t(pdlp_handle h, int iters)
         const double t2 = (double)(h->since_reset + 2);
         const T a = (T)((double)(h->since_reset + 1) / t2), b = (T)(1.0 / t2);
         const int cur = h->ix_cur, nxt = h->ix_prev, cand = h->ix_avg;
-        if (h->obj_diag) {         // diagonal quadratic objective (pdlp_set_objective_diag)
-            HalpernPrimalEpi<T, true> ep{xloc<T>(h, cur), xloc<T>(h, nxt), (T*)h->xbar + h->p.col0, xloc<T>(h, cand), (const T*)h->x_last,
-                                         (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, h->sc, a, b};
-            ep.diag.p = (const T*)h->obj_diag;
-            if ((rc = launch_mat<T, T>(h, true, h->yb[cur], ep, h->partA)) != PDLP_OK) return rc;
-        } else {
-            HalpernPrimalEpi<T> ep{xloc<T>(h, cur), xloc<T>(h, nxt), (T*)h->xbar + h->p.col0, xloc<T>(h, cand), (const T*)h->x_last,
-                                   (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, h->sc, a, b};
-            if ((rc = launch_csr<T>(h, true, h->yb[cur], ep, h->partA)) != PDLP_OK) return rc;
-        }
-        if (h->q_upper) {          // two-sided rows (pdlp_set_row_upper)
-            HalpernDualEpi<T, true> ed{yloc<T>(h, cur), yloc<T>(h, nxt), yloc<T>(h, cand), (const T*)h->y_last, (const T*)h->p.q, h->sc,
-                                       h->ineq_end, a, b};
-            ed.upper.p = (const T*)h->q_upper;
-            if ((rc = launch_mat<T, T>(h, false, h->xbar, ed, h->partB)) != PDLP_OK) return rc;
-        } else {
-            HalpernDualEpi<T> ed{yloc<T>(h, cur), yloc<T>(h, nxt), yloc<T>(h, cand), (const T*)h->y_last, (const T*)h->p.q, h->sc,
-                                 h->ineq_end, a, b};
-            if ((rc = launch_csr<T>(h, false, h->xbar, ed, h->partB)) != PDLP_OK) return rc;
-        }
+        // QUAD: diagonal quadratic objective (pdlp_set_objective_diag); RANGED: two-sided rows (pdlp_set_row_upper)
+        HalpernPrimalEpi<T, QUAD> ep{xloc<T>(h, cur), xloc<T>(h, nxt), (T*)h->xbar + h->p.col0, xloc<T>(h, cand), (const T*)h->x_last,
+                                     (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, h->sc, a, b};
+        set_optional(ep.diag, h);
+        if ((rc = launch_csr<T>(h, true, h->yb[cur], ep, h->partA)) != PDLP_OK) return rc;
+        HalpernDualEpi<T, RANGED> ed{yloc<T>(h, cur), yloc<T>(h, nxt), yloc<T>(h, cand), (const T*)h->y_last, (const T*)h->p.q, h->sc,
+                                     h->ineq_end, a, b};
+        set_optional(ed.upper, h);
+        if ((rc = launch_csr<T>(h, false, h->xbar, ed, h->partB)) != PDLP_OK) return rc;
         h->ix_cur = nxt;           // the freshly written z becomes current; the old z's buffers are the next iteration's target
         h->ix_prev = cur;
         ++h->since_reset;
     }
     return PDLP_OK;
+}
+
+template <typename T> int halpern_iterate_t(pdlp_handle h, int iters)
+{
+    return with_flags([&](auto R, auto Q) { return halpern_iterate_e<T, R.value, Q.value>(h, iters); }, h->q_upper != nullptr,
+                      h->obj_diag != nullptr);
 }
 
 // The fixed-point residual of the last iteration: z = PDLP_PREV, T(z) = PDLP_AVG.  One vector pass (dy into the detector's full-length
@@ -63,7 +58,7 @@ template <typename T> int halpern_fixed_point_t(pdlp_handle h)
 // the forms the Halpern mode does not have: mixed precision / delta mode, a shard of a problem, an exchange of any kind, graph replay
 inline bool halpern_refused(pdlp_handle h)
 {
-    return h->mixed || h->delta || h->nl != h->p.n || h->ml != h->p.m || h->comm || h->peer.on || h->graph_ok;
+    return !plain_single(h) || h->graph_ok;
 }
 
 }  // namespace

@@ -169,6 +169,14 @@ struct pdlp_solver {
 
 namespace {
 
+// what the PDLP_ERR_STATE guards of the entry points ask of a handle
+inline bool whole_problem(pdlp_handle h) { return h->nl == h->p.n && h->ml == h->p.m; }        // all of the LP on this GPU, not a shard
+inline bool plain_single(pdlp_handle h)         // ... in one precision and outside every exchange: the only form the extensions have
+{
+    return whole_problem(h) && !h->mixed && !h->delta && !h->comm && !h->peer.on;
+}
+inline bool has_extension(pdlp_handle h) { return h->q_upper || h->obj_diag; }    // two-sided rows or a quadratic objective
+
 void drop_graphs(pdlp_handle h)
 {
     for (auto& g : h->graphs) {

@@ -374,7 +374,7 @@ int pdlp_set_row_upper(pdlp_handle h, const void* q_upper_local)
 {
     if (!h) return PDLP_ERR_INVALID;
     // forms without two-sided rows: mixed precision / delta mode, a shard of a problem, an exchange of any kind
-    if (q_upper_local && (h->mixed || h->delta || h->nl != h->p.n || h->ml != h->p.m || h->comm || h->peer.on)) return PDLP_ERR_STATE;
+    if (q_upper_local && !plain_single(h)) return PDLP_ERR_STATE;
     if (h->sK.pending || h->sKT.pending) return PDLP_ERR_STATE;       // not in the middle of a split product
     drop_graphs(h);               // captured launches hold the functors without (or with the old) q_upper
     h->q_upper = q_upper_local;
@@ -389,7 +389,7 @@ int pdlp_set_objective_diag(pdlp_handle h, const void* d_local)
     if (!h) return PDLP_ERR_INVALID;
     // forms without the quadratic term: mixed precision / delta mode, a shard of a problem, an exchange of any kind.  (This is also
     // what keeps pdlp_set_delta(on) away from the term: it asks for a PDLP_MIXED handle, which can never have d set.)
-    if (d_local && (h->mixed || h->delta || h->nl != h->p.n || h->ml != h->p.m || h->comm || h->peer.on)) return PDLP_ERR_STATE;
+    if (d_local && !plain_single(h)) return PDLP_ERR_STATE;
     if (h->sK.pending || h->sKT.pending) return PDLP_ERR_STATE;       // not in the middle of a split product
     drop_graphs(h);               // captured launches hold the functors without (or with the old) d
     h->obj_diag = d_local;
@@ -603,7 +603,7 @@ int pdlp_iterate(pdlp_handle h, int iters, int adaptive)
     Range range(rname, h->stream);
     if (h->peer.on && h->peer.enabled) return iterate_peer(h, iters, adaptive);
     if (h->comm) return iterate_sharded(h, iters, adaptive);
-    if (h->nl != h->p.n || h->ml != h->p.m) return PDLP_ERR_STATE;   // sharded without a communicator: the caller does the exchange
+    if (!whole_problem(h)) return PDLP_ERR_STATE;   // sharded without a communicator: the caller does the exchange
     return iterate_single(h, iters, adaptive);
 }
 
@@ -690,14 +690,14 @@ int pdlp_infeas_reset(pdlp_handle h)
 int pdlp_infeas_begin(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->q_upper || h->obj_diag) return PDLP_ERR_STATE;       // (the detector's tests know one-sided rows and a linear objective only)
+    if (has_extension(h)) return PDLP_ERR_STATE;       // (the detector's tests know one-sided rows and a linear objective only)
     return DISPATCH(h, infeas_begin_t, h);
 }
 
 int pdlp_infeas_local(pdlp_handle h, double tol)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->q_upper || h->obj_diag) return PDLP_ERR_STATE;
+    if (has_extension(h)) return PDLP_ERR_STATE;
     return DISPATCH(h, infeas_local_t, h, tol);
 }
 
@@ -715,21 +715,21 @@ int pdlp_infeas_finish(pdlp_handle h, double tol, int32_t* status, double diag[8
 int pdlp_mv_steps(pdlp_handle h, int nvp, int steps, double eta, double omega, double theta, void* X, void* Y, void* work)
 {
     if (!h || !X || !Y || !work || steps < 0 || (nvp != 8 && nvp != 16 && nvp != 32)) return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper || h->obj_diag) return PDLP_ERR_STATE;   // (one-sided rows, linear objective)
+    if (!whole_problem(h) || h->mixed || has_extension(h)) return PDLP_ERR_STATE;   // (one-sided rows, linear objective)
     return DISPATCH(h, mv_steps_t, h, nvp, steps, eta, omega, theta, X, Y, work);
 }
 
 int pdlp_mv_gap(pdlp_handle h, int nvp, const void* X, const void* Y, void* work, double* gaps)
 {
     if (!h || !X || !Y || !work || !gaps || (nvp != 8 && nvp != 16 && nvp != 32)) return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper || h->obj_diag) return PDLP_ERR_STATE;   // (one-sided rows, linear objective)
+    if (!whole_problem(h) || h->mixed || has_extension(h)) return PDLP_ERR_STATE;   // (one-sided rows, linear objective)
     return DISPATCH(h, mv_gap_t, h, nvp, X, Y, work, gaps);
 }
 
 int pdlp_mv_product(pdlp_handle h, int nvp, const void* X, void* Y)
 {
     if (!h || !X || !Y || (nvp != 8 && nvp != 16 && nvp != 32)) return PDLP_ERR_INVALID;
-    if (h->nl != h->p.n || h->ml != h->p.m || h->mixed || h->q_upper || h->obj_diag) return PDLP_ERR_STATE;   // (one-sided rows, linear objective)
+    if (!whole_problem(h) || h->mixed || has_extension(h)) return PDLP_ERR_STATE;   // (one-sided rows, linear objective)
     return DISPATCH(h, mv_product_t, h, nvp, X, Y);
 }
 
@@ -743,7 +743,7 @@ int pdlp_power_iteration(pdlp_handle h, const void* b0, int iters, void* work_n,
 {
     if (!h || !b0 || !work_n || !work_m || !sigma || iters < 0) return PDLP_ERR_INVALID;
     Range range("pdlp: power iteration", h->stream);
-    if (h->nl != h->p.n || h->ml != h->p.m) return PDLP_ERR_STATE;
+    if (!whole_problem(h)) return PDLP_ERR_STATE;
     return DISPATCH(h, power_iteration_t, h, b0, iters, work_n, work_m, sigma);
 }
 

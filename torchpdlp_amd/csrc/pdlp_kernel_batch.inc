@@ -69,10 +69,7 @@ template <typename T, bool ADAPT> struct BPrimal {
         const T xo = X[at];
         if (ADAPT) Xsum[at] = Xsum[at] + wpend[b] * xo;
         const T tau = eta[b] / omega[b];
-        T v = xo - tau * (BCOL(c, cs, j, at) - kty);
-        const T lo = BCOL(l, ls, j, at), hi = BCOL(u, us, j, at);
-        v = v < lo ? lo : v;
-        v = v > hi ? hi : v;
+        const T v = primal_step(xo, tau, BCOL(c, cs, j, at), kty, BCOL(l, ls, j, at), BCOL(u, us, j, at));
         X[at] = v;
         Xprev[at] = xo;
         Xbar[at] = v + (v - xo);                       // theta = 1 (pdhg.py:27)
@@ -90,8 +87,7 @@ template <typename T, bool ADAPT> struct BDual {
         const T yo = Y[at];
         if (ADAPT) Ysum[at] = Ysum[at] + wpend[b] * yo;
         const T sigma = eta[b] * omega[b];
-        T v = yo + sigma * (BCOL(q, qs, i, at) - kx);
-        if (i < ineq_end && v < (T)0) v = (T)0;
+        const T v = dual_step(i, ineq_end, yo, sigma, BCOL(q, qs, i, at), kx);
         Y[at] = v;
         Yprev[at] = yo;
         if (!ADAPT) {
@@ -131,10 +127,7 @@ template <typename T> struct BHalpernPrimal {
         w(b, a, bw);                                  // before the first store: the load of t_since and the divisions overlap the others
         const T xo = X[at], xl = Xlast[at];
         const T tau = eta[b] / omega[b];
-        T v = xo - tau * (BCOL(c, cs, j, at) - kty);
-        const T lo = BCOL(l, ls, j, at), hi = BCOL(u, us, j, at);
-        v = v < lo ? lo : v;
-        v = v > hi ? hi : v;
+        const T v = primal_step(xo, tau, BCOL(c, cs, j, at), kty, BCOL(l, ls, j, at), BCOL(u, us, j, at));
         Xcand[at] = v;
         const T xb = v + (v - xo);
         Xbar[at] = xb;
@@ -153,8 +146,7 @@ template <typename T> struct BHalpernDual {
         w(b, a, bw);                                  // (as in the primal half)
         const T yo = Y[at], yl = Ylast[at];
         const T sigma = eta[b] * omega[b];
-        T v = yo + sigma * (BCOL(q, qs, i, at) - kx);
-        if (i < ineq_end && v < (T)0) v = (T)0;
+        const T v = dual_step(i, ineq_end, yo, sigma, BCOL(q, qs, i, at), kx);
         Ycand[at] = v;
         Y[at] = a * ((T)2 * v - yo) + bw * yl;
     }
@@ -187,13 +179,8 @@ template <typename T, bool UNSCALE> struct BKktDual {
             const T d = BCOL(dcol, dper, j, at);
             g = g / d; lo = lo * d; hi = hi * d;
         }
-        const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
-        T lam;
-        if (ninf && pinf) lam = (T)0;
-        else if (ninf) lam = g < (T)0 ? g : (T)0;
-        else if (pinf) lam = g > (T)0 ? g : (T)0;
-        else lam = g;
-        return {g, lam, ninf ? (T)0 : lo, pinf ? (T)0 : hi};
+        const BoxLam<T> b = project_lambda(g, lo, hi);
+        return {g, b.lam, b.ninf ? (T)0 : lo, b.pinf ? (T)0 : hi};
     }
     __device__ void operator()(int j, size_t at, int, int, T kty, double* acc) const
     {

@@ -14,10 +14,7 @@ template <typename T> struct PrimalMV {          // PDHG_step :277-284: x+ = cla
     __device__ void operator()(int j, size_t at, T kty, double*) const
     {
         const T xo = X[at];
-        T v = xo - tau * (c[j] - kty);
-        const T lo = l[j], hi = u[j];
-        v = v < lo ? lo : v;
-        v = v > hi ? hi : v;
+        const T v = primal_step(xo, tau, c[j], kty, l[j], u[j]);
         Xnew[at] = v;
         Xbar[at] = v + theta * (v - xo);
     }
@@ -28,8 +25,7 @@ template <typename T> struct DualMV {            // PDHG_step :287-292: y+ = y +
     const T* Y; T* Ynew; const T* q; T sigma; int ineq_end;
     __device__ void operator()(int i, size_t at, T kxbar, double*) const
     {
-        T v = Y[at] + sigma * (q[i] - kxbar);
-        if (i < ineq_end && v < (T)0) v = (T)0;
+        const T v = dual_step(i, ineq_end, Y[at], sigma, q[i], kxbar);
         Ynew[at] = v;
     }
 };
@@ -46,12 +42,11 @@ template <typename T> struct GapMV {             // get_best_pts :222-233: c'x, 
     __device__ void operator()(int j, size_t at, T kty, double* acc) const
     {
         const T cj = c[j], lo = l[j], hi = u[j];
-        const T g = cj - kty;
-        const bool ninf = isinf(lo) && lo < (T)0, pinf = isinf(hi) && hi > (T)0;
-        const T lam = (ninf && pinf) ? (T)0 : (ninf ? (g < (T)0 ? g : (T)0) : (pinf ? (g > (T)0 ? g : (T)0) : g));
+        const BoxLam<T> b = project_lambda(cj - kty, lo, hi);
+        const T lam = b.lam;
         acc[0] += (double)cj * (double)X[at];
-        acc[1] += (double)(ninf ? (T)0 : lo) * (double)(lam > (T)0 ? lam : (T)0);
-        acc[2] += (double)(pinf ? (T)0 : hi) * (double)(lam < (T)0 ? lam : (T)0);
+        acc[1] += (double)(b.ninf ? (T)0 : lo) * (double)(lam > (T)0 ? lam : (T)0);
+        acc[2] += (double)(b.pinf ? (T)0 : hi) * (double)(lam < (T)0 ? lam : (T)0);
     }
 };
 

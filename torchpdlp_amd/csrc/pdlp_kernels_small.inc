@@ -287,7 +287,8 @@ __global__ __launch_bounds__(BLOCK) void k_average(int64_t n, T* __restrict__ av
 
 __global__ void k_clear_pending(double* sc) { sc[S_WPEND] = 0.0; }
 
-// lam = project_lambda_box(g) (helpers.py:21-37) with the bound classes read off l, u
+// lam = project_lambda_box(g) (helpers.py:21-37) with the bound classes read off l, u.  project_lambda's arithmetic, written out as
+// one expression: called here, the vectorised float32 loop of this kernel comes out with other selects.
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_project_lambda(int64_t n, const T* __restrict__ g, const T* __restrict__ l,
                                                           const T* __restrict__ u, T* __restrict__ out)

@@ -6,38 +6,31 @@
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-// the constraint side's functors of a KKT pass / a report, with q_upper when the handle has two-sided rows (RANGED), and their
-// product with K: a handle with two-sided rows is never in mixed precision, so its matrix has the working type
+// the functors of a KKT pass and of a report: the constraint side with q_upper when the handle has two-sided rows (RANGED), the
+// variable side with d when it has a diagonal quadratic objective (QUAD)
 template <typename T, bool UNSCALE, bool RANGED> KktPrimalEpi<T, UNSCALE, RANGED> kkt_primal_epi(pdlp_handle h, int ix, const T* drow, T* kx_out)
 {
     KktPrimalEpi<T, UNSCALE, RANGED> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, kx_out, h->ineq_end};
-    if constexpr (RANGED) ep.upper.p = (const T*)h->q_upper;
+    set_optional(ep.upper, h);
     return ep;
 }
-template <typename T, bool RANGED, class Epi> int launch_rows(pdlp_handle h, const void* vin, Epi e, double* partials)
-{
-    if constexpr (RANGED) return launch_mat<T, T>(h, false, vin, e, partials);
-    else return launch_csr<T>(h, false, vin, e, partials);
-}
-
-// the variable side's functor of a KKT pass, with d when the handle has a diagonal quadratic objective (QUAD), and its product with
-// K': such a handle is never in mixed precision either
 template <typename T, bool UNSCALE, bool QUAD> KktDualEpi<T, UNSCALE, QUAD> kkt_dual_epi(pdlp_handle h, int ix, const T* dcol, T* kty_out)
 {
     KktDualEpi<T, UNSCALE, QUAD> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, kty_out};
-    if constexpr (QUAD) ed.diag.p = (const T*)h->obj_diag;
+    set_optional(ed.diag, h);
     return ed;
 }
-template <typename T, bool QUAD, class Epi> int launch_cols(pdlp_handle h, const void* vin, Epi e, double* partials)
+template <typename T, bool UNSCALE, bool RANGED> ReportPrimalEpi<T, UNSCALE, RANGED> report_primal_epi(pdlp_handle h, int ix, const T* drow, T* buf)
 {
-    if constexpr (QUAD) return launch_mat<T, T>(h, true, vin, e, partials);
-    else return launch_csr<T>(h, true, vin, e, partials);
+    ReportPrimalEpi<T, UNSCALE, RANGED> ep{buf, yloc<T>(h, ix), (const T*)h->p.q, drow, h->ineq_end};
+    set_optional(ep.upper, h);
+    return ep;
 }
-// f(RANGED, QUAD) with the handle's two problem-class switches as types
-template <class F> int with_ranged_quad(pdlp_handle h, F f)
+template <typename T, bool UNSCALE, bool QUAD> ReportDualEpi<T, UNSCALE, QUAD> report_dual_epi(pdlp_handle h, int ix, const T* dcol, T* buf)
 {
-    if (h->obj_diag) return h->q_upper ? f(std::true_type{}, std::true_type{}) : f(std::false_type{}, std::true_type{});
-    return h->q_upper ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{});
+    ReportDualEpi<T, UNSCALE, QUAD> ed{buf, xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol};
+    set_optional(ed.diag, h);
+    return ed;
 }
 
 template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int kkt_local_u(pdlp_handle h, int which)
@@ -61,7 +54,7 @@ template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int 
         T* kty_out = which == PDLP_CUR ? (T*)h->ktyb[0] : (which == PDLP_AVG ? (T*)h->ktyb[1] : nullptr);
         if (which == PDLP_CUR || (which == PDLP_AVG && h->kty_cur == 1)) h->kty_cur = -1;     // (the copy about to be overwritten)
         const auto ed = kkt_dual_epi<T, UNSCALE, QUAD>(h, ix, dcol, kty_out);
-        if ((rc = launch_cols<T, QUAD>(h, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
+        if ((rc = launch_csr<T>(h, true, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
         if (which == PDLP_CUR && h->kx_valid && !h->no_running) {
             // K x of the current iterate is carried along by the dual half-steps (kxb[0]): no product
             const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, nullptr);
@@ -70,7 +63,7 @@ template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int 
             h->cur_kx_cached = true;
         } else {
             const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, kx_out);
-            if ((rc = launch_rows<T, RANGED>(h, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
+            if ((rc = launch_csr<T>(h, false, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
             if (which == PDLP_CUR) h->cur_kx_cached = false;
         }
     }
@@ -81,13 +74,9 @@ template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int 
 
 template <typename T> int kkt_local_t(pdlp_handle h, int which, int unscaled)
 {
-    if (h->obj_diag)       // (a handle may have two-sided rows and the quadratic term)
-        return with_ranged_quad(h, [&](auto R, auto Q) {
-            return unscaled ? kkt_local_u<T, true, decltype(R)::value, decltype(Q)::value>(h, which)
-                            : kkt_local_u<T, false, decltype(R)::value, decltype(Q)::value>(h, which);
-        });
-    if (h->q_upper) return unscaled ? kkt_local_u<T, true, true>(h, which) : kkt_local_u<T, false, true>(h, which);
-    return unscaled ? kkt_local_u<T, true>(h, which) : kkt_local_u<T, false>(h, which);
+    // (a handle may have two-sided rows and the quadratic term)
+    return with_flags([&](auto U, auto R, auto Q) { return kkt_local_u<T, U.value, R.value, Q.value>(h, which); }, unscaled,
+                      h->q_upper != nullptr, h->obj_diag != nullptr);
 }
 
 // Solution report (pdlp_report_local): reduced costs and row activities of an iterate stored, with the six KKT sums.  The two
@@ -105,38 +94,30 @@ template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int 
     if (rc_local) {
         StoreEpi<T> st{(T*)rc_local};
         if ((rc = launch_csr<T>(h, true, h->yb[ix], st, h->partA)) != PDLP_OK) return rc;
-        ReportDualEpi<T, UNSCALE, QUAD> ed{(T*)rc_local, xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol};
-        if constexpr (QUAD) ed.diag.p = (const T*)h->obj_diag;
+        const auto ed = report_dual_epi<T, UNSCALE, QUAD>(h, ix, dcol, (T*)rc_local);
         if ((rc = epilogue_pass<T>(h, h->nl, nullptr, ed, h->partA)) != PDLP_OK) return rc;
         gridA = rows_grid(h->nl);
     } else {
         const auto ed = kkt_dual_epi<T, UNSCALE, QUAD>(h, ix, dcol, nullptr);
-        if ((rc = launch_cols<T, QUAD>(h, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
+        if ((rc = launch_csr<T>(h, true, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
     }
     if (act_local) {
         StoreEpi<T> st{(T*)act_local};
         if ((rc = launch_csr<T>(h, false, h->xb[ix], st, h->partB)) != PDLP_OK) return rc;
-        ReportPrimalEpi<T, UNSCALE, RANGED> ep{(T*)act_local, yloc<T>(h, ix), (const T*)h->p.q, drow, h->ineq_end};
-        if constexpr (RANGED) ep.upper.p = (const T*)h->q_upper;
+        const auto ep = report_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, (T*)act_local);
         if ((rc = epilogue_pass<T>(h, h->ml, nullptr, ep, h->partB)) != PDLP_OK) return rc;
         gridB = rows_grid(h->ml);
     } else {
         const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, nullptr);
-        if ((rc = launch_rows<T, RANGED>(h, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
+        if ((rc = launch_csr<T>(h, false, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
     }
     return finalize_kkt(h, gridA, gridB);
 }
 
 template <typename T> int report_local_t(pdlp_handle h, int which, int unscaled, void* rc_local, void* act_local)
 {
-    if (h->obj_diag)
-        return with_ranged_quad(h, [&](auto R, auto Q) {
-            return unscaled ? report_local_u<T, true, decltype(R)::value, decltype(Q)::value>(h, which, rc_local, act_local)
-                            : report_local_u<T, false, decltype(R)::value, decltype(Q)::value>(h, which, rc_local, act_local);
-        });
-    if (h->q_upper)
-        return unscaled ? report_local_u<T, true, true>(h, which, rc_local, act_local) : report_local_u<T, false, true>(h, which, rc_local, act_local);
-    return unscaled ? report_local_u<T, true>(h, which, rc_local, act_local) : report_local_u<T, false>(h, which, rc_local, act_local);
+    return with_flags([&](auto U, auto R, auto Q) { return report_local_u<T, U.value, R.value, Q.value>(h, which, rc_local, act_local); },
+                      unscaled, h->q_upper != nullptr, h->obj_diag != nullptr);
 }
 
 template <typename T> void kkt_finish_t(const double* r, double omega_d, double* out)

@@ -177,7 +177,7 @@ extern "C" {
 int pdlp_peer_export(pdlp_handle h, void* info)
 {
     if (!h || !info) return PDLP_ERR_INVALID;
-    if (h->nl == h->p.n && h->ml == h->p.m) return PDLP_ERR_STATE;              // not sharded: nothing to exchange
+    if (whole_problem(h)) return PDLP_ERR_STATE;              // not sharded: nothing to exchange
     HIP_TRY(hipSetDevice(h->p.device));
     int rc;
     if ((rc = peer_own_resources(h)) != PDLP_OK) return rc;
@@ -207,7 +207,7 @@ int pdlp_peer_connect(pdlp_handle h, int rank, int world, const void* infos, int
     if (!h || world < 2 || world > MAX_PEER + 1 || rank < 0 || rank >= world) return PDLP_ERR_INVALID;
     if (h->nl * world != h->p.n || h->ml * world != h->p.m || h->p.col0 != (int64_t)rank * h->nl || h->p.row0 != (int64_t)rank * h->ml)
         return PDLP_ERR_INVALID;                   // equal blocks, this rank's at rank * block (torchpdlp_amd/distributed.py)
-    if (h->q_upper || h->obj_diag) return PDLP_ERR_STATE;      // (two-sided rows and the quadratic term have no sharded form)
+    if (has_extension(h)) return PDLP_ERR_STATE;      // (two-sided rows and the quadratic term have no sharded form)
     const bool loopback = (flags & PDLP_PEER_LOOPBACK) != 0;
     if (!loopback && !infos) return PDLP_ERR_INVALID;
     HIP_TRY(hipSetDevice(h->p.device));

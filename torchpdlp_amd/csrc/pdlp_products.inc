@@ -1,7 +1,7 @@
 // pdlp_products.inc -- the products and the half-steps.  launch_mat: one product with K or K' with a fused epilogue, in every form
 // (CSR row blocks, tiles in one launch, tiles in panel groups, a split product's phases and output pieces); launch_csr picks the
 // matrix type of the handle's precision.  Then the launches every later file shares (epilogue_pass, finalize_kkt, iterate_index,
-// launch_adaptive_rule, with_adapt_peer), the primal and dual half-steps, their early parts for sharded problems (half_begin_t,
+// launch_adaptive_rule, with_flags), the primal and dual half-steps, their early parts for sharded problems (half_begin_t,
 // half_chunk_t, half_piece) and the plain product (spmv_t).
 // Part of pdlp_hip.hip (included at file scope; not a translation unit of its own).  Needs: pdlp_schedule.inc and what is before it.
 // ------------------------------------------------------------------------------------------------
@@ -130,11 +130,18 @@ int launch_mat(pdlp_handle h, bool transpose, const void* vin, Epi epi, double* 
     return PDLP_OK;
 }
 
-// the product in the handle's working precision T (the matrix is float32 under float64 vectors in mixed precision)
+// A functor in its RANGED or QUAD form exists only over a matrix in the working type -- a handle with two-sided rows or a quadratic
+// objective is one GPU in one precision (pdlp_set_row_upper, pdlp_set_objective_diag) -- and says so itself (working_matrix_only
+// beside its optional operand, pdlp_epilogues.inc): no float32-matrix product is built for it.
+template <class Epi, class = void> struct working_matrix_only : std::false_type {};
+template <class Epi> struct working_matrix_only<Epi, std::void_t<decltype(Epi::working_matrix_only)>> : std::bool_constant<Epi::working_matrix_only> {};
+
+// the product in the handle's working precision T (the matrix is float32 under float64 vectors in mixed precision): the one place
+// that chooses the matrix type
 template <typename T, class Epi>
 int launch_csr(pdlp_handle h, bool transpose, const void* vin, Epi epi, double* partials)
 {
-    if constexpr (std::is_same<T, double>::value) {
+    if constexpr (std::is_same<T, double>::value && !working_matrix_only<Epi>::value) {
         if (h->mixed) return launch_mat<double, float, Epi>(h, transpose, vin, epi, partials);
     }
     return launch_mat<T, T, Epi>(h, transpose, vin, epi, partials);
@@ -207,31 +214,35 @@ inline void launch_adaptive_rule(pdlp_handle h, int advance)
                                           h->last_gridB, h->red, h->sc, advance));
 }
 
-// f(ADAPT, PEER) with the two switches of a half-step's epilogue as types (std::true_type / std::false_type): ADAPT = the sums of
-// the step-size rule, PEER = the stores into the other ranks' vectors (only inside the direct exchange: iterate_peer)
-template <class F> int with_adapt_peer(pdlp_handle h, int adaptive, F f)
+// f(flags...) with run-time switches as types (std::true_type / std::false_type), in the order given: with_flags(f, a, b) calls
+// f(A, B).  A call site passes exactly the switches that vary there, so it instantiates f for their combinations and no others.
+template <class F> int with_flags(F f) { return f(); }
+template <class F, class... Rest> int with_flags(F f, bool flag, Rest... rest)
 {
-    if (h->peer.active) return adaptive ? f(std::true_type{}, std::true_type{}) : f(std::false_type{}, std::true_type{});
-    return adaptive ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{});
+    return with_flags([&](auto... t) { return flag ? f(std::true_type{}, t...) : f(std::false_type{}, t...); }, rest...);
 }
 
+// the optional operand of a RANGED / QUAD functor (an empty member otherwise)
+template <typename T> void set_optional(RowUpper<T, true>& o, pdlp_handle h) { o.p = (const T*)h->q_upper; }
+template <typename T> void set_optional(ObjDiag<T, true>& o, pdlp_handle h) { o.p = (const T*)h->obj_diag; }
+template <typename T> void set_optional(RowUpper<T, false>&, pdlp_handle) {}
+template <typename T> void set_optional(ObjDiag<T, false>&, pdlp_handle) {}
+
 // QUAD: the handle has a diagonal quadratic objective (pdlp_set_objective_diag: float32 / float64, one GPU, no exchange -- so never
-// PEER, and the matrix has the working type)
+// PEER)
 template <typename T, bool ADAPT, bool PEER, bool QUAD = false> int primal_half_e(pdlp_handle h, int src, T* ksum, const PieceCtl& pc)
 {
     PrimalEpi<T, ADAPT, PEER, QUAD> e{xloc<T>(h, h->ix_cur), xloc<T>(h, h->ix_prev), (T*)h->xbar + h->p.col0, (const T*)h->p.c,
                                       (const T*)h->p.l, (const T*)h->p.u, (T*)h->x_sum, h->sc, ksum};
     peer_targets(h, e.peer, 0);
-    if constexpr (QUAD) e.diag.p = (const T*)h->obj_diag;
+    set_optional(e.diag, h);
     if (src >= 0) {     // the primal update from a K'y that a KKT pass at this very iterate left behind: no product, one vector kernel
         if (ADAPT) h->last_gridA = rows_grid(h->nl);
         return epilogue_pass<T>(h, h->nl, h->ktyb[src], e, h->partA);
     }
     if (ADAPT) h->last_gridA = grid_of(h->sKT, h->nl);
     h->use_split = true;
-    int rc;
-    if constexpr (QUAD) rc = launch_mat<T, T>(h, true, h->yb[h->ix_cur], e, h->partA);
-    else rc = launch_csr<T>(h, true, h->yb[h->ix_cur], e, h->partA);
+    const int rc = launch_csr<T>(h, true, h->yb[h->ix_cur], e, h->partA);
     h->use_split = false;
     if (pc.finish) h->sKT.pending = false;
     return rc;
@@ -248,9 +259,9 @@ template <typename T> int primal_half_t(pdlp_handle h, int adaptive)
     T* ksum = (h->since_reset > 0 && !h->kty_tail_done && !h->sums_broken && !h->no_running && !h->graph_ok) ? (T*)h->kty_sum : nullptr;
     const PieceCtl pc = piece_ctl(h, h->sKT, src < 0);
     if (pc.skip) return PDLP_OK;                             // (all of this half-step went out with piece 0)
-    if (h->obj_diag) return adaptive ? primal_half_e<T, true, false, true>(h, src, ksum, pc) : primal_half_e<T, false, false, true>(h, src, ksum, pc);
+    if (h->obj_diag) return with_flags([&](auto A) { return primal_half_e<T, A.value, false, true>(h, src, ksum, pc); }, adaptive);
     // (inside the direct exchange the epilogue also stores xbar into the peers: its own instantiations)
-    return with_adapt_peer(h, adaptive, [&](auto A, auto P) { return primal_half_e<T, decltype(A)::value, decltype(P)::value>(h, src, ksum, pc); });
+    return with_flags([&](auto A, auto P) { return primal_half_e<T, A.value, P.value>(h, src, ksum, pc); }, adaptive, h->peer.active);
 }
 
 template <typename T> int refresh_kx_t(pdlp_handle h)
@@ -261,22 +272,16 @@ template <typename T> int refresh_kx_t(pdlp_handle h)
     return rc;
 }
 
-// RANGED: the handle has two-sided rows (pdlp_set_row_upper: float32 / float64, one GPU, no exchange -- so never PEER, and the
-// matrix has the working type)
+// RANGED: the handle has two-sided rows (pdlp_set_row_upper: float32 / float64, one GPU, no exchange -- so never PEER)
 template <typename T, bool ADAPT, bool PEER, bool RANGED = false> int dual_half_e(pdlp_handle h, T* ksum)
 {
     DualEpi<T, ADAPT, PEER, RANGED> e{yloc<T>(h, h->ix_cur), yloc<T>(h, h->ix_prev), (const T*)h->p.q, (T*)h->y_sum, (T*)h->kxb[0],
                                       h->sc, h->ineq_end, ksum};
     peer_targets(h, e.peer, 1 + h->ix_prev);
+    set_optional(e.upper, h);
     if (ADAPT) h->last_gridB = grid_of(h->sK, h->ml);
     h->use_split = true;
-    int rc;
-    if constexpr (RANGED) {
-        e.upper.p = (const T*)h->q_upper;
-        rc = launch_mat<T, T>(h, false, h->xbar, e, h->partB);
-    } else {
-        rc = launch_csr<T>(h, false, h->xbar, e, h->partB);
-    }
+    const int rc = launch_csr<T>(h, false, h->xbar, e, h->partB);
     h->use_split = false;
     return rc;
 }
@@ -289,9 +294,9 @@ template <typename T> int dual_half_t(pdlp_handle h, int adaptive)
     const PieceCtl pc = piece_ctl(h, h->sK);
     rc = PDLP_OK;
     if (!pc.skip && h->q_upper)
-        rc = adaptive ? dual_half_e<T, true, false, true>(h, ksum) : dual_half_e<T, false, false, true>(h, ksum);
+        rc = with_flags([&](auto A) { return dual_half_e<T, A.value, false, true>(h, ksum); }, adaptive);
     else if (!pc.skip)       // (else: all of this half-step went out with piece 0)
-        rc = with_adapt_peer(h, adaptive, [&](auto A, auto P) { return dual_half_e<T, decltype(A)::value, decltype(P)::value>(h, ksum); });
+        rc = with_flags([&](auto A, auto P) { return dual_half_e<T, A.value, P.value>(h, ksum); }, adaptive, h->peer.active);
     if (rc != PDLP_OK) { h->sK.pending = false; return rc; }
     if (!pc.finish) return PDLP_OK;                          // (more pieces of this half-step to come)
     h->sK.pending = false;

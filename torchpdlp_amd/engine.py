@@ -197,14 +197,13 @@ class PdlpEngine(KernelChoice, Exchange):
         = a one-sided row; ``y_i > 0``: the lower side is active, ``y_i < 0``: the upper side.  ``None`` switches them off.  Validated
         here (``ranged.check_row_upper``: ``ValueError``); float32 / float64 engines on one GPU (``ValueError`` otherwise).  While set,
         ``detect_infeasibility`` and the population calls raise ``PdlpError``."""
-        from .ranged import REFUSED, check_row_upper
+        from . import compose, ranged
         if q_upper is None:
             N.check(self.lib.pdlp_set_row_upper(self.h, None), "pdlp_set_row_upper")
             self.q_upper = None
             return
-        if self.mixed or self.comm is not None:
-            raise ValueError(REFUSED)
-        qu = check_row_upper(self.q, as_vec(q_upper, self.ml, self.device, self.dtype), self.m_ineq)
+        compose.check_composition(q_upper=True, mixed=self.mixed, comm=self.comm is not None)
+        qu = ranged.check_row_upper(self.q, as_vec(q_upper, self.ml, self.device, self.dtype), self.m_ineq)
         N.check(self.lib.pdlp_set_row_upper(self.h, qu.data_ptr()), "pdlp_set_row_upper")
         self.q_upper = qu                      # (kept alive: the library points into it)
 

@@ -5,8 +5,7 @@ from __future__ import annotations
 
 import torch
 
-REFUSED = ("quad_diag (diagonal quadratic objective) runs on one GPU in float32 or float64: not with mixed precision, a communicator, "
-           "direct_exchange, infeasibility_detect, fishnet or adaptive_retry")
+from .compose import QUAD_REFUSED as REFUSED     # noqa: F401  (the text of the refusals, under its name here)
 
 
 def check_quad_diag(d, n=None):

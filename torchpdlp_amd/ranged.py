@@ -6,8 +6,7 @@ from __future__ import annotations
 
 import torch
 
-REFUSED = ("q_upper (two-sided rows) runs on one GPU in float32 or float64: not with mixed precision, a communicator, "
-           "infeasibility_detect, fishnet or adaptive_retry")
+from .compose import RANGED_REFUSED as REFUSED     # noqa: F401  (the text of the refusals, under its name here)
 
 
 def check_row_upper(q, q_upper, m_ineq: int):

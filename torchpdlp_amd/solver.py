@@ -17,8 +17,9 @@ from . import _native as N
 from .engine import Comm, PdlpEngine
 from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, fixed_point_error, fixed_point_restart_decision,   # noqa: F401
                     kkt_error, np_type, previous_kkt_matters, primal_weight, restart_decision, start_eta, start_omega, terminated)
-from .quad import REFUSED as QUAD_REFUSED, check_quad_diag
-from .ranged import REFUSED as RANGED_REFUSED, check_row_upper, norm_vector as ranged_norm_vector
+from .compose import HALPERN_REFUSED, check_composition     # noqa: F401  (HALPERN_REFUSED: importable from here)
+from .quad import check_quad_diag
+from .ranged import check_row_upper, norm_vector as ranged_norm_vector
 from .sparse import CsrPair, as_vec, resolve_device     # noqa: F401  (resolve_device: api.py and callers take it from here)
 
 
@@ -29,8 +30,6 @@ def check_termination(primal_residual, dual_residual, duality_gap, prim_obj, adj
 
 
 kkt_from_residuals = kkt_error
-HALPERN_REFUSED = ("halpern=True runs the fixed step on one GPU in float32 or float64: not with adaptive, adaptive_retry, "
-                   "infeasibility_detect, mixed precision or a communicator")
 HALPERN_RESTARTS = ("kkt", "fixed_point")
 primal_weight_from_distances = primal_weight
 
@@ -99,8 +98,11 @@ class PdhgDriver:
         self.fixed_point = check_halpern_restart(halpern_restart, self.halpern) == "fixed_point"
         self.eta = None                                                     # the fixed step of the run (start)
         self.r0 = self.r_prev = None                                        # fixed-point rule: the residual at the restart point / at the previous check
-        if self.halpern and (adaptive or adaptive_retry or infeasibility_detect or getattr(eng, "mixed", False) or eng.comm is not None):
-            raise ValueError(HALPERN_REFUSED)
+        form = dict(adaptive_retry=adaptive_retry, infeasibility_detect=infeasibility_detect, mixed=getattr(eng, "mixed", False), comm=eng.comm is not None)
+        check_composition(halpern=self.halpern, adaptive=adaptive, **form)
+        q_upper = getattr(eng, "q_upper", None)     # (a refusal comes before anything more of the engine is read: one switch at a time)
+        check_composition(q_upper=q_upper is not None, **form)
+        check_composition(quad_diag=getattr(eng, "quad_diag", None) is not None, **form)
         self.kkt_prev_cand = None                                           # Halpern: the candidate's KKT error at the previous check
         self.infeasibility_detect, self.infeas_tol = bool(infeasibility_detect), float(infeas_tol)
         self.infeasible = None                                              # the detector's verdict (pdhg.py:94-100)
@@ -113,13 +115,6 @@ class PdhgDriver:
         self.tol, self.verbose, self.trace = tol, verbose, trace
         self.t = np_type(eng.dtype)
         # pdhg.py:19-20; with two-sided rows (the engine's q_upper) ||q|| is the norm of max(|q_i|, |q_upper_i|) on those rows
-        q_upper = getattr(eng, "q_upper", None)
-        if q_upper is not None and (adaptive_retry or infeasibility_detect or getattr(eng, "mixed", False) or eng.comm is not None):
-            raise ValueError(RANGED_REFUSED)
-        # a diagonal quadratic objective (the engine's quad_diag) changes nothing here: the engine's sums carry the term
-        if getattr(eng, "quad_diag", None) is not None and (adaptive_retry or infeasibility_detect or getattr(eng, "mixed", False)
-                                                             or eng.comm is not None):
-            raise ValueError(QUAD_REFUSED)
         self.q_norm = self.t(_global_norm(ranged_norm_vector(eng.q, q_upper, getattr(eng, "m_ineq", 0)), eng.comm))
         self.c_norm = self.t(_global_norm(eng.c, eng.comm))
         self.n = self.k = self.j = self.tt = 0
@@ -501,16 +496,10 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     """
     from .distributed import gather_report, gather_solution, shard_engine, start_blocks
     check_halpern_restart(halpern_restart, halpern)
-    if halpern and (adaptive or adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False)):
-        raise ValueError(HALPERN_REFUSED)
-    if q_upper is not None:
-        if adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False):
-            raise ValueError(RANGED_REFUSED)
-        q_upper = check_row_upper(q, q_upper, m_ineq)
-    if quad_diag is not None:
-        if adaptive_retry or infeasibility_detect or precision is not None or comm not in (None, False):
-            raise ValueError(QUAD_REFUSED)
-        quad_diag = check_quad_diag(quad_diag, torch.as_tensor(c).numel())
+    check_composition(halpern=halpern, q_upper=q_upper is not None, quad_diag=quad_diag is not None, adaptive=adaptive,
+                      adaptive_retry=adaptive_retry, infeasibility_detect=infeasibility_detect, mixed=precision is not None, comm=comm not in (None, False))
+    q_upper = check_row_upper(q, q_upper, m_ineq)
+    quad_diag = check_quad_diag(quad_diag, torch.as_tensor(c).numel())
     device = resolve_device(device)
     Kp = CsrPair.from_any(K, device=device)
     dtype = Kp.dtype
