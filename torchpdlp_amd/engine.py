@@ -499,7 +499,7 @@ class PdlpEngine(KernelChoice, Exchange):
 
     def mv_product(self, X: torch.Tensor) -> torch.Tensor:
         """K X for a population X (n x j, j in MV_WIDTHS) in one pass over K -- ``pts_y = K @ pts`` (spectral_casting.py:100)"""
-        Y = torch.empty(self.m, int(X.shape[1]), dtype=self.dtype, device=self.device)
+        Y = torch.empty(self.m, int(X.shape[1]) if X.dim() == 2 else 0, dtype=self.dtype, device=self.device)
         j = self._mv_check(X, Y)
         N.check(self.lib.pdlp_mv_product(self.h, j, X.data_ptr(), Y.data_ptr()), "pdlp_mv_product")
         return Y
@@ -520,7 +520,7 @@ class PdlpEngine(KernelChoice, Exchange):
     def _mv_check(self, X, Y) -> int:
         if self.comm is not None:
             raise N.PdlpError("the population kernels run on one GPU")
-        j = int(X.shape[1])
+        j = int(X.shape[1]) if X.dim() == 2 else 0          # (anything but a matrix: refused below like every other shape)
         ok = (X.dim() == 2 and Y.dim() == 2 and X.shape == (self.n, j) and Y.shape == (self.m, j) and j in self.MV_WIDTHS
               and X.is_contiguous() and Y.is_contiguous() and X.dtype == self.dtype == Y.dtype and X.device == self.device == Y.device)
         if not ok:
