@@ -3,9 +3,9 @@
 ``HandleModel`` holds what the header says a handle holds -- the current, previous and averaged (or Halpern candidate) iterates, the
 eta-weighted sums with ``eta_sum`` and the weight still pending, the restart point, eta / omega / theta / k, the Halpern count t and
 the infeasibility detector's ``lam_prev`` -- and NOTHING carried: every product is multiplied out in float64 from the vectors it
-belongs to at the moment it is needed.  The engine saves those products by carrying them along under about ten host flags
-(pdlp_handle.inc: kx_valid, cur_kx_cached, cand_valid, kty_cur, kty_tail_done, avg_products, sums_broken, since_reset, halpern,
-anchors_valid, dy_folded); whatever order the calls come in, inside the documented contract, its numbers must stay the model's.
+belongs to at the moment it is needed.  The engine saves those products by carrying them along; which of them still belongs to its
+vector is the state of one struct (``Carried`` in pdlp_handle.inc, whose comment holds the rules and whose member functions are the
+only writers); whatever order the calls come in, inside the documented contract, its numbers must stay the model's.
 The steps are the float64 oracle's (``step_fixed`` / ``step_adaptive`` / ``kkt`` / ``detect_infeasibility``), the Halpern step is the
 formula of ``pdlp_halpern_iterate``'s comment, the averaging is pdhg.py:107-119 as ``oracle.pdlp_algorithm`` restates it (adaptive:
 an iterate's weight is known one step later, so it is PENDING until the next iteration or ``flush_average(True)`` adds its term; the
@@ -471,6 +471,11 @@ DIRECTED = {
     "options_toggled_graph": _S + [("iterate", 2, False), ("set_option", "GRAPH", 1), ("iterate", 8, False), ("set_option", "GRAPH", 0),
                                    ("iterate", 2, False)] + _CHECK(False) + [("restart", AVG), ("iterate", 2, False),
                                                                              ("kkt", CUR, 1.25, False)],
+    # graph replay from the first iteration of a period, an even count (replays only), off again, direct iterations, a check: the
+    # period has run eight iterations, the running product sums would hold the last two (a replay has to count as iterations)
+    "graph_even_replays_from_restart": _S + [("iterate", 2, False), ("kkt", CUR, 1.25, False), ("restart", CUR), ("set_option", "GRAPH", 1),
+                                             ("iterate", 6, False), ("set_option", "GRAPH", 0), ("iterate", 2, False)] + _CHECK(False)
+    + [("restart", AVG), ("iterate", 2, False), ("kkt", CUR, 1.25, False)],
     # eta changes INSIDE a fixed-step period: K'y of an iterate used to join its running sum with the eta of the NEXT iteration
     # while y_sum had it with its own, so K'y_avg from the sums was not K' y_avg (pdlp_set_step now ends the running sums)
     "set_step_mid_period": _S + [("iterate", 3, False), ("set_step", 0.5, 1.25, 3), ("iterate", 2, False)] + _CHECK(False)

@@ -1,5 +1,5 @@
 // pdlp_delta.inc -- delta mode (mixed precision): every product of the iteration runs on the float32 kernels over a float32
-// DIFFERENCE vector and is added to a float64 anchor product that is carried along (struct pdlp_solver: delta, anchors_valid,
+// DIFFERENCE vector and is added to a float64 anchor product that is carried along (pdlp_solver::delta; Carried: anchors_valid,
 // dy_folded).  The exact anchors (delta_refresh), the two half-steps, the KKT sums of a candidate from the anchors, and the entry
 // points that switch the mode and set or report the anchors' state.
 // Part of pdlp_hip.hip (included at file scope; not a translation unit of its own).  Needs: pdlp_products.inc and what is before it.
@@ -14,20 +14,18 @@ int delta_refresh(pdlp_handle h)
     if ((rc = launch_mat<double, float, StoreEpi<double>>(h, false, h->xb[h->ix_cur], ex, h->partB)) != PDLP_OK) return rc;
     StoreEpi<double> ey{(double*)h->ktyr};
     if ((rc = launch_mat<double, float, StoreEpi<double>>(h, true, h->yb[h->ix_cur], ey, h->partA)) != PDLP_OK) return rc;
-    h->anchors_valid = true;
-    h->dy_folded = true;
-    h->kx_valid = true;
+    h->carry.anchors_exact();
     return PDLP_OK;
 }
 
 template <bool ADAPT, bool PEER> int delta_primal_half_a(pdlp_handle h)
 {
     int rc;
-    if (!h->anchors_valid && (rc = delta_refresh(h)) != PDLP_OK) return rc;
+    if (!h->carry.anchors_valid && (rc = delta_refresh(h)) != PDLP_OK) return rc;
     DeltaPrimalEpi<ADAPT, PEER> e{(const double*)xloc<double>(h, h->ix_cur), xloc<double>(h, h->ix_prev), h->gdx + h->p.col0, (const double*)h->p.c,
                                   (const double*)h->p.l, (const double*)h->p.u, (double*)h->x_sum, (double*)h->ktyr, h->sc};
     peer_targets(h, e.peer, 4);
-    if (h->dy_folded && !h->sKT.pending) {
+    if (h->carry.dy_folded && !h->sKT.pending) {
         // K'y of the current y is already in the anchor (a restart check folded dy in, or the anchors are fresh): vector pass
         if (h->range_sel > 0) return PDLP_OK;                // (issued piece by piece: all of it went out with piece 0)
         h->last_gridA = rows_grid(h->nl);
@@ -41,7 +39,7 @@ template <bool ADAPT, bool PEER> int delta_primal_half_a(pdlp_handle h)
     h->use_split = false;
     if (pc.finish || rc != PDLP_OK) {
         h->sKT.pending = false;
-        h->dy_folded = true;   // (the anchor now belongs to the current y)
+        h->carry.folded();
     }
     return rc;
 }
@@ -65,8 +63,7 @@ template <bool ADAPT, bool PEER> int delta_dual_half_a(pdlp_handle h)
     const int t = h->ix_cur;
     h->ix_cur = h->ix_prev;
     h->ix_prev = t;
-    h->cand_valid[0] = h->cand_valid[1] = false;
-    h->dy_folded = false;      // gdy = y_cur - y_prev waits for the next product with K'
+    h->carry.iterated(1, true);
     return PDLP_OK;
 }
 
@@ -89,10 +86,10 @@ template <bool UNSCALE> int delta_kkt_cur(pdlp_handle h)
     typedef KktPrimalEpi<double, UNSCALE> KP;
     KD ed{xloc<double>(h, h->ix_cur), (const double*)h->p.c, (const double*)h->p.l, (const double*)h->p.u,
           UNSCALE ? (const double*)h->p.d_col : nullptr, nullptr};
-    if (!h->dy_folded) {
+    if (!h->carry.dy_folded) {
         AnchorEpi<KD, true> e{ed, (double*)h->ktyr};
         if ((rc = launch_mat<float, float, AnchorEpi<KD, true>>(h, true, h->gdy, e, h->partA)) != PDLP_OK) return rc;
-        h->dy_folded = true;
+        h->carry.folded();
         gridA = grid_of(h->sKT, h->nl);
     } else {
         if ((rc = epilogue_pass<double>(h, h->nl, h->ktyr, ed, h->partA)) != PDLP_OK) return rc;
@@ -100,22 +97,22 @@ template <bool UNSCALE> int delta_kkt_cur(pdlp_handle h)
     KP ep{yloc<double>(h, h->ix_cur), (const double*)h->p.q, UNSCALE ? (const double*)h->p.d_row : nullptr, nullptr, h->ineq_end};
     if ((rc = epilogue_pass<double>(h, h->ml, h->kxb[0], ep, h->partB)) != PDLP_OK) return rc;
     if ((rc = finalize_kkt(h, gridA, rows_grid(h->ml))) != PDLP_OK) return rc;
-    h->cand_valid[0] = true;
+    h->carry.kkt_kept(PDLP_CUR, true);
     return PDLP_OK;
 }
 
 int delta_kkt_local(pdlp_handle h, int which, int unscaled)
 {
     int rc;
-    if (!h->anchors_valid && (rc = delta_refresh(h)) != PDLP_OK) return rc;
+    if (!h->carry.anchors_valid && (rc = delta_refresh(h)) != PDLP_OK) return rc;
     typedef KktDualEpi<double, false> KD;
     typedef KktPrimalEpi<double, false> KP;
     if (which == PDLP_CUR) return unscaled ? delta_kkt_cur<true>(h) : delta_kkt_cur<false>(h);
     if (unscaled) return PDLP_ERR_STATE;                  // (the driver evaluates the un-scaled problem at the current iterate only)
-    if (!h->dy_folded) {
+    if (!h->carry.dy_folded) {
         FoldEpi f{(double*)h->ktyr};
         if ((rc = launch_mat<float, float, FoldEpi>(h, true, h->gdy, f, h->partA)) != PDLP_OK) return rc;
-        h->dy_folded = true;
+        h->carry.folded();
     }
     const int ix = which == PDLP_AVG ? h->ix_avg : h->ix_prev;
     // the full-length differences (every rank holds the complete candidate and the complete current iterate)
@@ -132,7 +129,7 @@ int delta_kkt_local(pdlp_handle h, int which, int unscaled)
     AnchorEpi<KP, false> eb{ep, (double*)h->kxb[0]};
     if ((rc = launch_mat<float, float, AnchorEpi<KP, false>>(h, false, h->gdx, eb, h->partB)) != PDLP_OK) return rc;
     if ((rc = finalize_kkt(h, grid_of(h->sKT, h->nl), grid_of(h->sK, h->ml))) != PDLP_OK) return rc;
-    if (which == PDLP_AVG) h->cand_valid[1] = true;
+    h->carry.kkt_kept(which, false);
     return PDLP_OK;
 }
 
@@ -148,8 +145,7 @@ int pdlp_set_delta(pdlp_handle h, int on)
     drop_graphs(h);
     h->graph_ok = false;
     h->delta = on != 0;
-    h->anchors_valid = false; h->dy_folded = false;
-    h->kx_valid = false; h->cand_valid[0] = h->cand_valid[1] = false; h->kty_cur = -1;
+    h->carry.drop_products();
     return PDLP_OK;
 }
 
@@ -159,15 +155,14 @@ int pdlp_set_anchors(pdlp_handle h, const void* kx_local, const void* kty_local)
     if (!h->delta) return PDLP_ERR_STATE;
     HIP_TRY(hipMemcpyAsync(h->kxb[0], kx_local, (size_t)h->ml * 8, hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->ktyr, kty_local, (size_t)h->nl * 8, hipMemcpyDeviceToDevice, h->stream));
-    h->anchors_valid = true; h->dy_folded = true; h->kx_valid = true;
-    h->cand_valid[0] = h->cand_valid[1] = false;
+    h->carry.anchors_given();
     return PDLP_OK;
 }
 
 int pdlp_delta_state(pdlp_handle h, int32_t out[3])
 {
     if (!h || !out) return PDLP_ERR_INVALID;
-    out[0] = h->delta; out[1] = h->anchors_valid; out[2] = h->dy_folded;
+    out[0] = h->delta; out[1] = h->carry.anchors_valid; out[2] = h->carry.dy_folded;
     return PDLP_OK;
 }
 

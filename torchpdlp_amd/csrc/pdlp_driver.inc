@@ -21,11 +21,15 @@ int iterate_direct(pdlp_handle h, int iters, int adaptive)
 
 // Graph replay was asked for (PDLP_GRAPH) and cannot be had: say so once per process -- the iteration falls back to plain launches,
 // which is correct but slower on small LPs, and would otherwise show up only as a slower benchmark.
-void graph_abandoned(const char* why)
+// The running sums were not kept while replay was on: no running average before the next restart.
+pdlp_solver::IterGraph* graph_abandoned(pdlp_handle h, const char* why)
 {
     static bool said = false;
     if (!said) std::fprintf(stderr, "libpdlp_hip: PDLP_GRAPH: graph capture abandoned (%s); iterating with direct launches\n", why);
     said = true;
+    h->graph_ok = false;
+    h->carry.sums_end();
+    return nullptr;
 }
 
 // the executable graph of two iterations from the current buffer roles (captured on first use), or nullptr
@@ -37,18 +41,14 @@ pdlp_solver::IterGraph* pair_graph(pdlp_handle h, int adaptive)
         if (!g.valid && !slot) slot = &g;
     }
     if (!slot) return nullptr;
-    // capture: the launch code runs unchanged against the library's stream; host-side roles are put back afterwards
+    // capture: the launch code runs unchanged against the library's stream; the host-side roles and the whole carried state are
+    // put back afterwards -- a capture issues launches and leaves no trace (replayed() accounts for the replays)
     const int ix_cur = h->ix_cur, ix_prev = h->ix_prev, gA = h->last_gridA, gB = h->last_gridB;
-    const bool kxv = h->kx_valid, c0 = h->cand_valid[0], c1 = h->cand_valid[1];
-    const int64_t sr = h->since_reset;
-    const bool ktd = h->kty_tail_done;
+    const Carried carry = h->carry;
     hipStream_t user = h->stream;
     if (hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
         (void)hipGetLastError();
-        graph_abandoned("hipStreamBeginCapture failed");
-        h->graph_ok = false;
-        h->sums_broken = true;        // (the running sums were not kept while replay was on: no running average before the next restart)
-        return nullptr;
+        return graph_abandoned(h, "hipStreamBeginCapture failed");
     }
     h->stream = h->gstream;
     const int rc = iterate_direct(h, 2, adaptive);
@@ -56,16 +56,12 @@ pdlp_solver::IterGraph* pair_graph(pdlp_handle h, int adaptive)
     hipGraph_t graph = nullptr;
     const hipError_t e = hipStreamEndCapture(h->gstream, &graph);
     h->ix_cur = ix_cur; h->ix_prev = ix_prev; h->last_gridA = gA; h->last_gridB = gB;
-    h->kx_valid = kxv; h->cand_valid[0] = c0; h->cand_valid[1] = c1;
-    h->since_reset = sr; h->kty_tail_done = ktd;
+    h->carry = carry;
     if (rc != PDLP_OK || e != hipSuccess || !graph ||
         hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0) != hipSuccess) {
         if (graph) (void)hipGraphDestroy(graph);
         (void)hipGetLastError();
-        graph_abandoned(rc != PDLP_OK ? "a launch failed during capture" : "hipStreamEndCapture / hipGraphInstantiate failed");
-        h->graph_ok = false;
-        h->sums_broken = true;        // (the running sums were not kept while replay was on: no running average before the next restart)
-        return nullptr;
+        return graph_abandoned(h, rc != PDLP_OK ? "a launch failed during capture" : "hipStreamEndCapture / hipGraphInstantiate failed");
     }
     (void)hipGraphDestroy(graph);
     slot->valid = true; slot->ix_cur = ix_cur; slot->ix_prev = ix_prev; slot->adaptive = adaptive;
@@ -191,7 +187,7 @@ int iterate_sharded(pdlp_handle h, int iters, int adaptive)
 {
     int rc;
     const bool vec32 = h->p.dtype == PDLP_F32;
-    if (h->delta && iters > 0 && !h->anchors_valid) {
+    if (h->delta && iters > 0 && !h->carry.anchors_valid) {
         if ((rc = comm_all_gather(h, h->xb[h->ix_cur], h->nl, vec32)) != PDLP_OK) return rc;
         if ((rc = comm_all_gather(h, h->yb[h->ix_cur], h->ml, vec32)) != PDLP_OK) return rc;
         if ((rc = delta_refresh(h)) != PDLP_OK) return rc;
@@ -233,18 +229,19 @@ int iterate_single(pdlp_handle h, int iters, int adaptive)
 {
     int rc, left = iters;
     if (h->graph_ok && left >= 5) {
-        if (!h->kx_valid) {          // the first iteration after a reset also refreshes the K x cache: never inside a captured pair
+        if (!h->carry.kx_valid) {    // the first iteration after a reset also refreshes the K x cache: never inside a captured pair
             if ((rc = iterate_direct(h, 1, adaptive)) != PDLP_OK) return rc;
             --left;
         }
         pdlp_solver::IterGraph* g = pair_graph(h, adaptive);
         if (g) {
+            const int pairs = left / 2;
             HIP_TRY(hipEventRecord(h->ev_in, h->stream));
             HIP_TRY(hipStreamWaitEvent(h->gstream, h->ev_in, 0));
             for (; left >= 2; left -= 2) HIP_TRY(hipGraphLaunch(g->exec, h->gstream));
             HIP_TRY(hipEventRecord(h->ev_out, h->gstream));
             HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_out, 0));
-            h->cand_valid[0] = h->cand_valid[1] = false;     // (what two direct iterations leave behind)
+            h->carry.replayed(pairs, h->delta);              // (what that many direct iterations leave behind)
             if (adaptive) { h->last_gridA = grid_of(h->sKT, h->nl); h->last_gridB = grid_of(h->sK, h->ml); }
         }
     }

@@ -13,8 +13,8 @@ template <typename T, bool RANGED, bool QUAD> int halpern_iterate_e(pdlp_handle 
     int rc;
     for (int it = 0; it < iters; ++it) {
         // a = (t+1)/(t+2), b = 1/(t+2) in double, rounded once to the working type
-        const double t2 = (double)(h->since_reset + 2);
-        const T a = (T)((double)(h->since_reset + 1) / t2), b = (T)(1.0 / t2);
+        const double t2 = (double)(h->carry.since_reset + 2);
+        const T a = (T)((double)(h->carry.since_reset + 1) / t2), b = (T)(1.0 / t2);
         const int cur = h->ix_cur, nxt = h->ix_prev, cand = h->ix_avg;
         // QUAD: diagonal quadratic objective (pdlp_set_objective_diag); RANGED: two-sided rows (pdlp_set_row_upper)
         HalpernPrimalEpi<T, QUAD> ep{xloc<T>(h, cur), xloc<T>(h, nxt), (T*)h->xbar + h->p.col0, xloc<T>(h, cand), (const T*)h->x_last,
@@ -27,7 +27,7 @@ template <typename T, bool RANGED, bool QUAD> int halpern_iterate_e(pdlp_handle 
         if ((rc = launch_csr<T>(h, false, h->xbar, ed, h->partB)) != PDLP_OK) return rc;
         h->ix_cur = nxt;           // the freshly written z becomes current; the old z's buffers are the next iteration's target
         h->ix_prev = cur;
-        ++h->since_reset;
+        h->carry.halpern_iterated();
     }
     return PDLP_OK;
 }
@@ -73,21 +73,14 @@ int pdlp_halpern_iterate(pdlp_handle h, int iters)
     char rname[64];
     if (g_roctx.level > 0) std::snprintf(rname, sizeof rname, "pdlp: %d Halpern iterations", iters);
     Range range(rname, h->stream);
-    // nothing carried from before survives: the K x cache, a K'y kept by a KKT pass (every primal half here multiplies), the
-    // products of the candidates, and the running sums (broken until the next restart: pdlp_kkt_local(PDLP_AVG) multiplies)
-    h->kx_valid = false; h->cur_kx_cached = false;
-    h->cand_valid[0] = h->cand_valid[1] = false;
-    h->kty_cur = -1; h->kty_tail_done = false; h->avg_products = false;
-    h->sums_broken = true;
-    h->halpern = true;             // PDLP_AVG holds the candidate now: pdlp_flush_average / pdlp_compute_average are refused
-    h->halpern_pair = true;        // PDLP_PREV and PDLP_AVG are z and T(z) of the last iteration (pdlp_halpern_fixed_point)
+    h->carry.halpern_begins();     // nothing carried from before survives; PDLP_AVG holds the candidate from now on
     return DISPATCH(h, halpern_iterate_t, h, iters);
 }
 
 int pdlp_halpern_fixed_point(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (halpern_refused(h) || !h->halpern_pair) return PDLP_ERR_STATE;
+    if (halpern_refused(h) || !h->carry.halpern_pair) return PDLP_ERR_STATE;
     Range range("pdlp: Halpern fixed-point residual", h->stream);
     return DISPATCH(h, halpern_fixed_point_t, h);
 }

@@ -1,6 +1,7 @@
-// pdlp_handle.inc -- what a solver handle is made of: Schedule (the state of one matrix's product), struct pdlp_solver (every field
-// initialised at its declaration), the workspace Layout with the capacities derived from the problem's sizes, and the functions
-// that check a problem, bind a handle to its workspace and release it.
+// pdlp_handle.inc -- what a solver handle is made of: Schedule (the state of one matrix's product), Carried (which carried product
+// still belongs to its vector, with the transitions that are its only writers), struct pdlp_solver (every field initialised at its
+// declaration), the workspace Layout with the capacities derived from the problem's sizes, and the functions that check a problem,
+// bind a handle to its workspace and release it.
 // Part of pdlp_hip.hip (included at file scope; not a translation unit of its own).  Needs: the constants, HIP_TRY, align_up
 // (pdlp_hip.hip), TNT / TRPT_MAX_ANY (pdlp_kernel_tiled.inc), g_rccl (pdlp_loaders.inc).
 // ------------------------------------------------------------------------------------------------
@@ -65,6 +66,118 @@ inline int64_t rowsum_groups(int64_t rows)
     return rows <= (int64_t)512 * 40 * 512 ? 8 : 1;
 }
 
+// What the single-LP handle carries so as not to multiply again, and whether each carried product still belongs to its vector.
+// THE RULES ARE WRITTEN HERE AND NOWHERE ELSE: a field says which buffer it speaks about, which vector that buffer must belong to
+// for the field to be up, and which events raise and clear it.  The member functions below are those events and the ONLY writers;
+// everything else reads the fields.  Plain and copyable: pair_graph copies the whole struct around a capture.  The option switches
+// (no_running, no_kty_reuse, graph_ok, delta) are configuration and stay in pdlp_solver; a transition that depends on one takes it.
+enum { CAND_NONE = 0, CAND_KX_OWN, CAND_KX_CARRIED };
+struct Carried {
+    // kxb[0] is K x of the CURRENT x (delta mode: the float64 anchor K x_cur).  Up: a K x refresh, exact or given anchors, a
+    // restart that adopted a candidate WITH products.  Down: a restart without them (also to the current iterate: the next dual
+    // half-step multiplies once), a discarded trial (kxb[0] belongs to the rejected x+), Halpern iterations, a mode switch.  Every
+    // dual half-step keeps it up by carrying kxb[0] along.
+    bool kx_valid = false;
+    // The KKT pass of the CURRENT iterate kept K'y_cur in ktyb[0] and K x_cur in kxb[1] (CAND_KX_OWN: it multiplied) or took K x from
+    // kxb[0] (CAND_KX_CARRIED: nothing to swap on a restart; always this in delta mode).  Up: kkt_kept(PDLP_CUR).  Down: whatever
+    // moves the current iterate or changes the operands -- an iteration, a restart, new operands, drop_products.  (One field where
+    // there were two, cand_valid[0] and cur_kx_cached: the second was read only under the first, and every pass that raised the
+    // first set the second.)
+    int cand_cur = CAND_NONE;
+    // The KKT pass of the AVERAGED iterate (the Halpern candidate) kept K'y in ktyb[1] and K x in kxb[2]; same events.
+    bool cand_avg = false;
+    // ktyb[kty_cur] is K'y of the CURRENT y although cand_cur is down: the restart adopted candidate kty_cur with its products.
+    // -1: none (see cand_cur).  Up: restart_adopted with products.  Down: an iteration; a KKT pass at the current iterate (its own
+    // copy in ktyb[0] supersedes) or one that overwrites ktyb[1] while that is the copy; an average formed into ktyb[1]; a restart
+    // to the average without products; new operands; drop_products.
+    int kty_cur = -1;
+    // Delta mode: kxb[0] / ktyr are the float64 anchors of the current iterate (anchors_valid), and ktyr is K'y of the CURRENT y
+    // (dy_folded; else of the previous y, with gdy = y_cur - y_prev still to be folded in by the next product with K').  Both false
+    // outside delta mode.  Up: anchors_exact / anchors_given, folded; a restart to the average that adopted its products.  Down:
+    // dy_folded by an iteration; anchors_valid by a restart to the average without products; both by drop_products.
+    bool anchors_valid = false, dy_folded = false;
+    // Iterations since kx_sum / kty_sum (and x_sum, y_sum, eta_sum) were last zeroed; also the Halpern count t.  Not counted in
+    // delta mode, which keeps no running products.  Up: iterated -- replays of captured pairs included: a replay touches no host
+    // state, so replayed() counts for it.  Down: one by trial_undone; zero by period_reset.
+    int64_t since_reset = 0;
+    // kty_sum already holds the term of the CURRENT y (the fixed step adds the term of an iterate one half-step late; the flush at a
+    // restart check adds it at once).  Up: flushed_tail.  Down: an iteration, period_reset.  Read only while sums_broken is down.
+    bool kty_tail_done = false;
+    // kx_sum / kty_sum miss a term of this period, or hold one with another weight than x_sum / y_sum: no product of the average
+    // from the sums, the checks multiply.  Up: sums_end inside a period (the callers say why), a discarded trial, Halpern iterations.
+    // Down: period_reset, which goes with the zeroing of the sums.
+    bool sums_broken = false;
+    // kxb[2] / ktyb[1] are K x_avg / K'y_avg of the average in the PDLP_AVG buffers, formed from the sums.  Up: averaged(true).
+    // Down: averaged(false), period_reset, drop_all -- and an iteration, as a safeguard: nothing an iteration writes is read under
+    // this flag (profiles/r13_sequences/README.md, mutant (a)).
+    bool avg_products = false;
+    // pdlp_halpern_iterate has run since the last pdlp_set_iterate: PDLP_AVG holds its candidate, not an average, and the two
+    // averaging calls are refused.  Up: halpern_begins.  Down: new_iterate only.
+    bool halpern = false;
+    // PDLP_PREV / PDLP_AVG are still z / T(z) of the last Halpern iteration (pdlp_halpern_fixed_point).  Up: halpern_begins.
+    // Down: buffers_reassigned -- any call that re-assigns the iterate buffers.
+    bool halpern_pair = false;
+
+    // A capture (pair_graph) runs the launch code, transitions included, and puts the whole struct back: it leaves no trace.  It used
+    // to restore kx_valid, the candidates, since_reset and kty_tail_done only; what it left in the others, and why replayed() gives
+    // every later call the same answer: kty_cur = -1 and avg_products = false as after an iteration -- replayed() IS iterated();
+    // sums_broken, halpern and halpern_pair as they were (no half-step writes the first two, pdlp_iterate had cleared the third);
+    // delta mode: anchors_valid up (a capture starts only with kx_valid up, which the anchors raise together with it) and dy_folded
+    // down as after an iteration -- iterated() again.  A replay from a CACHED graph used to leave kty_cur and avg_products alone,
+    // stale after a restart; under replay nothing reads them, and replayed() now clears them before replay can be switched off.
+
+    void new_iterate() { *this = Carried(); }                                  // pdlp_set_iterate: nothing belongs to the new vectors
+    void period_reset() { since_reset = 0; kty_tail_done = avg_products = sums_broken = false; }     // the sums were zeroed
+    void drop_candidates() { cand_cur = CAND_NONE; cand_avg = false; }
+    // pdlp_restart made candidate `cand` (0: current, 1: average) the current iterate, with the products its KKT pass had left or
+    // without (the caller swaps the buffers BEFORE this call: it reads the candidates).  Delta mode keeps no running sums: no period.
+    void restart_adopted(int cand, bool delta)
+    {
+        const bool had = cand == 0 ? cand_cur != CAND_NONE : cand_avg;
+        if (delta) {
+            if (cand == 1) { if (had) dy_folded = true; else anchors_valid = false; }
+        } else {
+            kx_valid = had;
+            if (had) kty_cur = cand; else if (cand == 1) kty_cur = -1;
+            period_reset();
+        }
+        drop_candidates();
+    }
+    // `n` PDHG iterations finished (the last dual half-step of each has swapped the buffers)
+    void iterated(int64_t n, bool delta)
+    {
+        if (delta) dy_folded = false;      // gdy = y_cur - y_prev waits for the next product with K'
+        else { since_reset += n; kty_tail_done = avg_products = false; kty_cur = -1; }
+        drop_candidates();
+    }
+    void replayed(int pairs, bool delta) { iterated(2 * (int64_t)pairs, delta); }      // `pairs` launches of a captured pair
+    // a KKT pass at `which` is about to overwrite its K'y slot / has kept its products (kx_carried: K x came from kxb[0])
+    void kkt_begins(int which) { if (which == PDLP_CUR || (which == PDLP_AVG && kty_cur == 1)) kty_cur = -1; }
+    void kkt_kept(int which, bool kx_carried)
+    {
+        if (which == PDLP_CUR) cand_cur = kx_carried ? CAND_KX_CARRIED : CAND_KX_OWN;
+        if (which == PDLP_AVG) cand_avg = true;
+    }
+    void averaged(bool from_sums) { avg_products = from_sums; if (from_sums && kty_cur == 1) kty_cur = -1; }
+    void flushed_tail() { kty_tail_done = true; }
+    // the running sums stop being complete inside a period (at since_reset == 0 nothing has been added yet: nothing is missing)
+    void sums_end() { if (since_reset > 0) sums_broken = true; }
+    void operands_changed() { drop_candidates(); kty_cur = -1; }               // what a KKT pass kept belongs to the other q_upper / d
+    // pdlp_set_delta: no product survives the switch.  The sums' fields stay as they are, as they always did: delta mode reads none.
+    void drop_products() { kx_valid = false; drop_candidates(); kty_cur = -1; anchors_valid = dy_folded = false; }
+    // nothing carried survives, the running sums of this period included.  (One list where pdlp_halpern_iterate and
+    // pdlp_adaptive_retry had two that differed in cur_kx_cached: see cand_cur.  Neither runs in delta mode: the anchors are down.)
+    void drop_all() { drop_products(); kty_tail_done = avg_products = false; sums_broken = true; }
+    void trial_undone() { if (since_reset > 0) --since_reset; drop_all(); }    // pdlp_adaptive_retry: the products saw the rejected trial
+    void halpern_begins() { drop_all(); halpern = halpern_pair = true; }       // (every primal half of the mode multiplies)
+    void halpern_iterated() { ++since_reset; }
+    void buffers_reassigned() { halpern_pair = false; }
+    void kx_refreshed() { kx_valid = true; }
+    void anchors_exact() { anchors_valid = dy_folded = kx_valid = true; }      // delta_refresh
+    void anchors_given() { anchors_exact(); drop_candidates(); }               // pdlp_set_anchors
+    void folded() { dy_folded = true; }                                        // ktyr now belongs to the current y
+};
+
 }  // namespace
 
 // Every field carries its initial value HERE; pdlp_create sets only what depends on the problem (p, stream, es, mixed, nl, ml,
@@ -75,9 +188,9 @@ struct pdlp_solver {
     size_t es = 0;                // element size of the vectors
     bool mixed = false;           // PDLP_MIXED: float32 matrix values under float64 vectors
     // delta mode (mixed precision only): every product of the iteration runs on the float32 kernels over a float32 DIFFERENCE
-    // vector and is added to a float64 "anchor" product that is carried along: kxb[0] = K x_cur, ktyr = K'y (of y_cur once
-    // dy_folded, else of the previous y with gdy = y_cur - y_prev still to be folded in by the next product with K')
-    bool delta = false, anchors_valid = false, dy_folded = false;
+    // vector and is added to a float64 "anchor" product that is carried along: kxb[0] = K x_cur, ktyr = K'y (Carried: anchors_valid,
+    // dy_folded)
+    bool delta = false;
     ncclComm_t comm = nullptr;    // RCCL communicator of a sharded problem (pdlp_comm_init), or null: the caller does the exchange
     int comm_rank = 0, comm_size = 1;
     int xchunks = 1;              // chunks of the exchange of a gathered vector (pdlp_set_exchange_chunks); 1: one all-gather
@@ -101,9 +214,8 @@ struct pdlp_solver {
     char* kxb[3] = {};            // K x caches: [0] running, [1] from KKT(cur), [2] from KKT(avg)
     char *dxf = nullptr, *dyf = nullptr;         // infeasibility detection: full-length x - x_prev, y - y_prev (gathered by the caller when sharded)
     char *lam_prev = nullptr, *ktdy = nullptr;   //   this rank's block of the previous lambda and of K'dy
-    bool kx_valid = false, cand_valid[2] = {false, false};
     char* ktyb[2] = {};           // K'y of the candidates, kept by their KKT passes: [0] current, [1] averaged iterate
-    int kty_cur = -1;             // which of the two belongs to the CURRENT iterate after a restart (-1: see cand_valid[0])
+    Carried carry;                // which carried product still belongs to its vector
     bool no_kty_reuse = false;    // PDLP_OPT_KTY_REUSE = 0: timing experiments
     int split_local = 0, split_other = 0;   // PDLP_OPT_SPLIT_SLOTS: panel groups of a split product chosen by the caller (0: the library's rule)
     bool side_ok = false;         // the library's own streams and events exist (graph replay, split products)
@@ -139,14 +251,7 @@ struct pdlp_solver {
     // average's weights (kx_sum, kty_sum), so a restart check evaluates K x_cur, K x_avg and K'y_avg WITHOUT products:
     // one product (K'y_cur, kept for the next primal half-step) instead of four per check
     char *kx_sum = nullptr, *kty_sum = nullptr;
-    int64_t since_reset = 0;      // iterations since the sums were last zeroed (set_iterate / restart)
-    bool kty_tail_done = false;   // kty_sum already holds the term of the current y (added by the flush at a restart check)
-    bool sums_broken = false;     // a term was lost (flush before the K'y of the current iterate existed): no running average
-    bool avg_products = false;    // kxb[2] / ktyb[1] hold K x_avg / K'y_avg computed from the sums
-    bool cur_kx_cached = false;   // the KKT pass of the current iterate took K x from the cache (nothing to swap on restart)
     bool no_running = false;      // PDLP_OPT_RUNNING_KKT = 0: every KKT pass multiplies (round-1 behaviour)
-    bool halpern = false;         // pdlp_halpern_iterate has run since the last pdlp_set_iterate: PDLP_AVG holds its candidate, not an average
-    bool halpern_pair = false;    // PDLP_PREV / PDLP_AVG are still z / T(z) of the last Halpern iteration: no call has re-assigned the iterate buffers since
     double *partA = nullptr, *partB = nullptr, *red = nullptr, *sc = nullptr;
     void* rowsum = nullptr;       // row sums of the tiled kernel on their way to the epilogue: [groups][rs_stride]
     int64_t rs_stride = 0;        // rows + one row block                        (these three: copied from the Layout)
@@ -176,6 +281,7 @@ inline bool plain_single(pdlp_handle h)         // ... in one precision and outs
     return whole_problem(h) && !h->mixed && !h->delta && !h->comm && !h->peer.on;
 }
 inline bool has_extension(pdlp_handle h) { return h->q_upper || h->obj_diag; }    // two-sided rows or a quadratic objective
+inline bool mid_split_product(pdlp_handle h) { return h->sK.pending || h->sKT.pending; }      // in the middle of a split product
 
 void drop_graphs(pdlp_handle h)
 {

@@ -12,7 +12,8 @@
 //     pdlp_kernel_batch.inc   batched solves
 //   host side (at file scope; each opens its own anonymous namespace and, where it has entry points, its own extern "C" block)
 //     pdlp_loaders.inc        RCCL and roctx resolved with dlopen, Range; pdlp_trace_enable / pdlp_range_*
-//     pdlp_handle.inc         Schedule, struct pdlp_solver, the workspace Layout and its capacities, check / bind / free
+//     pdlp_handle.inc         Schedule, Carried (which carried product still belongs to its vector: the rules and the only writers),
+//                             struct pdlp_solver, the workspace Layout and its capacities, check / bind / free
 //     pdlp_schedule.inc       row-block and long-row schedules built on the host, the split-product planner (configure_split)
 //     pdlp_products.inc       launch_mat and what it is made of, the shared launch helpers, the half-steps
 //     pdlp_delta.inc          delta mode (mixed precision): half-steps and KKT from anchors; pdlp_set_delta / _anchors / _state
@@ -355,49 +356,27 @@ int pdlp_set_iterate(pdlp_handle h, const void* x_local, const void* y_local)
     HIP_TRY(hipMemcpyAsync(h->yb[h->ix_cur] + h->p.row0 * h->es, y_local, h->ml * h->es, hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->x_last, x_local, h->nl * h->es, hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->y_last, y_local, h->ml * h->es, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->x_sum, 0, h->nl * h->es, h->stream));
-    HIP_TRY(hipMemsetAsync(h->y_sum, 0, h->ml * h->es, h->stream));
-    hipLaunchKernelGGL(k_reset_average, dim3(1), dim3(1), 0, h->stream, h->sc);
-    HIP_TRY(hipGetLastError());
-    h->kx_valid = false;
-    h->cand_valid[0] = h->cand_valid[1] = false;
-    h->kty_cur = -1;
-    h->anchors_valid = false; h->dy_folded = false;
-    HIP_TRY(hipMemsetAsync(h->kx_sum, 0, h->ml * h->es, h->stream));
-    HIP_TRY(hipMemsetAsync(h->kty_sum, 0, h->nl * h->es, h->stream));
-    h->since_reset = 0; h->kty_tail_done = false; h->avg_products = false; h->sums_broken = false; h->cur_kx_cached = false;
-    h->halpern = false; h->halpern_pair = false;
+    int rc = zero_sums(h, true);
+    if (rc == PDLP_OK) h->carry.new_iterate();
+    return rc;
+}
+
+// q_upper (two-sided rows) or d (quadratic term) set, replaced or taken away.  The forms without them: mixed precision / delta mode,
+// a shard of a problem, an exchange of any kind.  (This is also what keeps pdlp_set_delta(on) away from d: it asks for a PDLP_MIXED
+// handle, which can never have it set.)
+static int set_operand(pdlp_handle h, const void* pdlp_solver::*operand, const void* local)
+{
+    if (!h) return PDLP_ERR_INVALID;
+    if (local && !plain_single(h)) return PDLP_ERR_STATE;
+    if (mid_split_product(h)) return PDLP_ERR_STATE;
+    drop_graphs(h);               // captured launches hold the functors without (or with the old) operand
+    h->*operand = local;
+    h->carry.operands_changed();
     return PDLP_OK;
 }
 
-int pdlp_set_row_upper(pdlp_handle h, const void* q_upper_local)
-{
-    if (!h) return PDLP_ERR_INVALID;
-    // forms without two-sided rows: mixed precision / delta mode, a shard of a problem, an exchange of any kind
-    if (q_upper_local && !plain_single(h)) return PDLP_ERR_STATE;
-    if (h->sK.pending || h->sKT.pending) return PDLP_ERR_STATE;       // not in the middle of a split product
-    drop_graphs(h);               // captured launches hold the functors without (or with the old) q_upper
-    h->q_upper = q_upper_local;
-    // what a KKT pass left behind belongs to the other set of rows: the candidates' products and the kept K'y
-    h->cand_valid[0] = h->cand_valid[1] = false;
-    h->kty_cur = -1; h->cur_kx_cached = false;
-    return PDLP_OK;
-}
-
-int pdlp_set_objective_diag(pdlp_handle h, const void* d_local)
-{
-    if (!h) return PDLP_ERR_INVALID;
-    // forms without the quadratic term: mixed precision / delta mode, a shard of a problem, an exchange of any kind.  (This is also
-    // what keeps pdlp_set_delta(on) away from the term: it asks for a PDLP_MIXED handle, which can never have d set.)
-    if (d_local && !plain_single(h)) return PDLP_ERR_STATE;
-    if (h->sK.pending || h->sKT.pending) return PDLP_ERR_STATE;       // not in the middle of a split product
-    drop_graphs(h);               // captured launches hold the functors without (or with the old) d
-    h->obj_diag = d_local;
-    // what a KKT pass left behind belongs to the other objective: the candidates' products and the kept K'y
-    h->cand_valid[0] = h->cand_valid[1] = false;
-    h->kty_cur = -1; h->cur_kx_cached = false;
-    return PDLP_OK;
-}
+int pdlp_set_row_upper(pdlp_handle h, const void* q_upper_local) { return set_operand(h, &pdlp_solver::q_upper, q_upper_local); }
+int pdlp_set_objective_diag(pdlp_handle h, const void* d_local) { return set_operand(h, &pdlp_solver::obj_diag, d_local); }
 
 int pdlp_get_iterate(pdlp_handle h, int which, void* x_local, void* y_local)
 {
@@ -417,7 +396,7 @@ int pdlp_set_step(pdlp_handle h, double eta, double omega, double theta, int64_t
     // inside an averaging period a new eta ends the running products: the fixed step adds K'y of an iterate to its running sum with
     // the eta of the NEXT iteration (the product only exists then), y_sum has it with its own, so K'y_avg from the sums would not be
     // K' y_avg any more; the checks multiply until the next restart
-    if (h->since_reset > 0) h->sums_broken = true;
+    h->carry.sums_end();
     return PDLP_OK;
 }
 
@@ -440,7 +419,7 @@ int pdlp_get_scalars(pdlp_handle h, double out[PDLP_NSCAL])
 int pdlp_primal_half(pdlp_handle h, int adaptive)
 {
     if (!h) return PDLP_ERR_INVALID;
-    h->halpern_pair = false;       // (a half-step re-assigns the iterate buffers)
+    h->carry.buffers_reassigned();
     if (h->delta) return delta_primal_half(h, adaptive);
     return DISPATCH(h, primal_half_t, h, adaptive);
 }
@@ -448,7 +427,7 @@ int pdlp_primal_half(pdlp_handle h, int adaptive)
 int pdlp_dual_half(pdlp_handle h, int adaptive)
 {
     if (!h) return PDLP_ERR_INVALID;
-    h->halpern_pair = false;
+    h->carry.buffers_reassigned();
     if (h->delta) return delta_dual_half(h, adaptive);
     return DISPATCH(h, dual_half_t, h, adaptive);
 }
@@ -459,15 +438,15 @@ int pdlp_dual_half_piece(pdlp_handle h, int adaptive, int piece, int pieces) { r
 int pdlp_primal_half_begin(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->delta && !h->anchors_valid) return PDLP_OK;
+    if (h->delta && !h->carry.anchors_valid) return PDLP_OK;
     return DISPATCH(h, half_begin_t, h, true, h->yb[h->ix_cur]);
 }
 
 int pdlp_dual_half_begin(pdlp_handle h, int adaptive)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->delta && !h->anchors_valid) return PDLP_OK;
-    if (!h->delta && !h->kx_valid) return PDLP_OK;        // the K x refresh ahead of this half-step uses the same scratch
+    if (h->delta && !h->carry.anchors_valid) return PDLP_OK;
+    if (!h->delta && !h->carry.kx_valid) return PDLP_OK;        // the K x refresh ahead of this half-step uses the same scratch
     return DISPATCH(h, half_begin_t, h, false, h->xbar);
 }
 
@@ -482,17 +461,17 @@ int pdlp_split_info(pdlp_handle h, int transpose, int32_t out[4])
 int pdlp_set_option(pdlp_handle h, int option, int64_t value)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->sK.pending || h->sKT.pending) return PDLP_ERR_STATE;       // not in the middle of a split product
+    if (mid_split_product(h)) return PDLP_ERR_STATE;
     switch (option) {
         case PDLP_OPT_RUNNING_KKT:
             // (switched back on inside a period: the running sums were not kept meanwhile -- no running average before the next restart)
-            if (h->no_running && value != 0 && h->since_reset > 0) h->sums_broken = true;
+            if (h->no_running && value != 0) h->carry.sums_end();
             h->no_running = value == 0;
             return PDLP_OK;
         case PDLP_OPT_KTY_REUSE: h->no_kty_reuse = value == 0; return PDLP_OK;
         case PDLP_OPT_GRAPH:
             drop_graphs(h);
-            if (h->graph_ok && h->since_reset > 0) h->sums_broken = true;      // (nor while replay was on)
+            if (h->graph_ok) h->carry.sums_end();      // (nor while replay was on)
             h->graph_ok = value != 0 && h->side_ok && !h->comm;
             return (value != 0 && !h->graph_ok) ? PDLP_ERR_STATE : PDLP_OK;
         case PDLP_OPT_BEGIN_INLINE: h->begin_inline = value != 0; return PDLP_OK;
@@ -520,7 +499,7 @@ int pdlp_set_option(pdlp_handle h, int option, int64_t value)
 int pdlp_set_exchange_chunks(pdlp_handle h, int chunks)
 {
     if (!h || chunks < 1 || chunks > MAX_CHUNKS) return PDLP_ERR_INVALID;
-    if (h->sK.pending || h->sKT.pending) return PDLP_ERR_STATE;       // not in the middle of a split product
+    if (mid_split_product(h)) return PDLP_ERR_STATE;
     h->xchunks = chunks;
     return reconfigure_splits(h);
 }
@@ -558,8 +537,7 @@ int pdlp_tile_limits(pdlp_handle h, int32_t out[6])
 int pdlp_adaptive_retry(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->delta || h->sK.pending || h->sKT.pending || h->graph_ok) return PDLP_ERR_STATE;   // (float32 / float64 handles, between iterations)
-    h->halpern_pair = false;
+    if (h->delta || mid_split_product(h) || h->graph_ok) return PDLP_ERR_STATE;   // (float32 / float64 handles, between iterations)
     // the scalars: the rejected trial's weight leaves eta_total again, nothing is pending (the trial's epilogues have folded the
     // previous iterate's weight into the sums: the repeated half-steps must add nothing), k goes back; eta keeps the rule's eta'
     hipLaunchKernelGGL(k_retry_scalars, dim3(1), dim3(1), 0, h->stream, h->sc);
@@ -569,11 +547,8 @@ int pdlp_adaptive_retry(pdlp_handle h)
     const int t = h->ix_cur;
     h->ix_cur = h->ix_prev;
     h->ix_prev = t;
-    if (h->since_reset > 0) --h->since_reset;
-    h->kx_valid = false;              // the carried K x now belongs to the rejected x+: recomputed by the next dual half-step
-    h->sums_broken = true;            // (the running products of this period saw the rejected trial: the checks multiply instead)
-    h->cand_valid[0] = h->cand_valid[1] = false;
-    h->kty_cur = -1; h->kty_tail_done = false; h->avg_products = false;
+    h->carry.buffers_reassigned();
+    h->carry.trial_undone();          // (kxb[0] belongs to the rejected x+, the running products of this period saw the trial)
     return PDLP_OK;
 }
 
@@ -597,7 +572,7 @@ int pdlp_iterate(pdlp_handle h, int iters, int adaptive)
 {
     if (!h || iters < 0) return PDLP_ERR_INVALID;
     adaptive = adaptive ? 1 : 0;
-    h->halpern_pair = false;       // (PDHG iterations re-assign the iterate buffers)
+    h->carry.buffers_reassigned();
     char rname[64];
     if (g_roctx.level > 0) std::snprintf(rname, sizeof rname, "pdlp: %d %s iterations", iters, adaptive ? "adaptive" : "fixed-step");
     Range range(rname, h->stream);
@@ -618,14 +593,14 @@ int pdlp_fixed_advance(pdlp_handle h, int iters)
 int pdlp_flush_average(pdlp_handle h, int adaptive)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->halpern) return PDLP_ERR_STATE;       // (the averaging calls would overwrite the Halpern candidate in PDLP_AVG)
+    if (h->carry.halpern) return PDLP_ERR_STATE;       // (the averaging calls would overwrite the Halpern candidate in PDLP_AVG)
     return DISPATCH(h, flush_t, h, adaptive ? 1 : 0);
 }
 
 int pdlp_compute_average(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->halpern) return PDLP_ERR_STATE;
+    if (h->carry.halpern) return PDLP_ERR_STATE;
     return DISPATCH(h, average_t, h);
 }
 
@@ -642,7 +617,7 @@ int pdlp_report_local(pdlp_handle h, int which, int unscaled, void* rc_local, vo
 {
     if (!h || which < PDLP_CUR || which > PDLP_PREV) return PDLP_ERR_INVALID;
     if (unscaled && (!h->p.d_col || !h->p.d_row)) return PDLP_ERR_STATE;
-    if (h->sK.pending || h->sKT.pending || h->range_sel >= 0) return PDLP_ERR_STATE;     // not in the middle of a split half-step
+    if (mid_split_product(h) || h->range_sel >= 0) return PDLP_ERR_STATE;     // (nor between the pieces of a half-step)
     Range range("pdlp: solution report", h->stream);
     return DISPATCH(h, report_local_t, h, which, unscaled, rc_local, act_local);
 }

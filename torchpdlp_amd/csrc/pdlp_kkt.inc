@@ -39,7 +39,8 @@ template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int 
     const T* dcol = UNSCALE ? (const T*)h->p.d_col : nullptr;
     const T* drow = UNSCALE ? (const T*)h->p.d_row : nullptr;
     int rc, gridA = grid_of(h->sKT, h->nl), gridB = grid_of(h->sK, h->ml);
-    if (which == PDLP_AVG && h->avg_products) {
+    const bool kx_carried = which == PDLP_CUR && h->carry.kx_valid && !h->no_running;
+    if (which == PDLP_AVG && h->carry.avg_products) {
         // K'y_avg (ktyb[1]) and K x_avg (kxb[2]) were formed from the running sums by pdlp_compute_average: two vector passes
         const auto ed = kkt_dual_epi<T, UNSCALE, QUAD>(h, ix, dcol, nullptr);
         if ((rc = epilogue_pass<T>(h, h->nl, h->ktyb[1], ed, h->partA)) != PDLP_OK) return rc;
@@ -52,23 +53,21 @@ template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int 
         // K'y of a candidate is the product the first primal half-step after the check needs again (same kernel, same
         // sums): keep it.  (A pass at the current iterate after a restart to the average supersedes that restart's copy.)
         T* kty_out = which == PDLP_CUR ? (T*)h->ktyb[0] : (which == PDLP_AVG ? (T*)h->ktyb[1] : nullptr);
-        if (which == PDLP_CUR || (which == PDLP_AVG && h->kty_cur == 1)) h->kty_cur = -1;     // (the copy about to be overwritten)
+        h->carry.kkt_begins(which);
         const auto ed = kkt_dual_epi<T, UNSCALE, QUAD>(h, ix, dcol, kty_out);
         if ((rc = launch_csr<T>(h, true, h->yb[ix], ed, h->partA)) != PDLP_OK) return rc;
-        if (which == PDLP_CUR && h->kx_valid && !h->no_running) {
+        if (kx_carried) {
             // K x of the current iterate is carried along by the dual half-steps (kxb[0]): no product
             const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, nullptr);
             if ((rc = epilogue_pass<T>(h, h->ml, h->kxb[0], ep, h->partB)) != PDLP_OK) return rc;
             gridB = rows_grid(h->ml);
-            h->cur_kx_cached = true;
         } else {
             const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, kx_out);
             if ((rc = launch_csr<T>(h, false, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
-            if (which == PDLP_CUR) h->cur_kx_cached = false;
         }
     }
     if ((rc = finalize_kkt(h, gridA, gridB)) != PDLP_OK) return rc;
-    if (which != PDLP_PREV) h->cand_valid[which == PDLP_CUR ? 0 : 1] = true;
+    h->carry.kkt_kept(which, kx_carried);
     return PDLP_OK;
 }
 
@@ -132,27 +131,48 @@ template <typename T> void kkt_finish_t(const double* r, double omega_d, double*
     out[0] = pr; out[1] = dr; out[2] = gap; out[3] = p; out[4] = adj; out[5] = kkt;
 }
 
+// the period's running product sums are being kept and are complete so far
+inline bool sums_running(pdlp_handle h)
+{
+    return !h->delta && !h->carry.sums_broken && !h->no_running && !h->graph_ok && h->carry.since_reset > 0;
+}
+
+// a new averaging period (pdhg.py:58-60): x_sum, y_sum, eta_sum and the pending weight; `products`: the running product sums too
+int zero_sums(pdlp_handle h, bool products)
+{
+    HIP_TRY(hipMemsetAsync(h->x_sum, 0, h->nl * h->es, h->stream));
+    HIP_TRY(hipMemsetAsync(h->y_sum, 0, h->ml * h->es, h->stream));
+    if (products) {
+        HIP_TRY(hipMemsetAsync(h->kx_sum, 0, h->ml * h->es, h->stream));
+        HIP_TRY(hipMemsetAsync(h->kty_sum, 0, h->nl * h->es, h->stream));
+    }
+    hipLaunchKernelGGL(k_reset_average, dim3(1), dim3(1), 0, h->stream, h->sc);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
 template <typename T> int flush_t(pdlp_handle h, int adaptive)
 {
-    const bool running = !h->delta && !h->sums_broken && !h->no_running && !h->graph_ok && h->since_reset > 0;
+    Carried& c = h->carry;
+    const bool running = sums_running(h);
     if (adaptive) {
         // the weight of the current iterate became known only after its step-size rule: add it now
         hipLaunchKernelGGL(k_flush<T>, dim3(grid_for(h->nl)), dim3(BLOCK), 0, h->stream, h->nl, (T*)h->x_sum,
                            (const T*)xloc<T>(h, h->ix_cur), h->sc, (int)S_WPEND);
         hipLaunchKernelGGL(k_flush<T>, dim3(grid_for(h->ml)), dim3(BLOCK), 0, h->stream, h->ml, (T*)h->y_sum,
                            (const T*)yloc<T>(h, h->ix_cur), h->sc, (int)S_WPEND);
-        if (running && h->kx_valid)
+        if (running && c.kx_valid)
             hipLaunchKernelGGL(k_flush<T>, dim3(grid_for(h->ml)), dim3(BLOCK), 0, h->stream, h->ml, (T*)h->kx_sum, (const T*)h->kxb[0],
                                h->sc, (int)S_WPEND);
     }
     // K'y of the current y exists only if the KKT pass of the current iterate ran before this call (it keeps it in ktyb[0])
-    if (running && !h->kty_tail_done) {
-        if (h->cand_valid[0] && h->kty_cur < 0) {
+    if (running && !c.kty_tail_done) {
+        if (c.cand_cur != CAND_NONE && c.kty_cur < 0) {
             hipLaunchKernelGGL(k_flush<T>, dim3(grid_for(h->nl)), dim3(BLOCK), 0, h->stream, h->nl, (T*)h->kty_sum, (const T*)h->ktyb[0],
                                h->sc, (int)(adaptive ? S_WPEND : S_ETA));
-            h->kty_tail_done = true;
+            c.flushed_tail();
         } else if (adaptive) {
-            h->sums_broken = true;       // the pending weight is cleared below: that term of the sum is lost until the next restart
+            c.sums_end();                // the pending weight is cleared below: that term of the sum is lost until the next restart
         }
     }
     if (adaptive) hipLaunchKernelGGL(k_clear_pending, dim3(1), dim3(1), 0, h->stream, h->sc);
@@ -167,13 +187,12 @@ template <typename T> int average_t(pdlp_handle h)
     hipLaunchKernelGGL(k_average<T>, dim3(grid_for(h->ml)), dim3(BLOCK), 0, h->stream, h->ml, yloc<T>(h, h->ix_avg),
                        (const T*)h->y_sum, h->sc);
     // the products of the average from the running sums (K is linear): K x_avg = sum w_k K x_k / sum w_k, the same for K'y
-    h->avg_products = false;
-    if (!h->delta && !h->sums_broken && !h->no_running && !h->graph_ok && h->since_reset > 0 && h->kty_tail_done && h->kx_valid) {
+    const bool from_sums = sums_running(h) && h->carry.kty_tail_done && h->carry.kx_valid;
+    if (from_sums) {
         hipLaunchKernelGGL(k_average<T>, dim3(grid_for(h->ml)), dim3(BLOCK), 0, h->stream, h->ml, (T*)h->kxb[2], (const T*)h->kx_sum, h->sc);
         hipLaunchKernelGGL(k_average<T>, dim3(grid_for(h->nl)), dim3(BLOCK), 0, h->stream, h->nl, (T*)h->ktyb[1], (const T*)h->kty_sum, h->sc);
-        if (h->kty_cur == 1) h->kty_cur = -1;
-        h->avg_products = true;
     }
+    h->carry.averaged(from_sums);
     HIP_TRY(hipGetLastError());
     return PDLP_OK;
 }
@@ -266,50 +285,20 @@ int pdlp_restart(pdlp_handle h, int which)
 {
     if (!h || (which != PDLP_CUR && which != PDLP_AVG)) return PDLP_ERR_INVALID;
     const int cand = which == PDLP_CUR ? 0 : 1;
-    h->halpern_pair = false;       // (t = 0 again: the next fixed-point residual belongs to the next Halpern iteration)
+    h->carry.buffers_reassigned();      // (t = 0 again: the next fixed-point residual belongs to the next Halpern iteration)
     if (which == PDLP_AVG) {       // the averaged iterate becomes current (pdhg.py:133,137,141)
         const int t = h->ix_cur;
         h->ix_cur = h->ix_avg;
         h->ix_avg = t;
     }
-    if (h->delta) {                // the anchors follow the iterate: K x and K'y of the average were kept by its KKT pass
-        if (which == PDLP_AVG) {
-            if (h->cand_valid[1]) {
-                char* t = h->kxb[0]; h->kxb[0] = h->kxb[2]; h->kxb[2] = t;
-                t = h->ktyr; h->ktyr = h->ktyb[1]; h->ktyb[1] = t;
-                h->dy_folded = true;
-            } else {
-                h->anchors_valid = false;
-            }
-        }
-        h->cand_valid[0] = h->cand_valid[1] = false;
-        HIP_TRY(hipMemsetAsync(h->x_sum, 0, h->nl * h->es, h->stream));
-        HIP_TRY(hipMemsetAsync(h->y_sum, 0, h->ml * h->es, h->stream));
-        hipLaunchKernelGGL(k_reset_average, dim3(1), dim3(1), 0, h->stream, h->sc);
-        HIP_TRY(hipGetLastError());
-        return PDLP_OK;
+    // K x and K'y of the chosen point as its KKT pass left them follow the iterate: the K x cache unless the pass read it from there;
+    // delta mode: the average's pair becomes the anchors (the current iterate's anchors are in place)
+    if (cand == 1 ? h->carry.cand_avg : h->carry.cand_cur == CAND_KX_OWN) {
+        char* t = h->kxb[0]; h->kxb[0] = h->kxb[1 + cand]; h->kxb[1 + cand] = t;
+        if (h->delta) { t = h->ktyr; h->ktyr = h->ktyb[1]; h->ktyb[1] = t; }
     }
-    if (h->cand_valid[cand]) {     // K x and K'y of the chosen point were produced by its KKT pass (or carried along)
-        if (!(cand == 0 && h->cur_kx_cached)) {
-            char* t = h->kxb[0];
-            h->kxb[0] = h->kxb[1 + cand];
-            h->kxb[1 + cand] = t;
-        }
-        h->kx_valid = true;
-        h->kty_cur = cand;
-    } else {
-        h->kx_valid = false;
-        if (which == PDLP_AVG) h->kty_cur = -1;
-    }
-    h->cand_valid[0] = h->cand_valid[1] = false;
-    HIP_TRY(hipMemsetAsync(h->x_sum, 0, h->nl * h->es, h->stream));          // pdhg.py:58-60
-    HIP_TRY(hipMemsetAsync(h->y_sum, 0, h->ml * h->es, h->stream));
-    HIP_TRY(hipMemsetAsync(h->kx_sum, 0, h->ml * h->es, h->stream));
-    HIP_TRY(hipMemsetAsync(h->kty_sum, 0, h->nl * h->es, h->stream));
-    h->since_reset = 0; h->kty_tail_done = false; h->avg_products = false; h->sums_broken = false; h->cur_kx_cached = false;
-    hipLaunchKernelGGL(k_reset_average, dim3(1), dim3(1), 0, h->stream, h->sc);
-    HIP_TRY(hipGetLastError());
-    return PDLP_OK;
+    h->carry.restart_adopted(cand, h->delta);
+    return zero_sums(h, !h->delta);
 }
 
 }  // extern "C"

@@ -101,7 +101,7 @@ int iterate_peer(pdlp_handle h, int iters, int adaptive)
 {
     int rc = PDLP_OK;
     pdlp_solver::Peer& P = h->peer;
-    if (h->delta && iters > 0 && !h->anchors_valid) return PDLP_ERR_STATE;       // (the caller refreshes the anchors: that needs gathers)
+    if (h->delta && iters > 0 && !h->carry.anchors_valid) return PDLP_ERR_STATE;       // (the caller refreshes the anchors: that needs gathers)
     if (iters == 0) return PDLP_OK;
     // entry handshake: a peer's first block may only arrive once this rank's stream has reached the iterations -- whatever this rank
     // did with its vectors before (a restart check, a restart) is behind the flag

@@ -252,11 +252,12 @@ template <typename T> int primal_half_t(pdlp_handle h, int adaptive)
 {
     // K'y of the current iterate may still be there from the restart check (of the current iterate if nothing moved
     // since, or of the candidate the restart adopted)
-    const int src = (h->no_kty_reuse || h->graph_ok || h->sKT.pending) ? -1 : (h->kty_cur >= 0 ? h->kty_cur : (h->cand_valid[0] ? 0 : -1));
+    const Carried& c = h->carry;
+    const int src = (h->no_kty_reuse || h->graph_ok || h->sKT.pending) ? -1 : (c.kty_cur >= 0 ? c.kty_cur : (c.cand_cur != CAND_NONE ? 0 : -1));
     // K'y of the previous iterate's y joins the running sum unless this is the first half-step after a reset (that y is the
     // restart point) or the restart check's flush has already added it
     // (not under graph replay: a captured launch would freeze this decision)
-    T* ksum = (h->since_reset > 0 && !h->kty_tail_done && !h->sums_broken && !h->no_running && !h->graph_ok) ? (T*)h->kty_sum : nullptr;
+    T* ksum = (c.since_reset > 0 && !c.kty_tail_done && !c.sums_broken && !h->no_running && !h->graph_ok) ? (T*)h->kty_sum : nullptr;
     const PieceCtl pc = piece_ctl(h, h->sKT, src < 0);
     if (pc.skip) return PDLP_OK;                             // (all of this half-step went out with piece 0)
     if (h->obj_diag) return with_flags([&](auto A) { return primal_half_e<T, A.value, false, true>(h, src, ksum, pc); }, adaptive);
@@ -268,7 +269,7 @@ template <typename T> int refresh_kx_t(pdlp_handle h)
 {
     StoreEpi<T> e{(T*)h->kxb[0]};
     int rc = launch_csr<T>(h, false, h->xb[h->ix_cur], e, h->partB);
-    if (rc == PDLP_OK) h->kx_valid = true;
+    if (rc == PDLP_OK) h->carry.kx_refreshed();
     return rc;
 }
 
@@ -289,8 +290,8 @@ template <typename T, bool ADAPT, bool PEER, bool RANGED = false> int dual_half_
 template <typename T> int dual_half_t(pdlp_handle h, int adaptive)
 {
     int rc;
-    if (!h->kx_valid && (rc = refresh_kx_t<T>(h)) != PDLP_OK) return rc;      // K x of the current x: carried along from here on
-    T* ksum = (h->sums_broken || h->no_running || h->graph_ok) ? nullptr : (T*)h->kx_sum;
+    if (!h->carry.kx_valid && (rc = refresh_kx_t<T>(h)) != PDLP_OK) return rc;      // K x of the current x: carried along from here on
+    T* ksum = (h->carry.sums_broken || h->no_running || h->graph_ok) ? nullptr : (T*)h->kx_sum;
     const PieceCtl pc = piece_ctl(h, h->sK);
     rc = PDLP_OK;
     if (!pc.skip && h->q_upper)
@@ -300,13 +301,10 @@ template <typename T> int dual_half_t(pdlp_handle h, int adaptive)
     if (rc != PDLP_OK) { h->sK.pending = false; return rc; }
     if (!pc.finish) return PDLP_OK;                          // (more pieces of this half-step to come)
     h->sK.pending = false;
-    ++h->since_reset;
-    h->kty_tail_done = false; h->avg_products = false;
     const int t = h->ix_cur;   // the freshly written buffers become current, the old ones previous
     h->ix_cur = h->ix_prev;
     h->ix_prev = t;
-    h->cand_valid[0] = h->cand_valid[1] = false;
-    h->kty_cur = -1;
+    h->carry.iterated(1, false);
     return PDLP_OK;
 }
 
