@@ -312,6 +312,46 @@ int pdlp_set_row_upper(pdlp_handle h, const void* q_upper_local);
  * because it needs a PDLP_MIXED handle and such a handle never has the term. */
 int pdlp_set_objective_diag(pdlp_handle h, const void* d_local);
 
+/* ---- sparse quadratic objective -----------------------------------------------------------------------------------------------
+ * min c'x + 1/2 x'Qx over the same constraints, Q an n x n CSR matrix in the working dtype, symmetric and positive semidefinite (no
+ * counterpart in the reference).  The library can check neither property: the caller owns both.  rowptr (n + 1, 64-bit), colidx and
+ * val are device memory the caller keeps alive like K; all three NULL take Q away again.  With preconditioning (x = D_col x_s) pass
+ * Q_s = D_col Q D_col.
+ * The prox of such an objective is not closed form; the iteration takes the linearised (Condat-Vu) step: with tau = eta/omega,
+ * sigma = eta omega
+ *     g  = c + Q x                          one product with Q, its epilogue stores g
+ *     x' = clamp(x - tau (g - K'y), l, u)   the primal half-step as it is, reading g where it reads c
+ *     xbar, y' as always.
+ * It converges for 1/tau - sigma ||K||^2 >= ||Q||/2: the caller chooses eta accordingly (torchpdlp_amd/rules.py, qp_eta) and sets
+ * it anew with pdlp_set_step whenever omega changes.  Fixed step only.
+ * pdlp_primal_half(h, 0) and pdlp_iterate(h, iters, 0) launch the product with Q on the current x ahead of EVERY primal half-step,
+ * also ahead of the vector pass over a K'y that a KKT pass kept.  pdlp_kkt_local and pdlp_report_local first form g of the point they
+ * evaluate -- one product with Q per pass, also for an average whose other products come from the running sums -- and run their
+ * variable side over g: lam, the dual residual, the bound terms and the reduced costs come from c + Qx - K'y (+ Dx with a diagonal
+ * term).  The SIX SUMS KEEP THEIR PLACES: with h = 1/2 x'Qx from the epilogue's own sum (double, fixed order, no atomics),
+ * PDLP_BUF_RED[3] ends as c'x + h and PDLP_BUF_RED[1] as its own term - h (the functor over g leaves c'x + 2h in slot 3; a one-thread
+ * kernel subtracts h from both slots behind the pass).  h is invariant under the scaling.  PDLP_BUF_RED[PDLP_NRED - 1] holds x'Qx
+ * after such a pass, and PDLP_BUF_LAM_PREV holds g of the point last looked at (the detector that owns the buffer is refused).
+ * A handle may have Q, the diagonal term and two-sided rows together.  K may be on any product form; Q itself is multiplied by the
+ * CSR row-block kernel only (it takes no tiles and no sorted copy).
+ *
+ * pdlp_objective_matrix_bytes: the size of `work` for a Q of nnz stored entries.  pdlp_set_objective_matrix reads the row pointers
+ * back once and builds Q's row-block schedule (blocks of at most 256 rows and 2048 stored entries, longer rows in chunks) into `work`,
+ * device memory the caller keeps alive as long as Q is set: the low words of the row pointers, the block pairs, the long-row tables.
+ * It drops the captured graphs and what the handle carries from a KKT pass: the candidates' products and the kept K'y.
+ * PDLP_ERR_INVALID: one or two of the arrays NULL, row pointers that do not start at 0 or decrease.  PDLP_ERR_WORKSPACE: `work` NULL,
+ * too small or not 256-byte aligned.  PDLP_ERR_STATE: PDLP_MIXED handles, a shard of a problem, a handle with a communicator or a peer
+ * exchange, a handle with PDLP_OPT_GRAPH on.
+ * While Q is set, PDLP_ERR_STATE from: pdlp_iterate / pdlp_primal_half / pdlp_dual_half with adaptive != 0, pdlp_adaptive_retry /
+ * _reduce / _update; pdlp_halpern_iterate and pdlp_halpern_fixed_point (the reflected operator 2T - I of the linearised step is not
+ * non-expansive); pdlp_infeas_*, pdlp_mv_steps / _gap / _product, every pdlp_batch_* call; pdlp_comm_init, pdlp_peer_connect;
+ * pdlp_set_option(PDLP_OPT_GRAPH, 1); and pdlp_set_delta(on), which needs a PDLP_MIXED handle.
+ *
+ * pdlp_objective_product: out_local = Q x_full, the plain product (power iteration on Q, tests).  PDLP_ERR_STATE without a Q. */
+int pdlp_objective_matrix_bytes(pdlp_handle h, int64_t nnz, int64_t* bytes);
+int pdlp_set_objective_matrix(pdlp_handle h, const int64_t* rowptr, const int32_t* colidx, const void* val, void* work, int64_t work_bytes);
+int pdlp_objective_product(pdlp_handle h, const void* x_full, void* out_local);
+
 /* ---- sharded problems: the exchange inside the library (RCCL over xGMI) ------------------------------------------------
  * One process per GPU; rank r owns block r of the constraints and of the variables (equal, padded blocks -- the layout of
  * torchpdlp_amd/distributed.py).  The reference is single-device, so these have no counterpart there; SURVEY.md 8b sketched

@@ -101,6 +101,9 @@ SIGNATURES = {
     "pdlp_halpern_fixed_point": (_I, [_H]),
     "pdlp_set_row_upper": (_I, [_H, _P]),
     "pdlp_set_objective_diag": (_I, [_H, _P]),
+    "pdlp_objective_matrix_bytes": (_I, [_H, _I64, C.POINTER(_I64)]),
+    "pdlp_set_objective_matrix": (_I, [_H, _P, _P, _P, _P, _I64]),
+    "pdlp_objective_product": (_I, [_H, _P, _P]),
     "pdlp_set_exchange_chunks": (_I, [_H, _I]),
     "pdlp_set_option": (_I, [_H, _I, _I64]),
     "pdlp_exchange_plan": (_I, [_H, _I, C.POINTER(C.c_int32), C.POINTER(_I64)]),

@@ -12,14 +12,14 @@ import torch
 
 from .mps import mps_to_ranged_form, mps_to_standard_form
 from .precondition import Scaling, equilibrate_matrix, ruiz_precondition, ruiz_precondition_batch
-from .solver import check_composition, check_quad_diag, check_row_upper, is_mixed, pdlp_algorithm, resolve_device
+from .solver import check_composition, check_quad_diag, check_quad_matrix, check_row_upper, is_mixed, pdlp_algorithm, resolve_device
 from .sparse import CsrPair
 
 
 @dataclass
 class LPResult:
     x: torch.Tensor            # (n, 1) primal solution of the ORIGINAL problem (un-scaled when preconditioned)
-    objective: float           # c'x of the original problem
+    objective: float           # c'x of the original problem (+ 1/2 x'Dx, + 1/2 x'Qx with quad_diag / quad_matrix)
     iterations: int            # k
     restarts: int              # n
     kkt_passes: int            # j
@@ -69,7 +69,8 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
              fishnet: bool = False, comm=None, infeasibility_detect: bool = False, infeas_tol: float = 1e-4,
              precision: Optional[str] = None, adaptive_retry: bool = False, direct_exchange: bool = False,
              report: bool = True, pock_chambolle: bool = False, halpern: bool = False, q_upper=None,
-             ranged_rows: bool = False, quad_diag=None, halpern_restart: str = "kkt") -> LPResult:
+             ranged_rows: bool = False, quad_diag=None, halpern_restart: str = "kkt", quad_matrix=None,
+             quad_norm: Optional[float] = None) -> LPResult:
     """Solve ``min c'x, K[:m_ineq]x >= q[:m_ineq], K[m_ineq:]x = q[m_ineq:], l <= x <= u`` on the current HIP device.
 
     ``problem`` is an MPS path or ``(c, K, q, m_ineq, l, u)`` with ``K`` dense / COO / scipy-sparse / ``CsrPair``.
@@ -115,6 +116,18 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     ``direct_exchange`` (a flag of sharded solves), ``infeasibility_detect``, ``fishnet`` and ``adaptive_retry``.  With an MPS path the
     vector's length can only be compared with ``n`` after the file is read, which puts the problem on the device; everything else
     about it is checked first.  MPS ``QUADOBJ`` / ``QMATRIX`` sections are not read.
+    ``quad_matrix`` (n x n, anything ``CsrPair.from_any`` takes; not in the reference): a general convex quadratic objective,
+    ``min c'x + 1/2 x'Qx`` with ``Q`` sparse, symmetric and positive semidefinite: a factor covariance, a
+    least-squares term, MPC.  Symmetry, the size, finiteness and a non-negative diagonal are checked; POSITIVE SEMIDEFINITENESS IS THE
+    CALLER'S DUTY.  The solver takes the linearised step with a fixed step size that follows the primal weight (``rules.qp_eta``);
+    ``quad_norm`` overrides its estimate of ``||Q||_2`` (of the scaled ``Q`` when ``precondition``).  ``objective`` is
+    ``c'x + 1/2 x'Qx`` (``+ 1/2 x'Dx`` with ``quad_diag`` too), ``dual_objective`` is ``q'y + l'lam+ + u'lam- - 1/2 x'Qx (- 1/2 x'Dx)``
+    and ``reduced_costs`` are ``project_lambda_box(c + Qx + Dx - K'y)``; the returned ``x`` is projected onto ``[l, u]`` (it moves by
+    the rounding of the averaged iterate, a few eps; the objective and the residuals are those of the point before).  Works with ``precondition``, ``pock_chambolle``,
+    ``primal_weight_update``, ``q_upper`` / ``ranged_rows``, ``quad_diag``, ``x_init`` / ``y_init`` and ``report`` in float32 and
+    float64, with ``K`` on any product form; ``ValueError`` (before any device work) for a malformed matrix and together with
+    ``adaptive_stepsize``, ``halpern``, ``adaptive_retry``, ``infeasibility_detect``, ``precision="mixed"``, ``comm``,
+    ``direct_exchange`` and ``fishnet``.  With an MPS path the size is compared with ``n`` once the file is read.
     """
     _check_pock_chambolle(pock_chambolle, precondition)
     from .solver import check_halpern_restart
@@ -122,15 +135,16 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     from_file = isinstance(problem, (str, os.PathLike))
     if ranged_rows and (not from_file or q_upper is not None):
         raise ValueError("ranged_rows=True reads the RANGES rows of an MPS path; arrays carry q_upper themselves")
-    if q_upper is not None or ranged_rows or quad_diag is not None:
+    if q_upper is not None or ranged_rows or quad_diag is not None or quad_matrix is not None:
         is_mixed(precision)                     # (an unknown precision is its own error)
     check_composition(halpern=halpern, q_upper=q_upper is not None or ranged_rows, quad_diag=quad_diag is not None,
-                      adaptive=adaptive_stepsize, adaptive_retry=adaptive_retry, infeasibility_detect=infeasibility_detect,
+                      quad_matrix=quad_matrix is not None, adaptive=adaptive_stepsize, adaptive_retry=adaptive_retry, infeasibility_detect=infeasibility_detect,
                       mixed=precision is not None, comm=comm not in (None, False), fishnet=fishnet, direct_exchange=direct_exchange)
     if q_upper is not None:
         check_row_upper(problem[2], q_upper, problem[3])
     # (an MPS path: shape, sign and finiteness now, the length once the file is read)
     quad_diag = check_quad_diag(quad_diag, None if from_file or quad_diag is None else torch.as_tensor(problem[0]).numel())
+    quad_matrix = check_quad_matrix(quad_matrix, None if from_file or quad_matrix is None else torch.as_tensor(problem[0]).numel())
     device = resolve_device(device)
     if is_mixed(precision):
         dtype = torch.float64
@@ -158,11 +172,14 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     time_used, data_precond = 0.0, None
     if quad_diag is not None:
         quad_diag = check_quad_diag(quad_diag, c.numel())                # (a problem read from a file: its n is known only now)
-    Ks, cs, qs, ls, us, qus, ds = K, c, q, l, u, q_upper, quad_diag
-    if precondition and quad_diag is not None:
+    if quad_matrix is not None:
+        quad_matrix = check_quad_matrix(quad_matrix, c.numel()).to(device=device, dtype=dtype)
+    Ks, cs, qs, ls, us, qus, ds, Qs = K, c, q, l, u, q_upper, quad_diag, quad_matrix
+    if precondition and (quad_diag is not None or quad_matrix is not None):
         Ks, cs, qs, ls, us, *more, data_precond, time_used = ruiz_precondition(c, K, q, l, u, device=device, pock_chambolle=pock_chambolle,
-                                                                               q_upper=q_upper, quad_diag=quad_diag)
-        qus, ds = (more[0], more[1]) if q_upper is not None else (None, more[0])
+                                                                               q_upper=q_upper, quad_diag=quad_diag, quad_matrix=quad_matrix)
+        # (the optional values follow u_s in this order, each only when it was given)
+        qus, ds, Qs = (more.pop(0) if v is not None else None for v in (q_upper, quad_diag, quad_matrix))
     elif precondition and q_upper is not None:
         Ks, cs, qs, ls, us, qus, data_precond, time_used = ruiz_precondition(c, K, q, l, u, device=device, pock_chambolle=pock_chambolle,
                                                                              q_upper=q_upper)
@@ -178,9 +195,14 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     x, obj, k, n, j, status, total = pdlp_algorithm(
         Ks, m_ineq, cs, qs, ls, us, device, verbose=verbose, data_precond=data_precond, time_used=time_used, x_init=x_init,
         y_init=y_init, seed=seed, comm=comm, precision=precision, report=rep, **({} if qus is None else dict(q_upper=qus)),
-        **({} if ds is None else dict(quad_diag=ds)), **run)
+        **({} if ds is None else dict(quad_diag=ds)), **({} if Qs is None else dict(quad_matrix=Qs, quad_norm=quad_norm)), **run)
     if precondition:        # the reference returns the scaled iterate (quirk Q4); solve_lp un-scales: x = D_col x_s (pdhg.py:161)
         x = Scaling(*data_precond[:2]).unscale_x(x)
+    if quad_matrix is not None:
+        # The returned point is usually an averaged iterate, x_sum / eta_sum.  Of iterates that all sit on a bound this is the bound
+        # only up to the rounding of the two running sums (about one eps per four iterations of the period),
+        # and D_col (l / D_col) adds its own.  In exact arithmetic the average is inside the box: project it onto the caller's bounds.
+        x = torch.clamp(x.reshape(-1), min=torch.as_tensor(l).to(x).reshape(-1), max=torch.as_tensor(u).to(x).reshape(-1)).view_as(x)
     return LPResult(x, obj, k, n, j, status, total, **report_fields(rep))
 
 
@@ -318,6 +340,9 @@ def solve_lp_batch(problem: Union[str, os.PathLike, tuple], c=None, q=None, l=No
         if name == "precision":
             if v is not None:
                 raise ValueError(f"precision={v!r} has no batched form (float32 or float64 through dtype)")
+        elif name == "quad_matrix":
+            if v is not None:
+                raise ValueError("quad_matrix has no batched form")
         elif name in _BATCH_UNSUPPORTED:
             if v:
                 raise ValueError(f"{name} has no batched form")

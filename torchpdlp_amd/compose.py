@@ -1,16 +1,19 @@
-"""The switches ``halpern``, ``q_upper`` and ``quad_diag`` against the forms they do not have: the refusals' text and the rule (the library: PDLP_ERR_STATE)."""
+"""The switches ``halpern``, ``q_upper``, ``quad_diag`` and ``quad_matrix`` against the forms they do not have: the refusals' text and the rule (the library: PDLP_ERR_STATE)."""
 HALPERN_REFUSED = ("halpern=True runs the fixed step on one GPU in float32 or float64: not with adaptive, adaptive_retry, "
                    "infeasibility_detect, mixed precision or a communicator")
 RANGED_REFUSED = ("q_upper (two-sided rows) runs on one GPU in float32 or float64: not with mixed precision, a communicator, "
                   "infeasibility_detect, fishnet or adaptive_retry")
 QUAD_REFUSED = ("quad_diag (diagonal quadratic objective) runs on one GPU in float32 or float64: not with mixed precision, a communicator, "
                 "direct_exchange, infeasibility_detect, fishnet or adaptive_retry")
+QMAT_REFUSED = ("quad_matrix (sparse quadratic objective) runs the fixed, linearised step on one GPU in float32 or float64: not with "
+                "adaptive, halpern, adaptive_retry, infeasibility_detect, mixed precision, a communicator, direct_exchange or fishnet")
 
 
-def check_composition(*, halpern=False, q_upper=False, quad_diag=False, adaptive=False, adaptive_retry=False,
+def check_composition(*, halpern=False, q_upper=False, quad_diag=False, quad_matrix=False, adaptive=False, adaptive_retry=False,
                       infeasibility_detect=False, mixed=False, comm=False, fishnet=False, direct_exchange=False):
     """``ValueError`` with the switch's message if a switch that is on meets a form it does not have (arguments by truth value; an
-    entry point leaves out what it has no flag for).  More than one refusal: Halpern, then ``q_upper``, then ``quad_diag``."""
+    entry point leaves out what it has no flag for).  More than one refusal: Halpern, then ``q_upper``, then ``quad_diag``, then
+    ``quad_matrix``."""
     one_gpu_only = adaptive_retry or infeasibility_detect or mixed or comm or direct_exchange
     if halpern and (adaptive or one_gpu_only):         # (only the fixed step; it does run behind a fishnet start)
         raise ValueError(HALPERN_REFUSED)
@@ -18,3 +21,5 @@ def check_composition(*, halpern=False, q_upper=False, quad_diag=False, adaptive
         raise ValueError(RANGED_REFUSED)
     if quad_diag and (one_gpu_only or fishnet):
         raise ValueError(QUAD_REFUSED)
+    if quad_matrix and (adaptive or halpern or one_gpu_only or fishnet):      # (the linearised step: fixed, and not reflected)
+        raise ValueError(QMAT_REFUSED)

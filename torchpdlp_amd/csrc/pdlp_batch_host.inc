@@ -18,7 +18,7 @@ int batch_check(pdlp_handle h, const pdlp_batch* b)
         !b->live || !b->action || !b->part || !b->out)
         return PDLP_ERR_INVALID;
     if (!whole_problem(h) || h->mixed || h->delta) return PDLP_ERR_STATE;     // single GPU, one precision
-    if (h->obj_diag) return PDLP_ERR_STATE;      // (the batch kernels know the linear objective only: pdlp_set_objective_diag)
+    if (h->obj_diag || h->obj_mat.on) return PDLP_ERR_STATE;      // (the batch kernels know the linear objective only)
     if (h->p.n < 1 || h->p.m < 1) return PDLP_ERR_INVALID;
     if (h->bm.K_val && h->bm.Bp != b->Bp) return PDLP_ERR_INVALID;      // the attached populations have another width
     return PDLP_OK;
@@ -330,7 +330,7 @@ int pdlp_batch_attach_matrices(pdlp_handle h, int Bp, const void* K_valB, const 
         return PDLP_OK;
     }
     if (!K_valB || !KT_valB || Bp < 8 || Bp % 8 != 0 || (d_colB == nullptr) != (d_rowB == nullptr)) return PDLP_ERR_INVALID;
-    if (!whole_problem(h) || h->mixed || h->delta || h->obj_diag) return PDLP_ERR_STATE;     // single GPU, one precision, linear objective
+    if (!whole_problem(h) || h->mixed || h->delta || h->obj_diag || h->obj_mat.on) return PDLP_ERR_STATE;     // single GPU, one precision, linear objective
     h->bm.Bp = Bp;
     h->bm.K_val = K_valB; h->bm.KT_val = KT_valB;
     h->bm.d_col = d_colB; h->bm.d_row = d_rowB;

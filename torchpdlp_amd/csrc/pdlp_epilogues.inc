@@ -75,6 +75,26 @@ template <typename T> __device__ __forceinline__ T quad_prox(T z, T tau, T dj) {
 // from the SCALED pair (d_s = d D_col^2, x_s = x / D_col), of which it is invariant, so UNSCALE needs no factor of its own.
 template <typename T> __device__ __forceinline__ double quad_half(T dj, T xj) { return 0.5 * (double)dj * ((double)xj * (double)xj); }
 
+// Sparse quadratic objective (pdlp_set_objective_matrix): min c'x + 1/2 x'Qx, Q symmetric positive semidefinite.  The prox of such an
+// objective is not closed form, so the iteration takes the linearised step: the epilogue of the product Q x stores the gradient of
+// the objective, g_j = c_j + (Q x)_j, and every variable-side functor then reads g where it reads c (the host swaps the pointer; no
+// functor changes).  SUM (the KKT pass and the report): acc[0] takes x_j (Q x)_j in double, which finishes as x'Qx; the iteration's
+// instantiation has no sum.  Over Q's own row blocks only (k_csr_fused / k_long_rows): Q has neither tiles nor a sorted copy.
+template <typename T> struct ObjGradPre { T cj, xj; };
+template <typename T, bool SUM> struct ObjGradEpi {
+    static constexpr int NA = SUM ? 1 : 0;
+    const T* c; const T* x; T* g;
+    typedef ObjGradPre<T> Pre;
+    __device__ void load() {}
+    __device__ Pre pre(int j) const { return Pre{c[j], x[j]}; }
+    __device__ void operator()(int j, T s, double* acc) const { (*this)(j, s, pre(j), acc); }
+    __device__ void operator()(int j, T s, const Pre& p, double* acc) const
+    {
+        g[j] = p.cj + s;
+        if (SUM) acc[0] += (double)p.xj * (double)s;
+    }
+};
+
 // ---- the arithmetic every kernel file shares (this file is included before all of them) --------------------------------------
 // lam = project_lambda_box(g) (helpers.py:21-37) with the bound classes read off l, u: a variable without a lower bound takes
 // min(g, 0), one without an upper bound max(g, 0), a free one 0, a boxed one g.  ninf / pinf: the classes, for the callers' own use.

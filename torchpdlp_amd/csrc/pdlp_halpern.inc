@@ -55,10 +55,11 @@ template <typename T> int halpern_fixed_point_t(pdlp_handle h)
     return PDLP_OK;
 }
 
-// the forms the Halpern mode does not have: mixed precision / delta mode, a shard of a problem, an exchange of any kind, graph replay
+// the forms the Halpern mode does not have: mixed precision / delta mode, a shard of a problem, an exchange of any kind, graph replay,
+// and a sparse quadratic objective (the reflected operator 2T - I of the linearised step is not non-expansive)
 inline bool halpern_refused(pdlp_handle h)
 {
-    return !plain_single(h) || h->graph_ok;
+    return !plain_single(h) || h->graph_ok || h->obj_mat.on;
 }
 
 }  // namespace

@@ -163,6 +163,9 @@ struct Carried {
     // the running sums stop being complete inside a period (at since_reset == 0 nothing has been added yet: nothing is missing)
     void sums_end() { if (since_reset > 0) sums_broken = true; }
     void operands_changed() { drop_candidates(); kty_cur = -1; }               // what a KKT pass kept belongs to the other q_upper / d
+    // pdlp_set_objective_matrix: Q set, replaced or taken away.  The gradient buffer g = c + Q x is never carried -- every primal
+    // half-step and every KKT pass forms it anew -- so only what a KKT pass kept goes, as with the other operands of the objective
+    void objective_matrix_changed() { operands_changed(); }
     // pdlp_set_delta: no product survives the switch.  The sums' fields stay as they are, as they always did: delta mode reads none.
     void drop_products() { kx_valid = false; drop_candidates(); kty_cur = -1; anchors_valid = dy_folded = false; }
     // nothing carried survives, the running sums of this period included.  (One list where pdlp_halpern_iterate and
@@ -205,7 +208,12 @@ struct pdlp_solver {
     int ineq_end = 0;             // local rows below this index are inequalities
     const void* obj_diag = nullptr;  // diagonal quadratic objective (pdlp_set_objective_diag): c'x + 1/2 x'Dx, d of the variables; the caller's memory
     const void* q_upper = nullptr;   // two-sided rows (pdlp_set_row_upper): q <= K x <= q_upper on the inequality rows; the caller's memory
-    Schedule sK, sKT;
+    // sparse quadratic objective (pdlp_set_objective_matrix): c'x + 1/2 x'Qx.  Q's CSR arrays are the caller's memory; sQ is its
+    // row-block schedule, built into the caller's `work`; the gradient g = c + Q x of the point a half-step or a KKT pass looks at
+    // lives in lam_prev (the infeasibility detector's, which is refused while Q is set); red[OBJ_XQX] receives x'Qx of a KKT pass
+    struct ObjMatrix { bool on = false; const int32_t* colidx = nullptr; const void* val = nullptr; } obj_mat;
+    static constexpr int OBJ_XQX = PDLP_NRED - 1;
+    Schedule sK, sKT, sQ;
     char* xb[3] = {};             // full-length primal buffers; roles via ix_*
     char* yb[3] = {};
     int ix_cur = 0, ix_prev = 1, ix_avg = 2;  // (x and y rotate together)
@@ -280,7 +288,7 @@ inline bool plain_single(pdlp_handle h)         // ... in one precision and outs
 {
     return whole_problem(h) && !h->mixed && !h->delta && !h->comm && !h->peer.on;
 }
-inline bool has_extension(pdlp_handle h) { return h->q_upper || h->obj_diag; }    // two-sided rows or a quadratic objective
+inline bool has_extension(pdlp_handle h) { return h->q_upper || h->obj_diag || h->obj_mat.on; }    // two-sided rows or a quadratic objective
 inline bool mid_split_product(pdlp_handle h) { return h->sK.pending || h->sKT.pending; }      // in the middle of a split product
 
 void drop_graphs(pdlp_handle h)

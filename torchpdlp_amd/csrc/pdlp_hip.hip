@@ -14,8 +14,9 @@
 //     pdlp_loaders.inc        RCCL and roctx resolved with dlopen, Range; pdlp_trace_enable / pdlp_range_*
 //     pdlp_handle.inc         Schedule, Carried (which carried product still belongs to its vector: the rules and the only writers),
 //                             struct pdlp_solver, the workspace Layout and its capacities, check / bind / free
-//     pdlp_schedule.inc       row-block and long-row schedules built on the host, the split-product planner (configure_split)
-//     pdlp_products.inc       launch_mat and what it is made of, the shared launch helpers, the half-steps
+//     pdlp_schedule.inc       row-block and long-row schedules built on the host (K, K' and the objective's Q), the split-product
+//                             planner (configure_split)
+//     pdlp_products.inc       launch_mat and what it is made of, the products with Q, the shared launch helpers, the half-steps
 //     pdlp_delta.inc          delta mode (mixed precision): half-steps and KKT from anchors; pdlp_set_delta / _anchors / _state
 //     pdlp_kkt.inc            KKT pass, report, flush / average / distance / infeasibility / power iteration; pdlp_restart
 //     pdlp_population.inc     the mv_* launchers; pdlp_mv_combine
@@ -378,6 +379,50 @@ static int set_operand(pdlp_handle h, const void* pdlp_solver::*operand, const v
 int pdlp_set_row_upper(pdlp_handle h, const void* q_upper_local) { return set_operand(h, &pdlp_solver::q_upper, q_upper_local); }
 int pdlp_set_objective_diag(pdlp_handle h, const void* d_local) { return set_operand(h, &pdlp_solver::obj_diag, d_local); }
 
+int pdlp_objective_matrix_bytes(pdlp_handle h, int64_t nnz, int64_t* bytes)
+{
+    if (!h || !bytes || nnz < 0) return PDLP_ERR_INVALID;
+    *bytes = objective_matrix_layout(h->p.n, nnz, (int64_t)h->es).bytes;
+    return PDLP_OK;
+}
+
+// Q set, replaced or taken away (NULL arrays).  The forms without it are those without the other extensions (set_operand), and graph
+// replay: a captured pair would have to hold the gradient product, which PDLP_OPT_GRAPH refuses while Q is set.
+int pdlp_set_objective_matrix(pdlp_handle h, const int64_t* rowptr, const int32_t* colidx, const void* val, void* work, int64_t work_bytes)
+{
+    if (!h) return PDLP_ERR_INVALID;
+    const bool on = rowptr || colidx || val;
+    if (on && (!rowptr || !colidx || !val)) return PDLP_ERR_INVALID;
+    if (on && (!plain_single(h) || h->graph_ok)) return PDLP_ERR_STATE;
+    if (mid_split_product(h)) return PDLP_ERR_STATE;
+    if (on) {
+        const int64_t n = h->p.n;
+        std::vector<int64_t> rp((size_t)n + 1, 0);
+        HIP_TRY(hipMemcpyAsync(rp.data(), rowptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));     // (ordered behind whatever produced the arrays on that stream)
+        if (rp[0] != 0) return PDLP_ERR_INVALID;
+        for (int64_t r = 0; r < n; ++r) if (rp[(size_t)r + 1] < rp[(size_t)r]) return PDLP_ERR_INVALID;
+        if (!work || work_bytes < objective_matrix_layout(n, rp[(size_t)n], (int64_t)h->es).bytes || ((uintptr_t)work & 255u)) return PDLP_ERR_WORKSPACE;
+        const int rc = upload_objective_schedule(h, rp, (char*)work);
+        if (rc != PDLP_OK) return rc;
+    } else {
+        h->sQ = Schedule();
+    }
+    drop_graphs(h);
+    h->obj_mat.on = on;
+    h->obj_mat.colidx = colidx;
+    h->obj_mat.val = val;
+    h->carry.objective_matrix_changed();
+    return PDLP_OK;
+}
+
+int pdlp_objective_product(pdlp_handle h, const void* x_full, void* out_local)
+{
+    if (!h || !x_full || !out_local) return PDLP_ERR_INVALID;
+    if (!h->obj_mat.on) return PDLP_ERR_STATE;
+    return DISPATCH(h, obj_product_t, h, x_full, out_local);
+}
+
 int pdlp_get_iterate(pdlp_handle h, int which, void* x_local, void* y_local)
 {
     if (!h) return PDLP_ERR_INVALID;
@@ -419,6 +464,7 @@ int pdlp_get_scalars(pdlp_handle h, double out[PDLP_NSCAL])
 int pdlp_primal_half(pdlp_handle h, int adaptive)
 {
     if (!h) return PDLP_ERR_INVALID;
+    if (adaptive && h->obj_mat.on) return PDLP_ERR_STATE;      // (the linearised step of a sparse quadratic objective: fixed step only)
     h->carry.buffers_reassigned();
     if (h->delta) return delta_primal_half(h, adaptive);
     return DISPATCH(h, primal_half_t, h, adaptive);
@@ -427,6 +473,7 @@ int pdlp_primal_half(pdlp_handle h, int adaptive)
 int pdlp_dual_half(pdlp_handle h, int adaptive)
 {
     if (!h) return PDLP_ERR_INVALID;
+    if (adaptive && h->obj_mat.on) return PDLP_ERR_STATE;
     h->carry.buffers_reassigned();
     if (h->delta) return delta_dual_half(h, adaptive);
     return DISPATCH(h, dual_half_t, h, adaptive);
@@ -470,6 +517,7 @@ int pdlp_set_option(pdlp_handle h, int option, int64_t value)
             return PDLP_OK;
         case PDLP_OPT_KTY_REUSE: h->no_kty_reuse = value == 0; return PDLP_OK;
         case PDLP_OPT_GRAPH:
+            if (value != 0 && h->obj_mat.on) return PDLP_ERR_STATE;      // (no replay with a sparse quadratic objective)
             drop_graphs(h);
             if (h->graph_ok) h->carry.sums_end();      // (nor while replay was on)
             h->graph_ok = value != 0 && h->side_ok && !h->comm;
@@ -537,7 +585,7 @@ int pdlp_tile_limits(pdlp_handle h, int32_t out[6])
 int pdlp_adaptive_retry(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->delta || mid_split_product(h) || h->graph_ok) return PDLP_ERR_STATE;   // (float32 / float64 handles, between iterations)
+    if (h->delta || mid_split_product(h) || h->graph_ok || h->obj_mat.on) return PDLP_ERR_STATE;   // (float32 / float64 handles, between iterations, no Q)
     // the scalars: the rejected trial's weight leaves eta_total again, nothing is pending (the trial's epilogues have folded the
     // previous iterate's weight into the sums: the repeated half-steps must add nothing), k goes back; eta keeps the rule's eta'
     hipLaunchKernelGGL(k_retry_scalars, dim3(1), dim3(1), 0, h->stream, h->sc);
@@ -555,6 +603,7 @@ int pdlp_adaptive_retry(pdlp_handle h)
 int pdlp_adaptive_reduce(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
+    if (h->obj_mat.on) return PDLP_ERR_STATE;
     launch_adaptive_rule(h, 0);
     HIP_TRY(hipGetLastError());
     return PDLP_OK;
@@ -563,6 +612,7 @@ int pdlp_adaptive_reduce(pdlp_handle h)
 int pdlp_adaptive_update(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
+    if (h->obj_mat.on) return PDLP_ERR_STATE;
     WITH_T(h->p.dtype, hipLaunchKernelGGL(k_adaptive_update<T>, dim3(1), dim3(1), 0, h->stream, h->sc, h->red));
     HIP_TRY(hipGetLastError());
     return PDLP_OK;
@@ -572,6 +622,7 @@ int pdlp_iterate(pdlp_handle h, int iters, int adaptive)
 {
     if (!h || iters < 0) return PDLP_ERR_INVALID;
     adaptive = adaptive ? 1 : 0;
+    if (adaptive && h->obj_mat.on) return PDLP_ERR_STATE;      // (sparse quadratic objective: fixed step only)
     h->carry.buffers_reassigned();
     char rname[64];
     if (g_roctx.level > 0) std::snprintf(rname, sizeof rname, "pdlp: %d %s iterations", iters, adaptive ? "adaptive" : "fixed-step");
@@ -657,7 +708,7 @@ int pdlp_mark_restart_point(pdlp_handle h)
 int pdlp_infeas_reset(pdlp_handle h)
 {
     if (!h) return PDLP_ERR_INVALID;
-    if (h->obj_diag) return PDLP_ERR_STATE;      // (no call of the detector with a quadratic objective: pdlp_set_objective_diag)
+    if (h->obj_diag || h->obj_mat.on) return PDLP_ERR_STATE;      // (no call of the detector with a quadratic objective)
     HIP_TRY(hipMemsetAsync(h->lam_prev, 0, h->nl * h->es, h->stream));          // pdhg.py:39-40
     return PDLP_OK;
 }
@@ -679,7 +730,7 @@ int pdlp_infeas_local(pdlp_handle h, double tol)
 int pdlp_infeas_finish(pdlp_handle h, double tol, int32_t* status, double diag[8])
 {
     if (!h || !status || !diag) return PDLP_ERR_INVALID;
-    if (h->obj_diag) return PDLP_ERR_STATE;
+    if (h->obj_diag || h->obj_mat.on) return PDLP_ERR_STATE;
     double r[PDLP_NRED];
     const int rc = pdlp_read_red(h, r);
     if (rc != PDLP_OK) return rc;

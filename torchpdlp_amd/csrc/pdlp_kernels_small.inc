@@ -287,6 +287,16 @@ __global__ __launch_bounds__(BLOCK) void k_average(int64_t n, T* __restrict__ av
 
 __global__ void k_clear_pending(double* sc) { sc[S_WPEND] = 0.0; }
 
+// Sparse quadratic objective: the end of a KKT pass or report whose variable-side functor ran over g = c + Q x.  It left
+// g'x = c'x + x'Qx in red[3]; with h = 1/2 x'Qx (red[xqx] holds x'Qx, the sum of ObjGradEpi) the contract of the six sums is
+// red[3] = c'x + h and red[1] = its own term - h (include/pdlp_hip.h, pdlp_set_objective_matrix).
+__global__ void k_obj_matrix_finish(double* red, int xqx)
+{
+    const double h = 0.5 * red[xqx];
+    red[3] -= h;
+    red[1] -= h;
+}
+
 // lam = project_lambda_box(g) (helpers.py:21-37) with the bound classes read off l, u.  project_lambda's arithmetic, written out as
 // one expression: called here, the vectorised float32 loop of this kernel comes out with other selects.
 template <typename T>

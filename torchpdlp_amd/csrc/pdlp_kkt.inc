@@ -7,7 +7,8 @@
 namespace {
 
 // the functors of a KKT pass and of a report: the constraint side with q_upper when the handle has two-sided rows (RANGED), the
-// variable side with d when it has a diagonal quadratic objective (QUAD)
+// variable side with d when it has a diagonal quadratic objective (QUAD); with a sparse quadratic objective the variable side reads
+// the gradient g = c + Q x of the evaluated point where it reads c (obj_linear: kkt_pass_begin has formed it)
 template <typename T, bool UNSCALE, bool RANGED> KktPrimalEpi<T, UNSCALE, RANGED> kkt_primal_epi(pdlp_handle h, int ix, const T* drow, T* kx_out)
 {
     KktPrimalEpi<T, UNSCALE, RANGED> ep{yloc<T>(h, ix), (const T*)h->p.q, drow, kx_out, h->ineq_end};
@@ -16,7 +17,7 @@ template <typename T, bool UNSCALE, bool RANGED> KktPrimalEpi<T, UNSCALE, RANGED
 }
 template <typename T, bool UNSCALE, bool QUAD> KktDualEpi<T, UNSCALE, QUAD> kkt_dual_epi(pdlp_handle h, int ix, const T* dcol, T* kty_out)
 {
-    KktDualEpi<T, UNSCALE, QUAD> ed{xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol, kty_out};
+    KktDualEpi<T, UNSCALE, QUAD> ed{xloc<T>(h, ix), obj_linear<T>(h), (const T*)h->p.l, (const T*)h->p.u, dcol, kty_out};
     set_optional(ed.diag, h);
     return ed;
 }
@@ -28,9 +29,19 @@ template <typename T, bool UNSCALE, bool RANGED> ReportPrimalEpi<T, UNSCALE, RAN
 }
 template <typename T, bool UNSCALE, bool QUAD> ReportDualEpi<T, UNSCALE, QUAD> report_dual_epi(pdlp_handle h, int ix, const T* dcol, T* buf)
 {
-    ReportDualEpi<T, UNSCALE, QUAD> ed{buf, xloc<T>(h, ix), (const T*)h->p.c, (const T*)h->p.l, (const T*)h->p.u, dcol};
+    ReportDualEpi<T, UNSCALE, QUAD> ed{buf, xloc<T>(h, ix), obj_linear<T>(h), (const T*)h->p.l, (const T*)h->p.u, dcol};
     set_optional(ed.diag, h);
     return ed;
+}
+
+// Sparse quadratic objective: a KKT pass or report first forms g = c + Q x of the evaluated point -- one product with Q per pass,
+// also for an average whose other products come out of the running sums -- and x'Qx with it; after the six sums are finished the
+// objective's two slots go from g'x = c'x + x'Qx to the contract's c'x + 1/2 x'Qx and - 1/2 x'Qx (include/pdlp_hip.h).
+template <typename T> int kkt_pass_begin(pdlp_handle h, int ix) { return h->obj_mat.on ? obj_gradient<T, true>(h, ix) : PDLP_OK; }
+inline int kkt_pass_end(pdlp_handle h, int gridA, int gridB)
+{
+    const int rc = finalize_kkt(h, gridA, gridB);
+    return rc == PDLP_OK && h->obj_mat.on ? obj_matrix_finish(h) : rc;
 }
 
 template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int kkt_local_u(pdlp_handle h, int which)
@@ -39,6 +50,7 @@ template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int 
     const T* dcol = UNSCALE ? (const T*)h->p.d_col : nullptr;
     const T* drow = UNSCALE ? (const T*)h->p.d_row : nullptr;
     int rc, gridA = grid_of(h->sKT, h->nl), gridB = grid_of(h->sK, h->ml);
+    if ((rc = kkt_pass_begin<T>(h, ix)) != PDLP_OK) return rc;
     const bool kx_carried = which == PDLP_CUR && h->carry.kx_valid && !h->no_running;
     if (which == PDLP_AVG && h->carry.avg_products) {
         // K'y_avg (ktyb[1]) and K x_avg (kxb[2]) were formed from the running sums by pdlp_compute_average: two vector passes
@@ -66,7 +78,7 @@ template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int 
             if ((rc = launch_csr<T>(h, false, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
         }
     }
-    if ((rc = finalize_kkt(h, gridA, gridB)) != PDLP_OK) return rc;
+    if ((rc = kkt_pass_end(h, gridA, gridB)) != PDLP_OK) return rc;
     h->carry.kkt_kept(which, kx_carried);
     return PDLP_OK;
 }
@@ -90,6 +102,7 @@ template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int 
     const T* dcol = UNSCALE ? (const T*)h->p.d_col : nullptr;
     const T* drow = UNSCALE ? (const T*)h->p.d_row : nullptr;
     int rc, gridA = grid_of(h->sKT, h->nl), gridB = grid_of(h->sK, h->ml);
+    if ((rc = kkt_pass_begin<T>(h, ix)) != PDLP_OK) return rc;
     if (rc_local) {
         StoreEpi<T> st{(T*)rc_local};
         if ((rc = launch_csr<T>(h, true, h->yb[ix], st, h->partA)) != PDLP_OK) return rc;
@@ -110,7 +123,7 @@ template <typename T, bool UNSCALE, bool RANGED = false, bool QUAD = false> int 
         const auto ep = kkt_primal_epi<T, UNSCALE, RANGED>(h, ix, drow, nullptr);
         if ((rc = launch_csr<T>(h, false, h->xb[ix], ep, h->partB)) != PDLP_OK) return rc;
     }
-    return finalize_kkt(h, gridA, gridB);
+    return kkt_pass_end(h, gridA, gridB);
 }
 
 template <typename T> int report_local_t(pdlp_handle h, int which, int unscaled, void* rc_local, void* act_local)

@@ -2,7 +2,8 @@
 // (CSR row blocks, tiles in one launch, tiles in panel groups, a split product's phases and output pieces); launch_csr picks the
 // matrix type of the handle's precision.  Then the launches every later file shares (epilogue_pass, finalize_kkt, iterate_index,
 // launch_adaptive_rule, with_flags), the primal and dual half-steps, their early parts for sharded problems (half_begin_t,
-// half_chunk_t, half_piece) and the plain product (spmv_t).
+// half_chunk_t, half_piece) and the plain product (spmv_t).  The objective's matrix Q (pdlp_set_objective_matrix) has its own
+// launcher over the CSR form alone (launch_obj_matrix) and the gradient product ahead of every primal half-step (obj_gradient).
 // Part of pdlp_hip.hip (included at file scope; not a translation unit of its own).  Needs: pdlp_schedule.inc and what is before it.
 // ------------------------------------------------------------------------------------------------
 namespace {
@@ -37,6 +38,20 @@ template <typename T, typename TV>
 void launch_phase(pdlp_handle h, const Schedule& s, int rows, const void* vin, hipStream_t stream, int phase, int b0 = 0, int nbl = -1)
 {
     launch_tiled_groups<T, TV>(h, s, rows, vin, stream, s.ph_slots[phase], s.ph_cnt[phase], s.ptab + s.ph_off[phase], s.ph_slot0[phase], b0, nbl);
+}
+
+// the CSR form of a product: the row blocks of schedule `s` over the arrays (ci, va) -- K's, K''s or Q's -- and the epilogue of the
+// rows that were multiplied in chunks; partial sums of s.grid (+ s.lgrid) workgroups
+template <typename T, typename TV, class Epi, bool SORTED>
+void launch_csr_rows(pdlp_handle h, const Schedule& s, const int32_t* ci, const TV* va, const void* vin, Epi epi, double* partials)
+{
+    // (s.rplo, the low words of the row pointers: csr_pass needs block-relative offsets only)
+    hipLaunchKernelGGL((k_csr_fused<T, TV, Epi, SORTED>), dim3(s.grid), dim3(BLOCK), 0, h->stream, s.blk, s.nblk, s.lch, s.nchunks,
+                       (T*)s.longpart, s.rplo, ci, va, SORTED ? s.sidx : (const uint32_t*)nullptr, SORTED ? (const TV*)s.sval : (const TV*)nullptr,
+                       SORTED ? s.cbase : (const int32_t*)nullptr, (const T*)vin, epi, partials);
+    if (s.nlong > 0)
+        hipLaunchKernelGGL((k_long_rows<T, Epi>), dim3(s.lgrid), dim3(BLOCK), 0, h->stream, s.lrow, s.lptr, s.nlong,
+                           (const T*)s.longpart, epi, partials + (size_t)s.grid * NACC);
 }
 
 // one product with K (or K') over the vector vin with the epilogue fused: T = type of vin, of the row sums and of what the
@@ -113,19 +128,10 @@ int launch_mat(pdlp_handle h, bool transpose, const void* vin, Epi epi, double* 
         HIP_TRY(hipGetLastError());
         return PDLP_OK;
     }
-    const uint32_t* rp = s.rplo;          // (low words of the row pointers: csr_pass needs block-relative offsets only)
     const int32_t* ci = transpose ? h->p.KT_colidx : h->p.K_colidx;
     const TV* va = (const TV*)(transpose ? h->p.KT_val : h->p.K_val);
-    if (s.sidx)
-        hipLaunchKernelGGL((k_csr_fused<T, TV, Epi, true>), dim3(s.grid), dim3(BLOCK), 0, h->stream, s.blk, s.nblk, s.lch, s.nchunks,
-                           (T*)s.longpart, rp, ci, va, s.sidx, (const TV*)s.sval, s.cbase, (const T*)vin, epi, partials);
-    else
-        hipLaunchKernelGGL((k_csr_fused<T, TV, Epi, false>), dim3(s.grid), dim3(BLOCK), 0, h->stream, s.blk, s.nblk, s.lch, s.nchunks,
-                           (T*)s.longpart, rp, ci, va, (const uint32_t*)nullptr, (const TV*)nullptr, (const int32_t*)nullptr,
-                           (const T*)vin, epi, partials);
-    if (s.nlong > 0)
-        hipLaunchKernelGGL((k_long_rows<T, Epi>), dim3(s.lgrid), dim3(BLOCK), 0, h->stream, s.lrow, s.lptr, s.nlong,
-                           (const T*)s.longpart, epi, partials + (size_t)s.grid * NACC);
+    if (s.sidx) launch_csr_rows<T, TV, Epi, true>(h, s, ci, va, vin, epi, partials);
+    else launch_csr_rows<T, TV, Epi, false>(h, s, ci, va, vin, epi, partials);
     HIP_TRY(hipGetLastError());
     return PDLP_OK;
 }
@@ -228,11 +234,52 @@ template <typename T> void set_optional(ObjDiag<T, true>& o, pdlp_handle h) { o.
 template <typename T> void set_optional(RowUpper<T, false>&, pdlp_handle) {}
 template <typename T> void set_optional(ObjDiag<T, false>&, pdlp_handle) {}
 
+// ---- the objective's matrix Q (pdlp_set_objective_matrix) -----------------------------------------------------------------------
+// A product with Q over its own schedule and the caller's arrays, in the working type; the CSR form only (Q has neither tiles nor a
+// sorted copy, and no epilogue of its own is built for the tiled kernels).  Q is a matrix of a whole problem on one GPU: no split
+// product is ever pending on such a handle.
+template <typename T, class Epi> int launch_obj_matrix(pdlp_handle h, const void* vin, Epi epi, double* partials)
+{
+    if (h->sQ.nblk == 0) return PDLP_OK;
+    launch_csr_rows<T, T, Epi, false>(h, h->sQ, h->obj_mat.colidx, (const T*)h->obj_mat.val, vin, epi, partials);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+// what the variable-side functors read as the objective's linear term: c, or the gradient g = c + Q x that obj_gradient has just formed
+template <typename T> const T* obj_linear(pdlp_handle h) { return h->obj_mat.on ? (const T*)h->lam_prev : (const T*)h->p.c; }
+
+// g = c + Q x of iterate buffer `ix` into the gradient buffer; SUM: also x'Qx into red[OBJ_XQX], through partA (before the pass that
+// follows reuses it: the stream orders the two)
+template <typename T, bool SUM> int obj_gradient(pdlp_handle h, int ix)
+{
+    ObjGradEpi<T, SUM> e{(const T*)h->p.c, xloc<T>(h, ix), (T*)h->lam_prev};
+    const int rc = launch_obj_matrix<T>(h, h->xb[ix], e, h->partA);
+    if (rc != PDLP_OK || !SUM) return rc;
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partA, grid_of(h->sQ, h->nl), 1, h->red, (int)pdlp_solver::OBJ_XQX);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+// the end of a KKT pass or report over g: the objective's slots from g'x to the contract's c'x + 1/2 x'Qx (k_obj_matrix_finish)
+inline int obj_matrix_finish(pdlp_handle h)
+{
+    hipLaunchKernelGGL(k_obj_matrix_finish, dim3(1), dim3(1), 0, h->stream, h->red, (int)pdlp_solver::OBJ_XQX);
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
+template <typename T> int obj_product_t(pdlp_handle h, const void* x_full, void* out_local)
+{
+    StoreEpi<T> e{(T*)out_local};
+    return launch_obj_matrix<T>(h, x_full, e, h->partA);
+}
+
 // QUAD: the handle has a diagonal quadratic objective (pdlp_set_objective_diag: float32 / float64, one GPU, no exchange -- so never
 // PEER)
 template <typename T, bool ADAPT, bool PEER, bool QUAD = false> int primal_half_e(pdlp_handle h, int src, T* ksum, const PieceCtl& pc)
 {
-    PrimalEpi<T, ADAPT, PEER, QUAD> e{xloc<T>(h, h->ix_cur), xloc<T>(h, h->ix_prev), (T*)h->xbar + h->p.col0, (const T*)h->p.c,
+    PrimalEpi<T, ADAPT, PEER, QUAD> e{xloc<T>(h, h->ix_cur), xloc<T>(h, h->ix_prev), (T*)h->xbar + h->p.col0, obj_linear<T>(h),
                                       (const T*)h->p.l, (const T*)h->p.u, (T*)h->x_sum, h->sc, ksum};
     peer_targets(h, e.peer, 0);
     set_optional(e.diag, h);
@@ -260,6 +307,12 @@ template <typename T> int primal_half_t(pdlp_handle h, int adaptive)
     T* ksum = (c.since_reset > 0 && !c.kty_tail_done && !c.sums_broken && !h->no_running && !h->graph_ok) ? (T*)h->kty_sum : nullptr;
     const PieceCtl pc = piece_ctl(h, h->sKT, src < 0);
     if (pc.skip) return PDLP_OK;                             // (all of this half-step went out with piece 0)
+    // sparse quadratic objective: the linearised step takes the gradient c + Q x of the current x where it takes c -- one more product
+    // ahead of EVERY primal half-step, the vector-pass form over a kept K'y included
+    if (h->obj_mat.on) {
+        const int rc = obj_gradient<T, false>(h, h->ix_cur);
+        if (rc != PDLP_OK) return rc;
+    }
     if (h->obj_diag) return with_flags([&](auto A) { return primal_half_e<T, A.value, false, true>(h, src, ksum, pc); }, adaptive);
     // (inside the direct exchange the epilogue also stores xbar into the peers: its own instantiations)
     return with_flags([&](auto A, auto P) { return primal_half_e<T, A.value, P.value>(h, src, ksum, pc); }, adaptive, h->peer.active);

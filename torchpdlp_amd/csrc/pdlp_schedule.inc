@@ -1,5 +1,5 @@
 // pdlp_schedule.inc -- how the work of a product is cut up: the row-block and long-row schedules of the CSR kernel, built on the
-// host and uploaded at pdlp_create; the pieces of a chunked exchange (plan_bounds); and the planner of a sharded problem's split
+// host and uploaded at pdlp_create (K, K') or by pdlp_set_objective_matrix (Q, into the caller's memory); the pieces of a chunked exchange (plan_bounds); and the planner of a sharded problem's split
 // products (configure_split: which panels belong to which phase of the exchange, how many panel groups each phase gets, in which
 // pieces the result leaves), with the helpers that turn an output piece into rows and grids.
 // Part of pdlp_hip.hip (included at file scope; not a translation unit of its own).  Needs: pdlp_handle.inc.
@@ -46,47 +46,73 @@ void build_schedule_host(const std::vector<int64_t>& rp, int64_t rows, std::vect
     }
 }
 
-// Everything pdlp_create uploads into the handle's workspace (bind_layout has set the pointers): the row pointers' low words, the
-// row-block schedules and the long-row tables of K and K', with the grids that follow from them.  Every copy is on the caller's
-// stream and waited for (the host vectors go away; later work on that stream is ordered behind it).
-int upload_schedules(pdlp_handle h, const std::vector<int64_t>& rpK, const std::vector<int64_t>& rpKT)
+// One matrix's tables into the device arrays `sc` points at: the row pointers' low words, the row-block schedule and the long-row
+// tables, with the grids that follow from them.  Every copy is on the caller's stream and waited for (the host vectors go away;
+// later work on that stream is ordered behind it).
+int upload_schedule(pdlp_handle h, Schedule& sc, const std::vector<int64_t>& rp, int64_t rows)
 {
-    const int64_t nl = h->nl, ml = h->ml;
     auto upload = [&](void* dst, const void* src, size_t bytes) {
         return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
     };
     const int fail = PDLP_ERR_HIP_BASE - 1;
-    std::vector<uint32_t> lo;
-    for (int t = 0; t < 2; ++t) {
-        const std::vector<int64_t>& rp = t == 0 ? rpK : rpKT;
-        lo.assign(rp.begin(), rp.end());                     // (truncating: the low 32 bits)
-        if (!upload((t == 0 ? h->sK : h->sKT).rplo, lo.data(), lo.size() * 4)) return fail;
-    }
+    const std::vector<uint32_t> lo(rp.begin(), rp.end());    // (truncating: the low 32 bits)
+    if (!upload(sc.rplo, lo.data(), lo.size() * 4)) return fail;
     std::vector<int64_t> sched;
-    for (int t = 0; t < 2; ++t) {
-        Schedule& sc = t == 0 ? h->sK : h->sKT;
-        const int64_t rows = t == 0 ? ml : nl;
-        build_schedule_host(t == 0 ? rpK : rpKT, rows, sched);
-        sc.nblk = rows > 0 ? (int)sched.size() / 2 - 1 : 0;
-        if (!upload(sc.blk, sched.data(), sched.size() * 8)) return fail;
-    }
+    build_schedule_host(rp, rows, sched);
+    sc.nblk = rows > 0 ? (int)sched.size() / 2 - 1 : 0;
+    if (!upload(sc.blk, sched.data(), sched.size() * 8)) return fail;
     // rows longer than NNZ_CAP
-    for (int t = 0; t < 2; ++t) {
-        Schedule& sc = t == 0 ? h->sK : h->sKT;
-        std::vector<int64_t> lch;
-        std::vector<int32_t> lrow, lptr;
-        build_long_rows_host(t == 0 ? rpK : rpKT, t == 0 ? ml : nl, lch, lrow, lptr);
-        sc.nchunks = (int)(lch.size() / 2); sc.nlong = (int)lrow.size();
-        sc.lgrid = sc.nlong > 0 ? (int)((sc.nlong + BLOCK - 1) / BLOCK < LONG_GRID ? (sc.nlong + BLOCK - 1) / BLOCK : LONG_GRID) : 0;
-        const int64_t work = (int64_t)sc.nblk + sc.nchunks;
-        sc.grid = (int)(work < MAX_GRID ? work : MAX_GRID);
-        if (sc.nlong > 0) {
-            if (!upload(sc.lch, lch.data(), lch.size() * 8) || !upload(sc.lrow, lrow.data(), lrow.size() * 4) ||
-                !upload(sc.lptr, lptr.data(), lptr.size() * 4))
-                return fail;
-        }
+    std::vector<int64_t> lch;
+    std::vector<int32_t> lrow, lptr;
+    build_long_rows_host(rp, rows, lch, lrow, lptr);
+    sc.nchunks = (int)(lch.size() / 2); sc.nlong = (int)lrow.size();
+    sc.lgrid = sc.nlong > 0 ? (int)((sc.nlong + BLOCK - 1) / BLOCK < LONG_GRID ? (sc.nlong + BLOCK - 1) / BLOCK : LONG_GRID) : 0;
+    const int64_t work = (int64_t)sc.nblk + sc.nchunks;
+    sc.grid = (int)(work < MAX_GRID ? work : MAX_GRID);
+    if (sc.nlong > 0) {
+        if (!upload(sc.lch, lch.data(), lch.size() * 8) || !upload(sc.lrow, lrow.data(), lrow.size() * 4) ||
+            !upload(sc.lptr, lptr.data(), lptr.size() * 4))
+            return fail;
     }
     return PDLP_OK;
+}
+
+// Everything pdlp_create uploads into the handle's workspace (bind_layout has set the pointers): the tables of K and K'.
+int upload_schedules(pdlp_handle h, const std::vector<int64_t>& rpK, const std::vector<int64_t>& rpKT)
+{
+    const int rc = upload_schedule(h, h->sK, rpK, h->ml);
+    return rc == PDLP_OK ? upload_schedule(h, h->sKT, rpKT, h->nl) : rc;
+}
+
+// The third schedule, of the objective's matrix Q (pdlp_set_objective_matrix): the same tables, carved out of the caller's `work` in
+// the order low words, block pairs, long-row tables.  objective_matrix_layout is the one place that knows the sizes (the size query
+// and the setter both call it).
+struct ObjMatrixLayout { int64_t rplo, blk, lch, lrow, lptr, longpart, bytes; };
+inline ObjMatrixLayout objective_matrix_layout(int64_t n, int64_t nnz, int64_t es)
+{
+    ObjMatrixLayout L{};
+    Carve c;
+    L.rplo = c.take((n + 1) * 4);
+    L.blk = c.take((max_blocks(n, nnz) + 1) * 16);
+    L.lch = c.take(max_chunks(nnz) * 2 * 8);
+    L.lrow = c.take(max_long(nnz) * 4);
+    L.lptr = c.take((max_long(nnz) + 1) * 4);
+    L.longpart = c.take(max_chunks(nnz) * es);
+    L.bytes = c.off;
+    return L;
+}
+
+int upload_objective_schedule(pdlp_handle h, const std::vector<int64_t>& rp, char* work)
+{
+    const int64_t n = h->p.n;
+    const ObjMatrixLayout L = objective_matrix_layout(n, rp[(size_t)n], (int64_t)h->es);
+    Schedule sc;
+    sc.rplo = (uint32_t*)(work + L.rplo); sc.blk = (int64_t*)(work + L.blk);
+    sc.lch = (int64_t*)(work + L.lch); sc.lrow = (int32_t*)(work + L.lrow); sc.lptr = (int32_t*)(work + L.lptr);
+    sc.longpart = (void*)(work + L.longpart);
+    const int rc = upload_schedule(h, sc, rp, n);
+    if (rc == PDLP_OK) h->sQ = sc;
+    return rc;
 }
 
 // Output pieces of a split product (Schedule::nrange > 1): rows of piece r = row blocks [rb_lo[r], rb_lo[r+1]).  The k_rowsum_epilogue

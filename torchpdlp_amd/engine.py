@@ -86,9 +86,10 @@ class PdlpEngine(KernelChoice, Exchange):
 
     def __init__(self, m: int, n: int, m_ineq: int, K_rows, KT_rows, c, q, l, u, rows: Tuple[int, int] = None,
                  cols: Tuple[int, int] = None, d_col=None, d_row=None, comm: Optional[Comm] = None, vec_dtype=None,
-                 delta: Optional[bool] = None, exact=None, tiles: bool = True, q_upper=None, quad_diag=None):
+                 delta: Optional[bool] = None, exact=None, tiles: bool = True, q_upper=None, quad_diag=None, quad_matrix=None):
         """``q_upper`` (length row1-row0, or None): two-sided rows ``q <= K x <= q_upper`` on the inequality rows (``set_row_upper``).
         ``quad_diag`` (length n, or None): the objective ``c'x + 1/2 sum_j d_j x_j^2`` (``set_objective_diag``).
+        ``quad_matrix`` (n x n, symmetric positive semidefinite, or None): the objective ``c'x + 1/2 x'Qx`` (``set_objective_matrix``).
         ``vec_dtype=torch.float64`` over float32 matrix values selects the mixed precision (``PDLP_MIXED``): float64 vectors,
         products and sums on a float32 matrix (12 -> 8 bytes per non-zero); ``delta`` (default: ``PDLP_DELTA`` in the environment,
         else on) then runs the iterations on the float32 kernels over float32 difference vectors added to float64 anchor
@@ -150,6 +151,9 @@ class PdlpEngine(KernelChoice, Exchange):
         self.quad_diag = None
         if quad_diag is not None:
             self.set_objective_diag(quad_diag)
+        self.quad_matrix = self._quad_work = None
+        if quad_matrix is not None:
+            self.set_objective_matrix(quad_matrix)
         # test / tool knobs of the handle (knobs_from_env)
         kn = self.knobs = knobs_from_env()
         if not kn.running_kkt:
@@ -163,7 +167,7 @@ class PdlpEngine(KernelChoice, Exchange):
         self.producer_pieces = kn.producer_pieces
         if not self.producer_pieces:
             self.set_option(N.OPT_PRODUCER_PIECES, 0)
-        if kn.graph and self.comm is None:
+        if kn.graph and self.comm is None and self.quad_matrix is None:      # (no replay with a sparse quadratic objective)
             self.set_option(N.OPT_GRAPH, 1)
         self.exact = None
         if exact is not None:          # the true float64 matrix, CSR kernels only: two products per restart
@@ -223,6 +227,39 @@ class PdlpEngine(KernelChoice, Exchange):
         N.check(self.lib.pdlp_set_objective_diag(self.h, d.data_ptr()), "pdlp_set_objective_diag")
         self.quad_diag = d                     # (kept alive: the library points into it)
 
+    def set_objective_matrix(self, Q):
+        """Sparse quadratic objective (``pdlp_set_objective_matrix``, include/pdlp_hip.h): ``min c'x + 1/2 x'Qx`` with ``Q`` n x n,
+        symmetric and positive semidefinite (the caller's duty), in the engine's scaling when it has one (``Scaling.scale(...,
+        quad_matrix=)``: ``D_col Q D_col``).  ``None`` takes it away.  Validated here (``quad.check_quad_matrix``: ``ValueError``);
+        float32 / float64 engines on one GPU without graph replay -- the library refuses the others (``PdlpError``).  While set,
+        ``iterate`` takes the linearised step (fixed step only; the caller keeps ``rules.qp_eta``), ``kkt`` / ``report`` give the
+        quadratic problem's objectives (``p = c'x + 1/2 x'Qx``, ``d_adj`` with ``-1/2 x'Qx``) and reduced costs
+        ``project_lambda_box(c + Qx - K'y)``, and the adaptive step, ``halpern_iterate``, ``detect_infeasibility``, the population
+        calls and the batch calls raise ``PdlpError``."""
+        from .quad import check_quad_matrix
+        if Q is None:
+            N.check(self.lib.pdlp_set_objective_matrix(self.h, None, None, None, None, 0), "pdlp_set_objective_matrix")
+            self.quad_matrix = self._quad_work = None
+            return
+        Qp = check_quad_matrix(Q, self.n).to(device=self.device, dtype=self.dtype)
+        nbytes = C.c_int64(0)
+        N.check(self.lib.pdlp_objective_matrix_bytes(self.h, Qp.nnz, C.byref(nbytes)), "pdlp_objective_matrix_bytes")
+        work = torch.empty(int(nbytes.value) + 256, dtype=torch.uint8, device=self.device)
+        off = (-work.data_ptr()) % 256
+        # (a Q without stored entries: its empty arrays have no address, and NULL means "take Q away" -- one unused element each)
+        ci = Qp.colidx if Qp.nnz else torch.zeros(1, dtype=torch.int32, device=self.device)
+        va = Qp.val if Qp.nnz else torch.zeros(1, dtype=self.dtype, device=self.device)
+        N.check(self.lib.pdlp_set_objective_matrix(self.h, Qp.rowptr.data_ptr(), ci.data_ptr(), va.data_ptr(),
+                                                   work.data_ptr() + off, nbytes.value), "pdlp_set_objective_matrix")
+        self.quad_matrix, self._quad_work = Qp, (work, ci, va)        # (kept alive: the library points into all of them)
+
+    def objective_product(self, x_full: torch.Tensor) -> torch.Tensor:
+        """``Q x`` (``pdlp_objective_product``): the plain product over the matrix of ``set_objective_matrix``"""
+        x = as_vec(x_full, self.n, self.device, self.dtype)
+        out = torch.empty(self.nl, dtype=self.dtype, device=self.device)
+        N.check(self.lib.pdlp_objective_product(self.h, x.data_ptr(), out.data_ptr()), "pdlp_objective_product")
+        return out
+
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
         th = getattr(self, "_comm_init_thread", None)
@@ -240,11 +277,12 @@ class PdlpEngine(KernelChoice, Exchange):
 
     @classmethod
     def from_full(cls, K: CsrPair, c, q, l, u, m_ineq: int, d_col=None, d_row=None, vec_dtype=None, delta=None,
-                  exact: Optional[CsrPair] = None, q_upper=None, quad_diag=None) -> "PdlpEngine":
+                  exact: Optional[CsrPair] = None, q_upper=None, quad_diag=None, quad_matrix=None) -> "PdlpEngine":
         """single-GPU engine over a whole problem (``exact``: the float64 matrix of which ``K`` is the float32 rounding)"""
         ex = None if exact is None else ((exact.rowptr, exact.colidx, exact.val), (exact.t_rowptr, exact.t_colidx, exact.t_val))
         return cls(K.m, K.n, m_ineq, (K.rowptr, K.colidx, K.val), (K.t_rowptr, K.t_colidx, K.t_val), c, q, l, u,
-                   d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, delta=delta, exact=ex, q_upper=q_upper, quad_diag=quad_diag)
+                   d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, delta=delta, exact=ex, q_upper=q_upper, quad_diag=quad_diag,
+                   quad_matrix=quad_matrix)
 
     # ---- buffers ------------------------------------------------------------------------------------
     def buffer(self, which: int) -> torch.Tensor:

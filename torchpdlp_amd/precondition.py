@@ -117,16 +117,29 @@ class Scaling:
             v = v.view(-1, 1)
         return op(v, D)
 
-    def scale(self, c, q, l, u, q_upper=None, quad_diag=None):
+    def scale(self, c, q, l, u, q_upper=None, quad_diag=None, quad_matrix=None):
         """``c * D_col, q * D_row, l / D_col, u / D_col`` as new tensors (enhancements.py:64-67); with ``q_upper`` (two-sided rows) a fifth,
         ``q_upper * D_row``: the other side of the same rows (``+inf`` stays ``+inf``, the factors are positive); with ``quad_diag``
         (the diagonal ``d`` of a quadratic objective) one more trailing value, ``d * D_col^2``: with ``x = D_col x_s`` the term
-        ``1/2 d x^2`` is ``1/2 (d D_col^2) x_s^2`` (the factors themselves stay functions of K alone)"""
+        ``1/2 d x^2`` is ``1/2 (d D_col^2) x_s^2`` (the factors themselves stay functions of K alone); with ``quad_matrix`` (the matrix
+        ``Q`` of a quadratic objective, anything ``CsrPair.from_any`` takes) the last value is ``D_col Q D_col`` as a new ``CsrPair``:
+        ``1/2 x'Qx = 1/2 x_s'(D_col Q D_col) x_s``.  Entry (i, j) is ``Q_ij (D_col_i D_col_j)`` -- the product of the two factors
+        first, which commutes -- so a symmetric ``Q`` stays symmetric bit for bit."""
         by, mul, div = self._by, torch.mul, torch.div
         out = by(c, self.d_col, mul), by(q, self.d_row, mul), by(l, self.d_col, div), by(u, self.d_col, div)
         if q_upper is not None:
             out = out + (by(q_upper, self.d_row, mul),)
-        return out if quad_diag is None else out + (by(by(quad_diag, self.d_col, mul), self.d_col, mul),)
+        if quad_diag is not None:
+            out = out + (by(by(quad_diag, self.d_col, mul), self.d_col, mul),)
+        return out if quad_matrix is None else out + (self._scale_quad_matrix(quad_matrix),)
+
+    def _scale_quad_matrix(self, Q) -> CsrPair:
+        d = self.d_col.reshape(-1)
+        Qp = CsrPair.from_any(Q, device=d.device, dtype=d.dtype)
+        rows_of = lambda rp: torch.repeat_interleave(torch.arange(Qp.n, device=d.device), rp[1:] - rp[:-1])
+        val = Qp.val * (d[rows_of(Qp.rowptr)] * d[Qp.colidx.long()])
+        t_val = Qp.t_val * (d[rows_of(Qp.t_rowptr)] * d[Qp.t_colidx.long()])
+        return CsrPair(Qp.m, Qp.n, Qp.rowptr, Qp.colidx, val, Qp.t_rowptr, Qp.t_colidx, t_val)
 
     def unscale_x(self, x):
         """``D_col x`` (pdhg.py:161), the factors in the iterate's dtype"""
@@ -197,17 +210,21 @@ def ruiz_precondition_shard(shard: dict, comm, max_iter=20, eps=1e-6) -> dict:
     return out
 
 
-def ruiz_precondition(c, K, q, l, u, device=None, max_iter=20, eps=1e-6, pock_chambolle=False, q_upper=None, quad_diag=None):
+def ruiz_precondition(c, K, q, l, u, device=None, max_iter=20, eps=1e-6, pock_chambolle=False, q_upper=None, quad_diag=None,
+                      quad_matrix=None):
     """Returns ``(K_s, c_s, q_s, l_s, u_s, (D_col, D_row, K, c, q, l, u), time_used)`` like the reference: ``equilibrate_matrix``
     (``K_s`` a ``CsrPair``) and ``Scaling.scale`` of the four vectors, as ``(len, 1)`` columns.  With ``q_upper`` (two-sided rows) the
-    scaled ``q_upper`` follows ``u_s`` in the result, and with ``quad_diag`` (quadratic objective) the scaled diagonal comes after it."""
+    scaled ``q_upper`` follows ``u_s`` in the result, with ``quad_diag`` (quadratic objective) the scaled diagonal comes after it, and
+    with ``quad_matrix`` the scaled matrix ``D_col Q D_col`` (a ``CsrPair``) after that."""
     t0 = time.time()
     Ks, scaling = equilibrate_matrix(K, device, max_iter, eps, pock_chambolle)
     vec = lambda v, ln: as_vec(v, ln, Ks.device, Ks.dtype)
     scaled = scaling.scale(vec(c, Ks.n), vec(q, Ks.m), vec(l, Ks.n), vec(u, Ks.n), None if q_upper is None else vec(q_upper, Ks.m),
                            None if quad_diag is None else vec(quad_diag, Ks.n))
     torch.cuda.current_stream(Ks.device).synchronize()
-    col = lambda v: v.view(-1, 1)
+    if quad_matrix is not None:
+        scaled = scaled + (scaling._scale_quad_matrix(quad_matrix),)
+    col = lambda v: v.view(-1, 1) if isinstance(v, torch.Tensor) else v
     return (Ks, *map(col, scaled), (col(scaling.d_col), col(scaling.d_row), K, c, q, l, u), time.time() - t0)
 
 

@@ -117,6 +117,26 @@ def start_eta(sigma, t=np.float32):
     return t(0.9) / t(sigma)
 
 
+def qp_eta(sigma, quad_norm, omega, t=np.float32):
+    """The fixed step of the linearised iteration for ``min c'x + 1/2 x'Qx`` (``quad_matrix``): with ``s`` the estimate of ``||K||_2``,
+    ``L`` that of ``||Q||_2`` and ``tau = eta/omega``, ``sigma = eta omega`` the step converges for
+    ``1/tau - sigma ||K||^2 >= ||Q||/2``, that is ``omega/eta - eta omega s^2 >= L/2``; the largest such ``eta`` is the positive root
+    of ``omega s^2 eta^2 + (L/2) eta - omega = 0``, and the step is 0.9 of it -- the safety ``start_eta`` has --
+
+        ``eta = 0.9 (-L/2 + sqrt(L^2/4 + 4 omega^2 s^2)) / (2 omega s^2)``,
+
+    formed in double and rounded ONCE to ``t``.  At 0.9 of the root the condition holds with a factor above 1.11 to spare (the left
+    side is decreasing in ``eta``), which an under-estimate of ``L`` by the power iteration may use up.  ``L == 0`` (a ``Q`` without
+    stored entries) is DEFINED as ``start_eta(s, t)``: the LP's step, bit for bit.  Unlike the LP's, the step depends on ``omega``:
+    the driver sets it anew after every restart that changes the primal weight."""
+    if float(quad_norm) == 0.0:
+        return start_eta(sigma, t)
+    s, L, w = np.float64(sigma), np.float64(quad_norm), np.float64(omega)
+    # the same root with the conjugate in the denominator, 2 omega / (L/2 + sqrt(L^2/4 + 4 omega^2 s^2)): the difference above
+    # cancels to nothing in double once L is large against omega s
+    return t(0.9 * (2.0 * w) / (0.5 * L + np.sqrt(0.25 * L * L + 4.0 * w * w * s * s)))
+
+
 def start_omega(q_norm, c_norm, t=np.float32):
     """pdhg.py:23: the first primal weight ||c|| / ||q||, 1 when either norm is (nearly) zero"""
     q_norm, c_norm = t(q_norm), t(c_norm)

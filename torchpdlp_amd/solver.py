@@ -16,9 +16,9 @@ import torch
 from . import _native as N
 from .engine import Comm, PdlpEngine
 from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, fixed_point_error, fixed_point_restart_decision,   # noqa: F401
-                    kkt_error, np_type, previous_kkt_matters, primal_weight, restart_decision, start_eta, start_omega, terminated)
+                    kkt_error, np_type, previous_kkt_matters, primal_weight, qp_eta, restart_decision, start_eta, start_omega, terminated)
 from .compose import HALPERN_REFUSED, check_composition     # noqa: F401  (HALPERN_REFUSED: importable from here)
-from .quad import check_quad_diag
+from .quad import check_quad_diag, check_quad_matrix
 from .ranged import check_row_upper, norm_vector as ranged_norm_vector
 from .sparse import CsrPair, as_vec, resolve_device     # noqa: F401  (resolve_device: api.py and callers take it from here)
 
@@ -88,6 +88,11 @@ class PdhgDriver:
     after the first iteration of every restart period -- a segment that starts a period is ``halpern_iterate(1)``, the evaluation,
     ``halpern_iterate(rest)``; the checks stay on the multiples of the period.  ``j += 1`` per evaluation, ``r0`` included.
     ``after_restart`` runs as it is: it adopts the candidate, and its KKT pass at the restart point is the termination test.
+
+    A sparse quadratic objective (the engine's ``quad_matrix``): the engine takes the linearised step, whose fixed step size
+    ``rules.qp_eta(sigma, quad_norm, omega)`` depends on the primal weight -- ``start`` takes ``quad_norm`` (the estimate of ``||Q||_2``)
+    and ``after_restart`` sets the step anew (``eng.set_step``) where it would set the primal weight alone (``eng.set_omega``).  A
+    ``trace`` receives every step size set under ``"eta"``.  Fixed step, averaged PDHG only.
     """
 
     def __init__(self, eng: PdlpEngine, restart_period=40, primal_update=False, adaptive=False, precondition=False,
@@ -103,6 +108,9 @@ class PdhgDriver:
         q_upper = getattr(eng, "q_upper", None)     # (a refusal comes before anything more of the engine is read: one switch at a time)
         check_composition(q_upper=q_upper is not None, **form)
         check_composition(quad_diag=getattr(eng, "quad_diag", None) is not None, **form)
+        self.quad = getattr(eng, "quad_matrix", None) is not None
+        check_composition(quad_matrix=self.quad, halpern=self.halpern, adaptive=adaptive, **form)
+        self.sigma = self.quad_norm = None                                  # the norm estimates the step rule of quad_matrix keeps
         self.kkt_prev_cand = None                                           # Halpern: the candidate's KKT error at the previous check
         self.infeasibility_detect, self.infeas_tol = bool(infeasibility_detect), float(infeas_tol)
         self.infeasible = None                                              # the detector's verdict (pdhg.py:94-100)
@@ -125,10 +133,18 @@ class PdhgDriver:
         self.checks = 0                # restart checks performed (pdhg.py:115)
         self.check_seconds = None      # set to 0.0 to accumulate the wall time of the restart checks (synchronises around them)
 
-    def start(self, sigma, x_init=None, y_init=None, theta=1.0):
+    def _set_quad_step(self, k=0):
+        """quad_matrix: the step that goes with the current primal weight, to the engine (and the trace)"""
+        self.eta = qp_eta(self.sigma, self.quad_norm, self.omega, self.t)
+        self.eng.set_step(self.eta, self.omega, 1.0, k)
+        if self.trace is not None:
+            self.trace.setdefault("eta", []).append(float(self.eta))
+
+    def start(self, sigma, x_init=None, y_init=None, theta=1.0, quad_norm=0.0):
         t, eng = self.t, self.eng
-        eta = start_eta(sigma, t)                                           # pdhg.py:22
         self.omega = start_omega(self.q_norm, self.c_norm, t)               # pdhg.py:23
+        self.sigma, self.quad_norm = float(sigma), float(quad_norm)
+        eta = qp_eta(sigma, quad_norm, self.omega, t) if self.quad else start_eta(sigma, t)      # pdhg.py:22
         zeros = lambda ln: torch.zeros(ln, dtype=eng.dtype, device=eng.device)
         if x_init is not None and y_init is not None:                       # pdhg.py:31-36
             eng.set_iterate(x_init, y_init)
@@ -136,6 +152,8 @@ class PdhgDriver:
             eng.set_iterate(zeros(eng.nl), zeros(eng.ml))
         eng.set_step(eta, self.omega, theta, 0)
         self.eta = eta
+        if self.quad and self.trace is not None:
+            self.trace.setdefault("eta", []).append(float(eta))
         self.r0 = self.r_prev = None
         if self.infeasibility_detect:
             eng.infeas_reset()                                              # pdhg.py:39-40
@@ -320,8 +338,12 @@ class PdhgDriver:
             eng.restart(N.CUR)
         if self.primal_update:                                              # pdhg.py:150-151
             dx2, dy2 = eng.restart_distance()
+            omega_before = self.omega
             self.omega = primal_weight(dx2, dy2, self.omega, 0.5, t)
-            eng.set_omega(self.omega)
+            if self.quad and self.omega != omega_before:
+                self._set_quad_step(self.k)          # (the step of the linearised iteration depends on the primal weight)
+            else:
+                eng.set_omega(self.omega)
             if self.trace is not None:
                 self.trace["omega"].append(float(self.omega))
         eng.mark_restart_point()                                            # pdhg.py:63-64 of the next round
@@ -369,16 +391,33 @@ def estimate_sigma(eng: PdlpEngine, b0=None, power_iters=100, seed=None) -> floa
     return eng.power_iteration(b0, power_iters)
 
 
+def estimate_quad_norm(eng: PdlpEngine, b0=None, power_iters=100, seed=None) -> float:
+    """The estimate of ``||Q||_2`` for ``rules.qp_eta``: ``estimate_sigma``'s recurrence (helpers.py:41-51) on the matrix of the
+    engine's quadratic objective -- ``b <- Q'(Q b) / ||.||`` from the same start vector for the same number of iterations, then
+    ``||Q b||`` -- through the plain product ``eng.objective_product``.  0 for a ``Q`` without stored entries."""
+    if b0 is None:
+        b0 = power_iteration_start(eng.n, seed)
+    b = as_vec(b0, eng.n, eng.device, eng.dtype)
+    for _ in range(int(power_iters)):
+        b = eng.objective_product(eng.objective_product(b))
+        nb = torch.linalg.norm(b)
+        if float(nb) == 0.0:
+            return 0.0
+        b = b / nb
+    return float(torch.linalg.norm(eng.objective_product(b)))
+
+
 def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_period=40, precondition=False,
              primal_update=False, adaptive=False, time_limit=3600, time_used=0, x_init=None, y_init=None,
              b0=None, sigma=None, power_iters=100, seed=None, trace=None, infeasibility_detect=False, infeas_tol=1e-4,
-             adaptive_retry=False, *, report=None, halpern=False, halpern_restart="kkt"):
+             adaptive_retry=False, *, report=None, halpern=False, halpern_restart="kkt", quad_norm=None):
     """The outer loop over an existing engine.  Returns (x_local, prim_obj, k, n, j, status, total_time).
     ``report``: a dict that receives ``PdlpEngine.report`` of the returned iterate (this rank's blocks; of the un-preconditioned
     problem when ``precondition``) whatever the status, and ``q_norm`` / ``c_norm`` as the termination test used them -- in the
     style of ``trace``.  ``halpern``: the restarted, reflected Halpern iteration (``PdhgDriver``); the returned iterate is then the
     candidate of the last restart or, when the run ends between restarts, of the last iteration.  ``halpern_restart``: "kkt" or
-    "fixed_point", the quantity its restart checks look at (``PdhgDriver``)."""
+    "fixed_point", the quantity its restart checks look at (``PdhgDriver``).  ``quad_norm``: overrides the estimate of ``||Q||_2`` of an
+    engine with a sparse quadratic objective (``estimate_quad_norm``), as ``sigma`` overrides that of ``||K||_2``."""
     t0 = time.time()
     check_halpern_restart(halpern_restart, halpern)
     if adaptive_retry and (getattr(eng, "delta", False) or infeasibility_detect):
@@ -388,7 +427,9 @@ def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_p
                      adaptive_retry=adaptive_retry, halpern=halpern, halpern_restart=halpern_restart)
     if sigma is None:                                                       # pdhg.py:22
         sigma = estimate_sigma(eng, b0, power_iters, seed)
-    drv.start(sigma, x_init, y_init)
+    if drv.quad and quad_norm is None:
+        quad_norm = estimate_quad_norm(eng, b0, power_iters, seed)
+    drv.start(sigma, x_init, y_init, quad_norm=quad_norm if drv.quad else 0.0)
     status = STATUS_KKT_LIMIT
     while drv.j < max_kkt:                                                  # pdhg.py:54
         n_before = drv.n
@@ -439,7 +480,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
                    precondition=False, primal_update=False, adaptive=False, data_precond=None, infeasibility_detect=False,
                    infeas_tol=1e-4, time_limit=3600, time_used=0, x_init=None, y_init=None, *, b0=None, sigma=None,
                    seed=None, trace=None, comm=None, precision=None, adaptive_retry=False, report=None,
-                   halpern=False, q_upper=None, quad_diag=None, halpern_restart="kkt"):
+                   halpern=False, q_upper=None, quad_diag=None, halpern_restart="kkt", quad_matrix=None, quad_norm=None):
     """Drop-in for the reference's ``pdlp_algorithm`` (primal_dual_hybrid_gradient.py:7) on one MI355X.
 
     ``K`` may be a dense / COO torch tensor (as the reference takes), a scipy sparse matrix or a
@@ -490,16 +531,28 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     any device work) for a malformed vector and together with ``precision="mixed"``, ``comm``, ``infeasibility_detect`` or
     ``adaptive_retry``.
 
+    ``quad_matrix`` (n x n, default None; the reference has no counterpart): the objective becomes ``c'x + 1/2 x'Qx`` with ``Q``
+    sparse, symmetric and positive semidefinite -- the last is the caller's duty, ``quad.check_quad_matrix`` checks the rest (DESIGN.md
+    4.5).  The iteration takes the linearised step (the gradient ``Qx`` joins ``c`` in the primal half-step) with the fixed step
+    ``rules.qp_eta``, which the driver sets anew whenever a restart changes the primal weight; ``quad_norm`` overrides the power
+    iteration's estimate of ``||Q||_2`` as ``sigma`` overrides that of ``||K||_2``.  The returned objective is the quadratic one, the
+    report's dual objective carries ``-1/2 x'Qx`` and its reduced costs are ``project_lambda_box(c + Qx - K'y)``; with
+    ``precondition`` pass the scaled matrix (``Scaling.scale(..., quad_matrix=)``: ``D_col Q D_col``).  Works with ``precondition``,
+    ``primal_update``, ``q_upper``, ``quad_diag`` and ``x_init`` / ``y_init`` in float32 and float64; ``ValueError`` (before any device
+    work) for a malformed matrix and together with ``adaptive``, ``halpern``, ``adaptive_retry``, ``infeasibility_detect``,
+    ``precision="mixed"`` or ``comm``.
+
     ``comm`` (a ``Comm``, or ``True`` for the default ``torch.distributed`` group): every rank calls with the SAME
     full problem and the same ``seed``/``b0``; each keeps its row blocks of K and K', the iterations exchange
     ``xbar`` and ``y`` over RCCL, and every rank returns the full solution.
     """
     from .distributed import gather_report, gather_solution, shard_engine, start_blocks
     check_halpern_restart(halpern_restart, halpern)
-    check_composition(halpern=halpern, q_upper=q_upper is not None, quad_diag=quad_diag is not None, adaptive=adaptive,
-                      adaptive_retry=adaptive_retry, infeasibility_detect=infeasibility_detect, mixed=precision is not None, comm=comm not in (None, False))
+    check_composition(halpern=halpern, q_upper=q_upper is not None, quad_diag=quad_diag is not None,
+                      quad_matrix=quad_matrix is not None, adaptive=adaptive, adaptive_retry=adaptive_retry, infeasibility_detect=infeasibility_detect, mixed=precision is not None, comm=comm not in (None, False))
     q_upper = check_row_upper(q, q_upper, m_ineq)
     quad_diag = check_quad_diag(quad_diag, torch.as_tensor(c).numel())
+    quad_matrix = check_quad_matrix(quad_matrix, torch.as_tensor(c).numel())
     device = resolve_device(device)
     Kp = CsrPair.from_any(K, device=device)
     dtype = Kp.dtype
@@ -528,12 +581,14 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
         verbose = verbose and comm.rank == 0
     else:
         eng = PdlpEngine.from_full(Kp, c, q, l, u, m_ineq, d_col=d_col, d_row=d_row, vec_dtype=vec_dtype, exact=exact_K, q_upper=q_upper,
-                                   **({} if quad_diag is None else dict(quad_diag=quad_diag)))
+                                   **({} if quad_diag is None else dict(quad_diag=quad_diag)),
+                                   **({} if quad_matrix is None else dict(quad_matrix=quad_matrix)))
     x, obj, k, n, j, status, total = run_pdlp(
         eng, max_kkt=max_kkt, tol=tol, verbose=verbose, restart_period=restart_period, precondition=precondition,
         primal_update=primal_update, adaptive=adaptive, time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init,
         b0=b0, sigma=sigma, seed=seed, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
-        adaptive_retry=adaptive_retry, report=report, halpern=halpern, halpern_restart=halpern_restart)
+        adaptive_retry=adaptive_retry, report=report, halpern=halpern, halpern_restart=halpern_restart,
+        **({} if quad_matrix is None else dict(quad_norm=quad_norm)))
     if report is not None:
         report.update(gather_report(eng, report, Kp.n, Kp.m))
     return gather_solution(eng, x, Kp.n).view(-1, 1), obj, k, n, j, status, total
