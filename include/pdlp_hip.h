@@ -347,10 +347,33 @@ int pdlp_set_objective_diag(pdlp_handle h, const void* d_local);
  * non-expansive); pdlp_infeas_*, pdlp_mv_steps / _gap / _product, every pdlp_batch_* call; pdlp_comm_init, pdlp_peer_connect;
  * pdlp_set_option(PDLP_OPT_GRAPH, 1); and pdlp_set_delta(on), which needs a PDLP_MIXED handle.
  *
- * pdlp_objective_product: out_local = Q x_full, the plain product (power iteration on Q, tests).  PDLP_ERR_STATE without a Q. */
+ * pdlp_objective_product: out_local = Q x_full, the plain product (power iteration on Q, tests).  PDLP_ERR_STATE without a Q.
+ *
+ * pdlp_objective_iterate: `iters` ADAPTIVE iterations of the linearised step, a mode of its own beside pdlp_iterate (whose refusal of
+ * adaptive != 0 with Q stands, as do those of pdlp_primal_half / pdlp_dual_half / pdlp_adaptive_*).  The step-size rule is the
+ * reference's (step.py:91-115: one trial, a rejected step is kept) with the curvature measured along the step in its denominator,
+ *     eta_bar = (omega ||dx||^2 + ||dy||^2 / omega) / (2 |dy'K dx| + max(dx'Q dx, 0)),
+ * the descent-lemma condition ||dz||_M^2 >= dx'Q dx, exact for a quadratic; t1, t2, eta', the acceptance test, the pending weight and
+ * the counters are pdlp_iterate's.  It costs no product: each iteration is
+ *     g = c + Q x                        only if the handle does not carry it (the first iteration; after a KKT pass or report,
+ *                                        pdlp_restart, pdlp_set_iterate, fixed iterations, pdlp_set_objective_matrix)
+ *     x', xbar                           the adaptive primal half-step reading g
+ *     g <- c + Q x', dx'Q dx             the product with Q at x': its epilogue holds g_j of the old x beside the new one and adds
+ *                                        dx_j (g'_j - g_j) in double -- and g(x') is the next iteration's gradient, accepted or not
+ *     y'                                 the adaptive dual half-step
+ *     the rule                           one workgroup, three partial-sum arrays
+ * i.e. the three products of the fixed step plus the rule's kernel.  g' - g cancels to eps |g| |dx| per row: the measured curvature
+ * is good to that, which matters only once the step has shrunk to the working type's resolution.  PDLP_BUF_RED[0..3] hold ||dx||^2,
+ * ||dy||^2, dy'K dx and dx'Q dx afterwards; pdlp_get_scalars: slot 11 keeps 2 dy'K dx, slot 13 the curvature.  The partial sums of
+ * the curvature live at the end of `work` (pdlp_objective_matrix_bytes counts them).  A Q without stored entries adds + 0: the bits
+ * of pdlp_iterate(h, iters, 1) on a handle without Q.  pdlp_flush_average(h, 1), pdlp_compute_average, pdlp_restart, pdlp_set_omega
+ * as for an adaptive LP; composes with the diagonal term (its prox stays in the half-step; only Q's curvature enters the rule) and
+ * with two-sided rows.  PDLP_ERR_STATE without Q -- so on every handle that cannot have one: PDLP_MIXED, a shard, a communicator,
+ * a peer exchange, PDLP_OPT_GRAPH -- and on a handle where pdlp_halpern_iterate has run since the last pdlp_set_iterate. */
 int pdlp_objective_matrix_bytes(pdlp_handle h, int64_t nnz, int64_t* bytes);
 int pdlp_set_objective_matrix(pdlp_handle h, const int64_t* rowptr, const int32_t* colidx, const void* val, void* work, int64_t work_bytes);
 int pdlp_objective_product(pdlp_handle h, const void* x_full, void* out_local);
+int pdlp_objective_iterate(pdlp_handle h, int iters);
 
 /* ---- sharded problems: the exchange inside the library (RCCL over xGMI) ------------------------------------------------
  * One process per GPU; rank r owns block r of the constraints and of the variables (equal, padded blocks -- the layout of

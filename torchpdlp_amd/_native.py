@@ -20,7 +20,7 @@ NRED, NSCAL = 8, 16
 OPT_RUNNING_KKT, OPT_KTY_REUSE, OPT_GRAPH, OPT_SPLIT_SLOTS, OPT_PRODUCER_PIECES, OPT_BEGIN_INLINE, OPT_PEER_EXCHANGE, OPT_PEER_TIMEOUT_MS, OPT_PEER_LOCAL_FIRST, OPT_PEER_PUSH = range(10)
 PEER_INFO_BYTES, PEER_LOOPBACK, PEER_LOOPBACK_HOST = 256, 1, 2
 # indices into the scalar block
-S_ETA, S_OMEGA, S_THETA, S_TAU, S_SIGMA, S_WPEND, S_ETASUM, S_K, S_INV1PT, S_ACCEPT, S_ETABAR, S_DEN, S_ETASUM_PREV = range(13)
+S_ETA, S_OMEGA, S_THETA, S_TAU, S_SIGMA, S_WPEND, S_ETASUM, S_K, S_INV1PT, S_ACCEPT, S_ETABAR, S_DEN, S_ETASUM_PREV, S_CURV = range(14)
 
 
 class PdlpProblem(C.Structure):
@@ -102,6 +102,7 @@ SIGNATURES = {
     "pdlp_set_row_upper": (_I, [_H, _P]),
     "pdlp_set_objective_diag": (_I, [_H, _P]),
     "pdlp_objective_matrix_bytes": (_I, [_H, _I64, C.POINTER(_I64)]),
+    "pdlp_objective_iterate": (_I, [_H, _I]),
     "pdlp_set_objective_matrix": (_I, [_H, _P, _P, _P, _P, _I64]),
     "pdlp_objective_product": (_I, [_H, _P, _P]),
     "pdlp_set_exchange_chunks": (_I, [_H, _I]),

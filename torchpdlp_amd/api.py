@@ -10,6 +10,7 @@ from typing import Optional, Union
 
 import torch
 
+from .compose import check_quad_step
 from .mps import mps_to_ranged_form, mps_to_standard_form
 from .precondition import Scaling, equilibrate_matrix, ruiz_precondition, ruiz_precondition_batch
 from .solver import check_composition, check_quad_diag, check_quad_matrix, check_row_upper, is_mixed, pdlp_algorithm, resolve_device
@@ -70,7 +71,7 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
              precision: Optional[str] = None, adaptive_retry: bool = False, direct_exchange: bool = False,
              report: bool = True, pock_chambolle: bool = False, halpern: bool = False, q_upper=None,
              ranged_rows: bool = False, quad_diag=None, halpern_restart: str = "kkt", quad_matrix=None,
-             quad_norm: Optional[float] = None) -> LPResult:
+             quad_norm: Optional[float] = None, quad_step: str = "fixed") -> LPResult:
     """Solve ``min c'x, K[:m_ineq]x >= q[:m_ineq], K[m_ineq:]x = q[m_ineq:], l <= x <= u`` on the current HIP device.
 
     ``problem`` is an MPS path or ``(c, K, q, m_ineq, l, u)`` with ``K`` dense / COO / scipy-sparse / ``CsrPair``.
@@ -128,10 +129,17 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     float64, with ``K`` on any product form; ``ValueError`` (before any device work) for a malformed matrix and together with
     ``adaptive_stepsize``, ``halpern``, ``adaptive_retry``, ``infeasibility_detect``, ``precision="mixed"``, ``comm``,
     ``direct_exchange`` and ``fishnet``.  With an MPS path the size is compared with ``n`` once the file is read.
+    ``quad_step`` ("fixed", the default, or "adaptive"; with ``quad_matrix``): "adaptive" runs the same linearised step under an
+    adaptive step size -- the rule of ``adaptive_stepsize`` with the curvature ``dx'Q dx`` measured along every step in its
+    denominator, so the step follows the directions actually taken instead of 0.9 of the worst case over ``||K||`` and ``||Q||``
+    (DESIGN.md section 4.5.1); it starts from ``rules.qp_eta``, costs the fixed step's three products per iteration and composes
+    with everything ``quad_matrix`` composes with.  ``ValueError`` (before any device work) for another value, without
+    ``quad_matrix``, and together with what ``quad_matrix`` refuses -- ``adaptive_stepsize`` itself included.
     """
     _check_pock_chambolle(pock_chambolle, precondition)
     from .solver import check_halpern_restart
     check_halpern_restart(halpern_restart, halpern)
+    check_quad_step(quad_step, quad_matrix is not None)
     from_file = isinstance(problem, (str, os.PathLike))
     if ranged_rows and (not from_file or q_upper is not None):
         raise ValueError("ranged_rows=True reads the RANGES rows of an MPS path; arrays carry q_upper themselves")
@@ -195,7 +203,7 @@ def solve_lp(problem: Union[str, os.PathLike, tuple], device=None, tol: float = 
     x, obj, k, n, j, status, total = pdlp_algorithm(
         Ks, m_ineq, cs, qs, ls, us, device, verbose=verbose, data_precond=data_precond, time_used=time_used, x_init=x_init,
         y_init=y_init, seed=seed, comm=comm, precision=precision, report=rep, **({} if qus is None else dict(q_upper=qus)),
-        **({} if ds is None else dict(quad_diag=ds)), **({} if Qs is None else dict(quad_matrix=Qs, quad_norm=quad_norm)), **run)
+        **({} if ds is None else dict(quad_diag=ds)), **({} if Qs is None else dict(quad_matrix=Qs, quad_norm=quad_norm, quad_step=quad_step)), **run)
     if precondition:        # the reference returns the scaled iterate (quirk Q4); solve_lp un-scales: x = D_col x_s (pdhg.py:161)
         x = Scaling(*data_precond[:2]).unscale_x(x)
     if quad_matrix is not None:

@@ -7,6 +7,18 @@ QUAD_REFUSED = ("quad_diag (diagonal quadratic objective) runs on one GPU in flo
                 "direct_exchange, infeasibility_detect, fishnet or adaptive_retry")
 QMAT_REFUSED = ("quad_matrix (sparse quadratic objective) runs the fixed, linearised step on one GPU in float32 or float64: not with "
                 "adaptive, halpern, adaptive_retry, infeasibility_detect, mixed precision, a communicator, direct_exchange or fishnet")
+QUAD_STEPS = ("fixed", "adaptive")
+
+
+def check_quad_step(quad_step, quad_matrix) -> str:
+    """``quad_step`` as given to a solve: one of ``QUAD_STEPS``, and "adaptive" (the step-size rule with the measured curvature
+    ``dx'Q dx``, pdlp_objective_iterate) only with ``quad_matrix`` (``ValueError`` otherwise: the callers check before any device
+    work).  What ``quad_matrix`` itself refuses stays refused under either value (``check_composition``)."""
+    if quad_step not in QUAD_STEPS:
+        raise ValueError(f"unknown quad_step {quad_step!r}: one of {', '.join(map(repr, QUAD_STEPS))}")
+    if quad_step != "fixed" and not quad_matrix:
+        raise ValueError(f"quad_step={quad_step!r} is a step rule of the sparse quadratic objective: it needs quad_matrix")
+    return quad_step
 
 
 def check_composition(*, halpern=False, q_upper=False, quad_diag=False, quad_matrix=False, adaptive=False, adaptive_retry=False,

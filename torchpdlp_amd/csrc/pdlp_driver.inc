@@ -224,6 +224,27 @@ int iterate_sharded(pdlp_handle h, int iters, int adaptive)
     return PDLP_OK;
 }
 
+// pdlp_objective_iterate: the adaptive iteration of the linearised step (sparse quadratic objective; one GPU, plain launches).  The
+// product with Q sits BEHIND the primal half-step, at x': its epilogue has g(x) and g(x') of a row side by side and sums the
+// curvature dx'Q dx for the rule, and -- a rejected trial is kept -- g(x') is the gradient the next iteration's half-step reads.
+// Three products per iteration, as the fixed step has; the gradient is formed ahead of the half-step only where nothing carried it
+// (Carried::g_cur: the first iteration, after a KKT pass, a restart, fixed iterations).
+template <typename T> int objective_iterate_t(pdlp_handle h, int iters)
+{
+    int rc;
+    for (int it = 0; it < iters; ++it) {
+        if (!h->carry.g_cur && (rc = obj_gradient<T, false>(h, h->ix_cur)) != PDLP_OK) return rc;
+        if ((rc = primal_half_t<T>(h, 1)) != PDLP_OK) return rc;
+        h->carry.gradient_overwritten();       // (from here the buffer holds g(x') while x is still current: down until the swap succeeds)
+        if ((rc = obj_gradient_step<T>(h)) != PDLP_OK) return rc;
+        if ((rc = dual_half_t<T>(h, 1)) != PDLP_OK) return rc;
+        h->carry.gradient_stepped();
+        launch_objective_rule(h);
+    }
+    HIP_TRY(hipGetLastError());
+    return PDLP_OK;
+}
+
 // the iterations of a problem on one GPU: direct launches, or (PDLP_OPT_GRAPH) pairs of iterations replayed from a captured graph
 int iterate_single(pdlp_handle h, int iters, int adaptive)
 {

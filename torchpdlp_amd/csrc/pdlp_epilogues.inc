@@ -95,6 +95,27 @@ template <typename T, bool SUM> struct ObjGradEpi {
     }
 };
 
+// The same product behind the primal half-step of an adaptive iteration (pdlp_objective_iterate), taken at the NEW x: row j sees the
+// gradient g_j of the old x, still in g[j] (the half-step that read it is an earlier launch; row j is the only reader and writer of
+// g[j]), beside the one it forms, and the difference of the two is (Q dx)_j up to the rounding of either.  acc[0] takes
+// dx_j (g'_j - g_j) in double, g' the STORED value: the sum finishes as the curvature dx'Q dx of the step-size rule without a
+// product of its own.  The cancellation in g' - g is of order eps |g| |dx| per row (DESIGN.md 4.5.1).  Q's own row blocks only.
+template <typename T> struct ObjGradStepPre { T cj, xn, xo, go; };
+template <typename T> struct ObjGradStepEpi {
+    static constexpr int NA = 1;
+    const T* c; const T* x_new; const T* x_old; T* g;
+    typedef ObjGradStepPre<T> Pre;
+    __device__ void load() {}
+    __device__ Pre pre(int j) const { return Pre{c[j], x_new[j], x_old[j], g[j]}; }
+    __device__ void operator()(int j, T s, double* acc) const { (*this)(j, s, pre(j), acc); }
+    __device__ void operator()(int j, T s, const Pre& p, double* acc) const
+    {
+        const T gn = p.cj + s;
+        g[j] = gn;
+        acc[0] += (double)(p.xn - p.xo) * ((double)gn - (double)p.go);
+    }
+};
+
 // ---- the arithmetic every kernel file shares (this file is included before all of them) --------------------------------------
 // lam = project_lambda_box(g) (helpers.py:21-37) with the bound classes read off l, u: a variable without a lower bound takes
 // min(g, 0), one without an upper bound max(g, 0), a free one 0, a boxed one g.  ninf / pinf: the classes, for the callers' own use.

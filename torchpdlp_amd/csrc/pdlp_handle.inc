@@ -117,6 +117,16 @@ struct Carried {
     // PDLP_PREV / PDLP_AVG are still z / T(z) of the last Halpern iteration (pdlp_halpern_fixed_point).  Up: halpern_begins.
     // Down: buffers_reassigned -- any call that re-assigns the iterate buffers.
     bool halpern_pair = false;
+    // Sparse quadratic objective: lam_prev is c + Q x of the CURRENT x, so the adaptive iteration (pdlp_objective_iterate) need not
+    // form it ahead of its primal half-step.  Up: gradient_stepped -- the step product of that iteration, which multiplies at the x'
+    // the dual half-step of the same iteration then makes current (a rejected trial is kept: x' stays); raised only once that
+    // half-step has swapped the buffers, and down from the moment the product overwrites the buffer (an iteration that fails in
+    // between leaves it down).  Down: whatever else writes lam_prev or moves x -- a KKT pass or report at any point
+    // (gradient_overwritten: it forms g of the point it looks at, the current one included), the fixed primal half-step (it forms g
+    // of the x it then leaves), every finished iteration (iterated: any dual half-step swaps the buffers, a bare pdlp_dual_half
+    // included), a restart, new_iterate, objective_matrix_changed, drop_all.  Read by pdlp_objective_iterate alone: the fixed-step path forms g ahead of every primal
+    // half-step whatever this says.
+    bool g_cur = false;
 
     // A capture (pair_graph) runs the launch code, transitions included, and puts the whole struct back: it leaves no trace.  It used
     // to restore kx_valid, the candidates, since_reset and kty_tail_done only; what it left in the others, and why replayed() gives
@@ -142,6 +152,7 @@ struct Carried {
             period_reset();
         }
         drop_candidates();
+        g_cur = false;
     }
     // `n` PDHG iterations finished (the last dual half-step of each has swapped the buffers)
     void iterated(int64_t n, bool delta)
@@ -149,6 +160,7 @@ struct Carried {
         if (delta) dy_folded = false;      // gdy = y_cur - y_prev waits for the next product with K'
         else { since_reset += n; kty_tail_done = avg_products = false; kty_cur = -1; }
         drop_candidates();
+        g_cur = false;          // (x has moved; pdlp_objective_iterate raises it again behind its own dual half-step)
     }
     void replayed(int pairs, bool delta) { iterated(2 * (int64_t)pairs, delta); }      // `pairs` launches of a captured pair
     // a KKT pass at `which` is about to overwrite its K'y slot / has kept its products (kx_carried: K x came from kxb[0])
@@ -163,14 +175,17 @@ struct Carried {
     // the running sums stop being complete inside a period (at since_reset == 0 nothing has been added yet: nothing is missing)
     void sums_end() { if (since_reset > 0) sums_broken = true; }
     void operands_changed() { drop_candidates(); kty_cur = -1; }               // what a KKT pass kept belongs to the other q_upper / d
-    // pdlp_set_objective_matrix: Q set, replaced or taken away.  The gradient buffer g = c + Q x is never carried -- every primal
-    // half-step and every KKT pass forms it anew -- so only what a KKT pass kept goes, as with the other operands of the objective
-    void objective_matrix_changed() { operands_changed(); }
+    // pdlp_set_objective_matrix: Q set, replaced or taken away.  What a KKT pass kept goes, as with the other operands of the
+    // objective, and the gradient buffer g = c + Q x belongs to the other Q (the fixed step never carries it: every primal half-step
+    // and every KKT pass forms it anew; see g_cur)
+    void objective_matrix_changed() { operands_changed(); g_cur = false; }
+    void gradient_stepped() { g_cur = true; }                                  // lam_prev = c + Q x' and x' has just become current
+    void gradient_overwritten() { g_cur = false; }                             // a KKT pass, a report, the fixed primal half-step
     // pdlp_set_delta: no product survives the switch.  The sums' fields stay as they are, as they always did: delta mode reads none.
     void drop_products() { kx_valid = false; drop_candidates(); kty_cur = -1; anchors_valid = dy_folded = false; }
     // nothing carried survives, the running sums of this period included.  (One list where pdlp_halpern_iterate and
     // pdlp_adaptive_retry had two that differed in cur_kx_cached: see cand_cur.  Neither runs in delta mode: the anchors are down.)
-    void drop_all() { drop_products(); kty_tail_done = avg_products = false; sums_broken = true; }
+    void drop_all() { drop_products(); kty_tail_done = avg_products = false; sums_broken = true; g_cur = false; }
     void trial_undone() { if (since_reset > 0) --since_reset; drop_all(); }    // pdlp_adaptive_retry: the products saw the rejected trial
     void halpern_begins() { drop_all(); halpern = halpern_pair = true; }       // (every primal half of the mode multiplies)
     void halpern_iterated() { ++since_reset; }
@@ -210,8 +225,9 @@ struct pdlp_solver {
     const void* q_upper = nullptr;   // two-sided rows (pdlp_set_row_upper): q <= K x <= q_upper on the inequality rows; the caller's memory
     // sparse quadratic objective (pdlp_set_objective_matrix): c'x + 1/2 x'Qx.  Q's CSR arrays are the caller's memory; sQ is its
     // row-block schedule, built into the caller's `work`; the gradient g = c + Q x of the point a half-step or a KKT pass looks at
-    // lives in lam_prev (the infeasibility detector's, which is refused while Q is set); red[OBJ_XQX] receives x'Qx of a KKT pass
-    struct ObjMatrix { bool on = false; const int32_t* colidx = nullptr; const void* val = nullptr; } obj_mat;
+    // lives in lam_prev (the infeasibility detector's, which is refused while Q is set); red[OBJ_XQX] receives x'Qx of a KKT pass;
+    // part: the partial sums of the step product's curvature (pdlp_objective_iterate), at the end of the caller's `work`
+    struct ObjMatrix { bool on = false; const int32_t* colidx = nullptr; const void* val = nullptr; double* part = nullptr; } obj_mat;
     static constexpr int OBJ_XQX = PDLP_NRED - 1;
     Schedule sK, sKT, sQ;
     char* xb[3] = {};             // full-length primal buffers; roles via ix_*

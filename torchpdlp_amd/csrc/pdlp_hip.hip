@@ -61,7 +61,7 @@ constexpr int PEER_WAIT_BLOCKS = 8; // one waiting wave per XCD (k_peer_wait)
 constexpr int BOX_BYTES = 4096, BOX_FLAG_STRIDE = 16 /* uint32 */, BOX_SUMS_AT = 1024 /* bytes */, BOX_SUMS_STRIDE = 4 /* doubles */;
 
 // indices into the device scalar block (double[PDLP_NSCAL])
-enum { S_ETA = 0, S_OMEGA, S_THETA, S_TAU, S_SIGMA, S_WPEND, S_ETASUM, S_K, S_INV1PT, S_ACCEPT, S_ETABAR, S_DEN, S_ETASUM_PREV };
+enum { S_ETA = 0, S_OMEGA, S_THETA, S_TAU, S_SIGMA, S_WPEND, S_ETASUM, S_K, S_INV1PT, S_ACCEPT, S_ETABAR, S_DEN, S_ETASUM_PREV, S_CURV };
 
 #define HIP_TRY(expr)                                                   \
     do {                                                                \
@@ -153,8 +153,9 @@ inline int rows_grid(int64_t rows) { return rows > 0 ? grid_for(rows) : 0; }    
 extern "C" {
 
 // 18: pdlp_batch_* (batched solves over one matrix); pdlp_batch_attach_matrices, pdlp_batch_product, pdlp_halpern_iterate, then
-//     pdlp_pack_tile_items / pdlp_attach_packed_items (7-byte items on the float32 path; struct pdlp_tiles is unchanged) and
-//     pdlp_halpern_fixed_point joined them without a change to any existing signature or struct, so the number stands
+//     pdlp_pack_tile_items / pdlp_attach_packed_items (7-byte items on the float32 path; struct pdlp_tiles is unchanged),
+//     pdlp_halpern_fixed_point, the pdlp_*objective_matrix* calls and pdlp_objective_iterate joined them without a change to any
+//     existing signature or struct, so the number stands
 // 17: pdlp_peer_* (direct exchange over HIP IPC), PDLP_OPT_BEGIN_INLINE
 // 16: pdlp_set_option (the library reads no environment variables), pdlp_mv_product, pdlp_mv_combine, pdlp_vec_sqdist,
 //     pdlp_probe_gather, pdlp_tile_limits reports the threads per workgroup, pdlp_primal_half_piece / pdlp_dual_half_piece (results
@@ -407,6 +408,7 @@ int pdlp_set_objective_matrix(pdlp_handle h, const int64_t* rowptr, const int32_
         if (rc != PDLP_OK) return rc;
     } else {
         h->sQ = Schedule();
+        h->obj_mat.part = nullptr;
     }
     drop_graphs(h);
     h->obj_mat.on = on;
@@ -631,6 +633,20 @@ int pdlp_iterate(pdlp_handle h, int iters, int adaptive)
     if (h->comm) return iterate_sharded(h, iters, adaptive);
     if (!whole_problem(h)) return PDLP_ERR_STATE;   // sharded without a communicator: the caller does the exchange
     return iterate_single(h, iters, adaptive);
+}
+
+// The adaptive iteration of a handle with a sparse quadratic objective: a mode of its own beside pdlp_iterate, whose refusal of
+// adaptive != 0 on such a handle stands.  The forms without it are those without Q (pdlp_set_objective_matrix), and a handle on which
+// the Halpern iteration has run since the last pdlp_set_iterate (PDLP_AVG holds its candidate, not an average).
+int pdlp_objective_iterate(pdlp_handle h, int iters)
+{
+    if (!h || iters < 0) return PDLP_ERR_INVALID;
+    if (!h->obj_mat.on || !plain_single(h) || h->graph_ok || h->carry.halpern || mid_split_product(h)) return PDLP_ERR_STATE;
+    h->carry.buffers_reassigned();
+    char rname[64];
+    if (g_roctx.level > 0) std::snprintf(rname, sizeof rname, "pdlp: %d adaptive iterations (quadratic objective)", iters);
+    Range range(rname, h->stream);
+    return DISPATCH(h, objective_iterate_t, h, iters);
 }
 
 int pdlp_fixed_advance(pdlp_handle h, int iters)

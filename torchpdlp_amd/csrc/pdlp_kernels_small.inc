@@ -44,15 +44,24 @@ template <typename T> __global__ void k_fixed_advance(double* sc, int iters)
 // pdhg.py:107-112: weight of the new iterate, eta_total, eta <- eta_hat.
 // pw03 / pw06 = (k + 1)^-0.3 / ^-0.6 of the reference's 1-based k of this step (k1 = sc[S_K] + 1): passed in so that the
 // one-workgroup kernel can evaluate the two double-precision pow() calls while its partial sums are still on their way
-template <typename T> __device__ void adaptive_rule(double* sc, const double* red, double k1, double pw03, double pw06)
+// QMAT (pdlp_objective_iterate: the linearised step of a sparse quadratic objective): red[3] holds the curvature dx'Q dx measured
+// along the step, and the bound gains it -- eta_bar = (omega ||dx||^2 + ||dy||^2 / omega) / (2 |dy'K dx| + max(dx'Q dx, 0)), the
+// descent-lemma condition ||dz||_M^2 >= dx'Q dx, exact for a quadratic (DESIGN.md 4.5.1).  Everything behind eta_bar is the LP's.
+template <typename T, bool QMAT = false> __device__ void adaptive_rule(double* sc, const double* red, double k1, double pw03, double pw06)
 {
     const T eta = (T)sc[S_ETA], omega = (T)sc[S_OMEGA];
     const T den = (T)2 * (T)red[2];                        // step.py:96
     T eta_bar, t1;
-    if (den != (T)0) {                                     // step.py:99-102
+    [[maybe_unused]] T curv = (T)0, den_abs = (T)0;
+    if constexpr (QMAT) {
+        curv = (T)red[3];
+        den_abs = (T)fabs((double)den) + (curv > (T)0 ? curv : (T)0);
+    }
+    if (QMAT ? den_abs != (T)0 : den != (T)0) {            // step.py:99-102
         const T nx = (T)sqrt(red[0]), ny = (T)sqrt(red[1]);
         const T num = omega * (nx * nx) + (ny * ny) / omega;
-        eta_bar = num / (T)fabs((double)den);
+        if constexpr (QMAT) eta_bar = num / den_abs;
+        else eta_bar = num / (T)fabs((double)den);
         t1 = (T)(1.0 - pw03) * eta_bar;
     } else {                                               // step.py:104-105
         eta_bar = (T)INFINITY;
@@ -72,6 +81,7 @@ template <typename T> __device__ void adaptive_rule(double* sc, const double* re
     sc[S_ACCEPT] = accept ? 1.0 : 0.0;
     sc[S_ETABAR] = (double)eta_bar;
     sc[S_DEN] = (double)den;
+    if constexpr (QMAT) sc[S_CURV] = (double)curv;
 }
 
 // pdlp_adaptive_retry: the trial just taken is discarded (the intended loop of the adaptive step, enhancements/test_ass.py:322-363)
@@ -89,28 +99,36 @@ template <typename T> __global__ void k_adaptive_update(double* sc, const double
 }
 
 // single-rank fusion of pdlp_adaptive_reduce + pdlp_adaptive_update
-template <typename T>
+// QMAT: a third array of partial sums, pq[b][0] of nq_blocks workgroups (the curvature, ObjGradStepEpi), added in the same fixed
+// order into red[3], which nothing else uses while the rule runs
+template <typename T, bool QMAT = false>
 __device__ __forceinline__ void adaptive_reduce_body(const double* __restrict__ pa, int na_blocks, const double* __restrict__ pb, int nb_blocks,
-                                                     double* __restrict__ red, double* __restrict__ sc, int update)
+                                                     double* __restrict__ red, double* __restrict__ sc, int update,
+                                                     const double* __restrict__ pq = nullptr, int nq_blocks = 0)
 {
     // This one-workgroup kernel sits between the two products of EVERY adaptive iteration: on small problems its latency is a
     // tenth of the iteration.  All partial sums of a thread are requested at once (unconditional loads on clamped block indices;
     // the additions keep the plain loop's order), and the three sums share one barrier.
-    __shared__ double dred3[BLOCK / 64][3];
+    __shared__ double dred3[BLOCK / 64][QMAT ? 4 : 3];
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    [[maybe_unused]] double s3 = 0.0;
     constexpr int U = 8;
     const double k1 = sc[S_K] + 1.0;                       // (wave uniform; thread 0 needs it)
     double pw03 = 0.0, pw06 = 0.0;
-    const int nmax = na_blocks > nb_blocks ? na_blocks : nb_blocks;
+    int nmax = na_blocks > nb_blocks ? na_blocks : nb_blocks;
+    if constexpr (QMAT) nmax = nq_blocks > nmax ? nq_blocks : nmax;
     const int la = na_blocks > 0 ? na_blocks - 1 : 0, lb = nb_blocks > 0 ? nb_blocks - 1 : 0;
+    [[maybe_unused]] const int lq = nq_blocks > 0 ? nq_blocks - 1 : 0;
     for (int base = 0; base < nmax; base += BLOCK * U) {
         double va[U], vb[U], vc[U];
+        [[maybe_unused]] double vq[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int b = base + u * BLOCK + (int)threadIdx.x;
             va[u] = pa[(size_t)(b < la ? b : la) * NACC];
             vb[u] = pb[(size_t)(b < lb ? b : lb) * NACC];
             vc[u] = pb[(size_t)(b < lb ? b : lb) * NACC + 1];
+            if constexpr (QMAT) vq[u] = pq[(size_t)(b < lq ? b : lq) * NACC];      // (pq has room for one workgroup at least)
         }
         // the two pow() of the rule (hundreds of instructions in double precision) go here: behind the loads' issue, in front of
         // their first use
@@ -123,6 +141,7 @@ __device__ __forceinline__ void adaptive_reduce_body(const double* __restrict__ 
             s0 = b < na_blocks ? s0 + va[u] : s0;
             s1 = b < nb_blocks ? s1 + vb[u] : s1;
             s2 = b < nb_blocks ? s2 + vc[u] : s2;
+            if constexpr (QMAT) s3 = b < nq_blocks ? s3 + vq[u] : s3;
         }
     }
     if (nmax <= 0 && update && threadIdx.x < 64) { pw03 = pow(k1 + 1.0, -0.3); pw06 = pow(k1 + 1.0, -0.6); }      // (no partial sums at all)
@@ -131,24 +150,28 @@ __device__ __forceinline__ void adaptive_reduce_body(const double* __restrict__ 
         s0 += shfl_xor_t(s0, off);
         s1 += shfl_xor_t(s1, off);
         s2 += shfl_xor_t(s2, off);
+        if constexpr (QMAT) s3 += shfl_xor_t(s3, off);
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { dred3[w][0] = s0; dred3[w][1] = s1; dred3[w][2] = s2; }
+    if constexpr (QMAT) { if (lane == 0) dred3[w][3] = s3; }
     __syncthreads();
     if (threadIdx.x == 0) {
         red[0] = dred3[0][0] + dred3[1][0] + dred3[2][0] + dred3[3][0];       // (block_sum's order)
         red[1] = dred3[0][1] + dred3[1][1] + dred3[2][1] + dred3[3][1];
         red[2] = dred3[0][2] + dred3[1][2] + dred3[2][2] + dred3[3][2];
-        if (update) adaptive_rule<T>(sc, red, k1, pw03, pw06);
+        if constexpr (QMAT) red[3] = dred3[0][3] + dred3[1][3] + dred3[2][3] + dred3[3][3];
+        if (update) adaptive_rule<T, QMAT>(sc, red, k1, pw03, pw06);
     }
 }
 
-template <typename T>
+template <typename T, bool QMAT = false>
 __global__ __launch_bounds__(BLOCK) void k_adaptive_reduce_update(const double* __restrict__ pa, int na_blocks,
                                                                   const double* __restrict__ pb, int nb_blocks,
-                                                                  double* __restrict__ red, double* __restrict__ sc, int update)
+                                                                  double* __restrict__ red, double* __restrict__ sc, int update,
+                                                                  const double* __restrict__ pq, int nq_blocks)
 {
-    adaptive_reduce_body<T>(pa, na_blocks, pb, nb_blocks, red, sc, update);
+    adaptive_reduce_body<T, QMAT>(pa, na_blocks, pb, nb_blocks, red, sc, update, pq, nq_blocks);
 }
 
 

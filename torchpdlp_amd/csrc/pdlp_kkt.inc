@@ -37,7 +37,12 @@ template <typename T, bool UNSCALE, bool QUAD> ReportDualEpi<T, UNSCALE, QUAD> r
 // Sparse quadratic objective: a KKT pass or report first forms g = c + Q x of the evaluated point -- one product with Q per pass,
 // also for an average whose other products come out of the running sums -- and x'Qx with it; after the six sums are finished the
 // objective's two slots go from g'x = c'x + x'Qx to the contract's c'x + 1/2 x'Qx and - 1/2 x'Qx (include/pdlp_hip.h).
-template <typename T> int kkt_pass_begin(pdlp_handle h, int ix) { return h->obj_mat.on ? obj_gradient<T, true>(h, ix) : PDLP_OK; }
+template <typename T> int kkt_pass_begin(pdlp_handle h, int ix)
+{
+    if (!h->obj_mat.on) return PDLP_OK;
+    h->carry.gradient_overwritten();       // (also at the current iterate: one rule for every pass)
+    return obj_gradient<T, true>(h, ix);
+}
 inline int kkt_pass_end(pdlp_handle h, int gridA, int gridB)
 {
     const int rc = finalize_kkt(h, gridA, gridB);

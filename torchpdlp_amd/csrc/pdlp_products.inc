@@ -217,7 +217,14 @@ inline int finalize_kkt(pdlp_handle h, int gridA, int gridB)
 inline void launch_adaptive_rule(pdlp_handle h, int advance)
 {
     WITH_T(h->p.dtype, hipLaunchKernelGGL(k_adaptive_reduce_update<T>, dim3(1), dim3(BLOCK), 0, h->stream, h->partA, h->last_gridA, h->partB,
-                                          h->last_gridB, h->red, h->sc, advance));
+                                          h->last_gridB, h->red, h->sc, advance, (const double*)nullptr, 0));
+}
+
+// ... with the curvature of the step product among the sums (pdlp_objective_iterate: always the library's own loop)
+inline void launch_objective_rule(pdlp_handle h)
+{
+    WITH_T(h->p.dtype, hipLaunchKernelGGL((k_adaptive_reduce_update<T, true>), dim3(1), dim3(BLOCK), 0, h->stream, h->partA, h->last_gridA,
+                                          h->partB, h->last_gridB, h->red, h->sc, 1, (const double*)h->obj_mat.part, grid_of(h->sQ, h->nl)));
 }
 
 // f(flags...) with run-time switches as types (std::true_type / std::false_type), in the order given: with_flags(f, a, b) calls
@@ -259,6 +266,15 @@ template <typename T, bool SUM> int obj_gradient(pdlp_handle h, int ix)
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, h->stream, h->partA, grid_of(h->sQ, h->nl), 1, h->red, (int)pdlp_solver::OBJ_XQX);
     HIP_TRY(hipGetLastError());
     return PDLP_OK;
+}
+
+// The step product of the adaptive iteration (pdlp_objective_iterate), behind its primal half-step: g = c + Q x' of the NEW x (still
+// in the "previous" buffers: the dual half-step swaps the roles) over the g of the old x, and the partial sums of the curvature
+// dx'Q dx into the handle's own array -- partA holds ||dx||^2 and partB will hold the dual half's sums when the rule reads all three
+template <typename T> int obj_gradient_step(pdlp_handle h)
+{
+    ObjGradStepEpi<T> e{(const T*)h->p.c, xloc<T>(h, h->ix_prev), xloc<T>(h, h->ix_cur), (T*)h->lam_prev};
+    return launch_obj_matrix<T>(h, h->xb[h->ix_prev], e, h->obj_mat.part);
 }
 
 // the end of a KKT pass or report over g: the objective's slots from g'x to the contract's c'x + 1/2 x'Qx (k_obj_matrix_finish)
@@ -308,10 +324,12 @@ template <typename T> int primal_half_t(pdlp_handle h, int adaptive)
     const PieceCtl pc = piece_ctl(h, h->sKT, src < 0);
     if (pc.skip) return PDLP_OK;                             // (all of this half-step went out with piece 0)
     // sparse quadratic objective: the linearised step takes the gradient c + Q x of the current x where it takes c -- one more product
-    // ahead of EVERY primal half-step, the vector-pass form over a kept K'y included
-    if (h->obj_mat.on) {
+    // ahead of EVERY primal half-step, the vector-pass form over a kept K'y included.  (The adaptive half-step reaches this function
+    // from pdlp_objective_iterate alone, which has seen to the gradient itself: carried from its last step product, or formed.)
+    if (h->obj_mat.on && !adaptive) {
         const int rc = obj_gradient<T, false>(h, h->ix_cur);
         if (rc != PDLP_OK) return rc;
+        h->carry.gradient_overwritten();       // (g of the x this half-step leaves)
     }
     if (h->obj_diag) return with_flags([&](auto A) { return primal_half_e<T, A.value, false, true>(h, src, ksum, pc); }, adaptive);
     // (inside the direct exchange the epilogue also stores xbar into the peers: its own instantiations)

@@ -86,8 +86,15 @@ int upload_schedules(pdlp_handle h, const std::vector<int64_t>& rpK, const std::
 
 // The third schedule, of the objective's matrix Q (pdlp_set_objective_matrix): the same tables, carved out of the caller's `work` in
 // the order low words, block pairs, long-row tables.  objective_matrix_layout is the one place that knows the sizes (the size query
-// and the setter both call it).
-struct ObjMatrixLayout { int64_t rplo, blk, lch, lrow, lptr, longpart, bytes; };
+// and the setter both call it).  At the end: the partial sums of the step product's curvature (pdlp_objective_iterate) -- partA and
+// partB hold the half-steps' sums when the step-size rule reads all three -- for as many workgroups as a product with Q can have
+// (grid_of(sQ, n): at most MAX_GRID row-block workgroups and LONG_GRID of the long rows, and never more than there is work).
+struct ObjMatrixLayout { int64_t rplo, blk, lch, lrow, lptr, longpart, part, bytes; };
+inline int64_t objective_part_blocks(int64_t n, int64_t nnz)
+{
+    const int64_t work = max_blocks(n, nnz) + max_chunks(nnz), lg = (max_long(nnz) + BLOCK - 1) / BLOCK;
+    return (work < MAX_GRID ? work : MAX_GRID) + (lg < LONG_GRID ? lg : LONG_GRID);
+}
 inline ObjMatrixLayout objective_matrix_layout(int64_t n, int64_t nnz, int64_t es)
 {
     ObjMatrixLayout L{};
@@ -98,6 +105,7 @@ inline ObjMatrixLayout objective_matrix_layout(int64_t n, int64_t nnz, int64_t e
     L.lrow = c.take(max_long(nnz) * 4);
     L.lptr = c.take((max_long(nnz) + 1) * 4);
     L.longpart = c.take(max_chunks(nnz) * es);
+    L.part = c.take(objective_part_blocks(n, nnz) * NACC * 8);
     L.bytes = c.off;
     return L;
 }
@@ -111,7 +119,7 @@ int upload_objective_schedule(pdlp_handle h, const std::vector<int64_t>& rp, cha
     sc.lch = (int64_t*)(work + L.lch); sc.lrow = (int32_t*)(work + L.lrow); sc.lptr = (int32_t*)(work + L.lptr);
     sc.longpart = (void*)(work + L.longpart);
     const int rc = upload_schedule(h, sc, rp, n);
-    if (rc == PDLP_OK) h->sQ = sc;
+    if (rc == PDLP_OK) { h->sQ = sc; h->obj_mat.part = (double*)(work + L.part); }
     return rc;
 }
 

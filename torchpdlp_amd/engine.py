@@ -232,10 +232,11 @@ class PdlpEngine(KernelChoice, Exchange):
         symmetric and positive semidefinite (the caller's duty), in the engine's scaling when it has one (``Scaling.scale(...,
         quad_matrix=)``: ``D_col Q D_col``).  ``None`` takes it away.  Validated here (``quad.check_quad_matrix``: ``ValueError``);
         float32 / float64 engines on one GPU without graph replay -- the library refuses the others (``PdlpError``).  While set,
-        ``iterate`` takes the linearised step (fixed step only; the caller keeps ``rules.qp_eta``), ``kkt`` / ``report`` give the
-        quadratic problem's objectives (``p = c'x + 1/2 x'Qx``, ``d_adj`` with ``-1/2 x'Qx``) and reduced costs
-        ``project_lambda_box(c + Qx - K'y)``, and the adaptive step, ``halpern_iterate``, ``detect_infeasibility``, the population
-        calls and the batch calls raise ``PdlpError``."""
+        ``iterate`` takes the linearised step (fixed step only; the caller keeps ``rules.qp_eta``) and ``objective_iterate`` the same
+        step under its own adaptive rule, ``kkt`` / ``report`` give the quadratic problem's objectives (``p = c'x + 1/2 x'Qx``,
+        ``d_adj`` with ``-1/2 x'Qx``) and reduced costs ``project_lambda_box(c + Qx - K'y)``, and the LP's adaptive step
+        (``iterate(n, True)``), ``halpern_iterate``, ``detect_infeasibility``, the population calls and the batch calls raise
+        ``PdlpError``."""
         from .quad import check_quad_matrix
         if Q is None:
             N.check(self.lib.pdlp_set_objective_matrix(self.h, None, None, None, None, 0), "pdlp_set_objective_matrix")
@@ -380,7 +381,7 @@ class PdlpEngine(KernelChoice, Exchange):
         N.check(self.lib.pdlp_get_scalars(self.h, out), "pdlp_get_scalars")
         names = ("eta", "omega", "theta", "tau", "sigma", "w_pending", "eta_sum", "k", "inv1pt", "accepted", "eta_bar",
                  "denominator")
-        return {k: out[i] for i, k in enumerate(names)}
+        return dict({k: out[i] for i, k in enumerate(names)}, curvature=out[N.S_CURV])
 
     # ---- iterations ---------------------------------------------------------------------------------
     def iterate(self, iters: int, adaptive: bool):
@@ -399,6 +400,14 @@ class PdlpEngine(KernelChoice, Exchange):
             self._iterate_loop(iters, adaptive)
         else:
             N.check(self.lib.pdlp_iterate(self.h, iters, int(adaptive)), "pdlp_iterate")
+
+    def objective_iterate(self, iters: int):
+        """``iters`` adaptive iterations of the linearised step of an engine with ``quad_matrix`` (``pdlp_objective_iterate``,
+        include/pdlp_hip.h), no host synchronisation: the step-size rule of ``iterate(iters, True)`` with the curvature ``dx'Q dx``
+        measured along the step in its denominator, at the fixed step's three products per iteration.  ``scalars()`` reports the last
+        iteration's ``"accepted"``, ``"eta_bar"``, ``"denominator"`` (``2 dy'K dx``) and ``"curvature"``.  ``flush_average(True)``,
+        ``restart`` and ``set_omega`` as for an adaptive LP.  ``PdlpError`` without ``quad_matrix``."""
+        N.check(self.lib.pdlp_objective_iterate(self.h, int(iters)), "pdlp_objective_iterate")
 
     def halpern_iterate(self, iters: int):
         """``iters`` iterations of the restarted, reflected Halpern iteration (``pdlp_halpern_iterate``, include/pdlp_hip.h), no host

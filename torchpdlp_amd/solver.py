@@ -17,7 +17,7 @@ from . import _native as N
 from .engine import Comm, PdlpEngine
 from .rules import (STATUS_KKT_LIMIT, STATUS_SOLVED, STATUS_TIME_LIMIT, fixed_point_error, fixed_point_restart_decision,   # noqa: F401
                     kkt_error, np_type, previous_kkt_matters, primal_weight, qp_eta, restart_decision, start_eta, start_omega, terminated)
-from .compose import HALPERN_REFUSED, check_composition     # noqa: F401  (HALPERN_REFUSED: importable from here)
+from .compose import HALPERN_REFUSED, check_composition, check_quad_step     # noqa: F401  (HALPERN_REFUSED: importable from here)
 from .quad import check_quad_diag, check_quad_matrix
 from .ranged import check_row_upper, norm_vector as ranged_norm_vector
 from .sparse import CsrPair, as_vec, resolve_device     # noqa: F401  (resolve_device: api.py and callers take it from here)
@@ -92,12 +92,17 @@ class PdhgDriver:
     A sparse quadratic objective (the engine's ``quad_matrix``): the engine takes the linearised step, whose fixed step size
     ``rules.qp_eta(sigma, quad_norm, omega)`` depends on the primal weight -- ``start`` takes ``quad_norm`` (the estimate of ``||Q||_2``)
     and ``after_restart`` sets the step anew (``eng.set_step``) where it would set the primal weight alone (``eng.set_omega``).  A
-    ``trace`` receives every step size set under ``"eta"``.  Fixed step, averaged PDHG only.
+    ``trace`` receives every step size set under ``"eta"``.  Averaged PDHG only; ``adaptive`` stays refused.
+    ``quad_step="adaptive"`` (default "fixed" = the sentences above): a segment is ``eng.objective_iterate`` -- the linearised step
+    under the step-size rule whose denominator carries the measured curvature ``dx'Q dx`` (include/pdlp_hip.h,
+    pdlp_objective_iterate).  The start step is ``rules.qp_eta`` as before; from there the rule owns the step size,
+    so a restart that changes the primal weight sets the weight alone (``eng.set_omega``) and the average is flushed as for an
+    adaptive LP solve, whose KKT-pass accounting this mode has.  ``ValueError`` without a ``quad_matrix`` engine.
     """
 
     def __init__(self, eng: PdlpEngine, restart_period=40, primal_update=False, adaptive=False, precondition=False,
                  tol=1e-4, verbose=False, trace=None, infeasibility_detect=False, infeas_tol=1e-4, adaptive_retry=False,
-                 halpern=False, halpern_restart="kkt"):
+                 halpern=False, halpern_restart="kkt", quad_step="fixed"):
         self.eng, self.period = eng, int(restart_period)
         self.halpern = bool(halpern)
         self.fixed_point = check_halpern_restart(halpern_restart, self.halpern) == "fixed_point"
@@ -110,6 +115,7 @@ class PdhgDriver:
         check_composition(quad_diag=getattr(eng, "quad_diag", None) is not None, **form)
         self.quad = getattr(eng, "quad_matrix", None) is not None
         check_composition(quad_matrix=self.quad, halpern=self.halpern, adaptive=adaptive, **form)
+        self.quad_adaptive = check_quad_step(quad_step, self.quad) == "adaptive"     # (the rule owns eta: objective_iterate)
         self.sigma = self.quad_norm = None                                  # the norm estimates the step rule of quad_matrix keeps
         self.kkt_prev_cand = None                                           # Halpern: the candidate's KKT error at the previous check
         self.infeasibility_detect, self.infeas_tol = bool(infeasibility_detect), float(infeas_tol)
@@ -216,6 +222,9 @@ class PdhgDriver:
                     eng.adaptive_retry()
                 self.j += trials
                 self.trials += trials
+        elif self.quad_adaptive:
+            eng.objective_iterate(iters)
+            self.j += iters
         else:
             eng.iterate(iters, self.adaptive)
             self.j += iters
@@ -298,7 +307,7 @@ class PdhgDriver:
             # the current iterate first: its pass keeps K'y, which closes the running sum of K'y_k -- the averaged iterate then
             # needs no product at all (K x_avg and K'y_avg come out of the sums; include/pdlp_hip.h, pdlp_flush_average)
             r_cur = eng.kkt(N.CUR, self.omega)                              # pdhg.py:122-125
-            eng.flush_average(self.adaptive)
+            eng.flush_average(self.adaptive or self.quad_adaptive)
             eng.compute_average()                                           # pdhg.py:118-119
             r_avg = eng.kkt(N.AVG, self.omega)
             k_cur, k_avg = t(r_cur["kkt"]), t(r_avg["kkt"])
@@ -340,7 +349,7 @@ class PdhgDriver:
             dx2, dy2 = eng.restart_distance()
             omega_before = self.omega
             self.omega = primal_weight(dx2, dy2, self.omega, 0.5, t)
-            if self.quad and self.omega != omega_before:
+            if self.quad and not self.quad_adaptive and self.omega != omega_before:
                 self._set_quad_step(self.k)          # (the step of the linearised iteration depends on the primal weight)
             else:
                 eng.set_omega(self.omega)
@@ -410,21 +419,22 @@ def estimate_quad_norm(eng: PdlpEngine, b0=None, power_iters=100, seed=None) -> 
 def run_pdlp(eng: PdlpEngine, max_kkt=100_000, tol=1e-4, verbose=True, restart_period=40, precondition=False,
              primal_update=False, adaptive=False, time_limit=3600, time_used=0, x_init=None, y_init=None,
              b0=None, sigma=None, power_iters=100, seed=None, trace=None, infeasibility_detect=False, infeas_tol=1e-4,
-             adaptive_retry=False, *, report=None, halpern=False, halpern_restart="kkt", quad_norm=None):
+             adaptive_retry=False, *, report=None, halpern=False, halpern_restart="kkt", quad_norm=None, quad_step="fixed"):
     """The outer loop over an existing engine.  Returns (x_local, prim_obj, k, n, j, status, total_time).
     ``report``: a dict that receives ``PdlpEngine.report`` of the returned iterate (this rank's blocks; of the un-preconditioned
     problem when ``precondition``) whatever the status, and ``q_norm`` / ``c_norm`` as the termination test used them -- in the
     style of ``trace``.  ``halpern``: the restarted, reflected Halpern iteration (``PdhgDriver``); the returned iterate is then the
     candidate of the last restart or, when the run ends between restarts, of the last iteration.  ``halpern_restart``: "kkt" or
     "fixed_point", the quantity its restart checks look at (``PdhgDriver``).  ``quad_norm``: overrides the estimate of ``||Q||_2`` of an
-    engine with a sparse quadratic objective (``estimate_quad_norm``), as ``sigma`` overrides that of ``||K||_2``."""
+    engine with a sparse quadratic objective (``estimate_quad_norm``), as ``sigma`` overrides that of ``||K||_2``.  ``quad_step``:
+    "fixed" or "adaptive", the step rule of such an engine (``PdhgDriver``)."""
     t0 = time.time()
     check_halpern_restart(halpern_restart, halpern)
     if adaptive_retry and (getattr(eng, "delta", False) or infeasibility_detect):
         raise ValueError("adaptive_retry works on float32 / float64 engines without the infeasibility detector")
     drv = PdhgDriver(eng, restart_period, primal_update=primal_update, adaptive=adaptive, precondition=precondition, tol=tol,
                      verbose=verbose, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
-                     adaptive_retry=adaptive_retry, halpern=halpern, halpern_restart=halpern_restart)
+                     adaptive_retry=adaptive_retry, halpern=halpern, halpern_restart=halpern_restart, quad_step=quad_step)
     if sigma is None:                                                       # pdhg.py:22
         sigma = estimate_sigma(eng, b0, power_iters, seed)
     if drv.quad and quad_norm is None:
@@ -480,7 +490,8 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
                    precondition=False, primal_update=False, adaptive=False, data_precond=None, infeasibility_detect=False,
                    infeas_tol=1e-4, time_limit=3600, time_used=0, x_init=None, y_init=None, *, b0=None, sigma=None,
                    seed=None, trace=None, comm=None, precision=None, adaptive_retry=False, report=None,
-                   halpern=False, q_upper=None, quad_diag=None, halpern_restart="kkt", quad_matrix=None, quad_norm=None):
+                   halpern=False, q_upper=None, quad_diag=None, halpern_restart="kkt", quad_matrix=None, quad_norm=None,
+                   quad_step="fixed"):
     """Drop-in for the reference's ``pdlp_algorithm`` (primal_dual_hybrid_gradient.py:7) on one MI355X.
 
     ``K`` may be a dense / COO torch tensor (as the reference takes), a scipy sparse matrix or a
@@ -540,7 +551,12 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     ``precondition`` pass the scaled matrix (``Scaling.scale(..., quad_matrix=)``: ``D_col Q D_col``).  Works with ``precondition``,
     ``primal_update``, ``q_upper``, ``quad_diag`` and ``x_init`` / ``y_init`` in float32 and float64; ``ValueError`` (before any device
     work) for a malformed matrix and together with ``adaptive``, ``halpern``, ``adaptive_retry``, ``infeasibility_detect``,
-    ``precision="mixed"`` or ``comm``.
+    ``precision="mixed"`` or ``comm``.  ``quad_step="adaptive"`` (default "fixed"): the same linearised step under an adaptive step
+    size -- the reference's rule (step.py:91-115) with the curvature measured along the step in its denominator,
+    ``eta_bar = (omega ||dx||^2 + ||dy||^2 / omega) / (2 |dy'K dx| + max(dx'Q dx, 0))``, at the same three products per iteration
+    (DESIGN.md 4.5.1); it starts from ``rules.qp_eta`` and composes with everything ``quad_matrix`` composes with.  ``ValueError``
+    (before any device work) for another value, without ``quad_matrix``, and together with anything ``quad_matrix`` refuses
+    (``adaptive`` included: that switch is the LP's rule).
 
     ``comm`` (a ``Comm``, or ``True`` for the default ``torch.distributed`` group): every rank calls with the SAME
     full problem and the same ``seed``/``b0``; each keeps its row blocks of K and K', the iterations exchange
@@ -548,6 +564,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
     """
     from .distributed import gather_report, gather_solution, shard_engine, start_blocks
     check_halpern_restart(halpern_restart, halpern)
+    check_quad_step(quad_step, quad_matrix is not None)
     check_composition(halpern=halpern, q_upper=q_upper is not None, quad_diag=quad_diag is not None,
                       quad_matrix=quad_matrix is not None, adaptive=adaptive, adaptive_retry=adaptive_retry, infeasibility_detect=infeasibility_detect, mixed=precision is not None, comm=comm not in (None, False))
     q_upper = check_row_upper(q, q_upper, m_ineq)
@@ -588,7 +605,7 @@ def pdlp_algorithm(K, m_ineq, c, q, l, u, device=None, max_kkt=100_000, tol=1e-4
         primal_update=primal_update, adaptive=adaptive, time_limit=time_limit, time_used=time_used, x_init=x_init, y_init=y_init,
         b0=b0, sigma=sigma, seed=seed, trace=trace, infeasibility_detect=infeasibility_detect, infeas_tol=infeas_tol,
         adaptive_retry=adaptive_retry, report=report, halpern=halpern, halpern_restart=halpern_restart,
-        **({} if quad_matrix is None else dict(quad_norm=quad_norm)))
+        **({} if quad_matrix is None else dict(quad_norm=quad_norm, quad_step=quad_step)))
     if report is not None:
         report.update(gather_report(eng, report, Kp.n, Kp.m))
     return gather_solution(eng, x, Kp.n).view(-1, 1), obj, k, n, j, status, total
