@@ -385,9 +385,14 @@ def exact_product(A, v):
     prod = A.data * v[A.indices]
     assert np.array_equal(prod.astype(np.float64), prod) and A.data.dtype == np.float64
     ip = A.indptr
-    ref = np.array([math.fsum(prod[ip[r]:ip[r + 1]]) for r in range(A.shape[0])])
-    mag = np.array([math.fsum(np.abs(prod[ip[r]:ip[r + 1]])) for r in range(A.shape[0])])
-    return ref, mag, np.diff(ip)
+    items = np.diff(ip)
+    ref = np.zeros(A.shape[0])
+    ref[items == 1] = prod[ip[:-1][items == 1]]            # (rows of one item: the exact product itself; of none: 0)
+    mag = np.abs(ref)
+    for r in np.flatnonzero(items > 1):
+        ref[r] = math.fsum(prod[ip[r]:ip[r + 1]])
+        mag[r] = math.fsum(np.abs(prod[ip[r]:ip[r + 1]]))
+    return ref, mag, items
 
 
 def product_bound(prec, mag, items):

@@ -93,6 +93,14 @@ class KernelChoice:
     def _time_spmv(self, transpose: int, vin: torch.Tensor, out: torch.Tensor, reps: int = 3) -> float:
         return self._timed(lambda: N.check(self.lib.pdlp_spmv(self.h, int(transpose), vin.data_ptr(), out.data_ptr()), "pdlp_spmv"), reps)
 
+    def schedule_info(self, transpose: int) -> torch.Tensor:
+        """The CSR kernel's row blocks of K (``transpose`` 0) or K' as the handle holds them (``pdlp_schedule_info``): an int64 view of
+        shape (blocks + 1, 2) into the workspace, (first row, first non-zero) of every block and (rows, non-zeros) as the end"""
+        nb, bp = C.c_int32(0), C.c_void_p()
+        N.check(self.lib.pdlp_schedule_info(self.h, int(transpose), C.byref(nb), C.byref(bp)), "pdlp_schedule_info")
+        off = bp.value - self.workspace.data_ptr()
+        return self.workspace[off:off + (nb.value + 1) * 16].view(torch.int64).view(-1, 2)
+
     def attach_sorted(self, transpose: int, on: bool = True, force: bool = True):
         """Column-sorted copy of every row block's items for the CSR kernel (``pdlp_attach_sorted``; the format and when it pays:
         ``tiled.sorted_row_blocks``): for matrices whose entries cluster (banded, block structured) a wave's gathers then touch a
@@ -106,17 +114,14 @@ class KernelChoice:
         _, ci, va = self.KT if transpose else self.K
         if int(va.numel()) == 0:
             return
-        nb, bp = C.c_int32(0), C.c_void_p()
-        N.check(self.lib.pdlp_schedule_info(self.h, transpose, C.byref(nb), C.byref(bp)), "pdlp_schedule_info")
-        off = bp.value - self.workspace.data_ptr()
-        blk = self.workspace[off:off + (nb.value + 1) * 16].view(torch.int64).view(-1, 2)
+        blk = self.schedule_info(transpose)
         built = _tiled.sorted_row_blocks(blk[:, 1], ci, va, force)       # (column 1: first non-zero of every block, and the end)
         if built is None:
             return
         sidx, sval, cbase, n_sorted = built
         N.check(self.lib.pdlp_attach_sorted(self.h, transpose, sidx.data_ptr(), sval.data_ptr(), cbase.data_ptr()), "pdlp_attach_sorted")
         self._sorted[transpose] = (sidx, sval, cbase)              # keep the arrays alive
-        self.kernels[transpose] = f"csr, sorted row blocks ({n_sorted} of {nb.value})"
+        self.kernels[transpose] = f"csr, sorted row blocks ({n_sorted} of {blk.shape[0] - 1})"
 
     def attach_tiles(self, transpose: int, t: Optional["_tiled.Tiles"]):
         if t is None:
